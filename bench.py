@@ -8,6 +8,12 @@ configuration BASELINE.json's metric is quoted on: toy_mvn_target(1024), n_chain
 SliceSampler(w=10, p=20, n_passes=3), seed=1, synthetic (states drawn from split RNG streams).
 Replica states are resident in HBM before the timed region starts.
 
+A plain run does what the headline needs: set up and prepare the input, --warmup scans, the --steps timed scans (`value`,
+`ms_per_step`, and the `roofline` of the dominant kernel read off those same scans), then the line.  `--full` adds everything
+else the line has carried: the timed scans again without HIP events, a 256-scan long_run, the round-trip leg, value_unprepared,
+hbm_kernels, extra_configs, the restated CPU baseline and, with N > 1, the parallelism-invariance check and the boundary-exchange
+timing.  `--dump-outputs DIR` writes what the last timed scan left (states, chains, RNG words, recorders) as DIR/<name>.npy.
+
 N > 1: one process per GPU.  Started as plain `python bench.py --gpus N` this process only LAUNCHES: it touches no
 GPU, spawns N fresh children (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in their environment), relays rank 0's JSON
 line and exits non-zero if any child fails.  Started under `python -m torch.distributed.run --nproc-per-node N` the
@@ -50,8 +56,15 @@ def parse_args():
                     help="untimed preparation of the synthetic input before --warmup: this many scans from the initial states, reduce + schedule "
                          "adaptation, this many scans again (the states of a run in progress: a schedule change is followed by ~20 scans "
                          "that cost 2 %% more, tools/bench_equilibration.py).  0 = the order of rounds 1-5: warm-up, then the adaptation")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the untimed hbm_kernels / extra_configs blocks")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the same scans without HIP events, the 256-scan long_run, the round-trip leg, "
+                         "value_unprepared, hbm_kernels, extra_configs, the CPU baseline; with N > 1 the parallelism-invariance check and "
+                         "the boundary-exchange timing.  Without it a run sets up, warms up, times --steps scans and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed scans, write what the last one left to its caller as DIR/<name>.npy (float64): the replica "
+                         "states (a fixed, seeded sample of rows when they exceed 48 MB), chains, RNG words, and the recorders of the timed scans")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the untimed value_unprepared / hbm_kernels / extra_configs blocks")
     ap.add_argument("--same-device", action="store_true",
                     help="TEST ONLY: every rank uses HIP device 0 (the control plane then runs over gloo, and the data path needs an "
                          "RCCL stand-in that accepts two ranks on one device: $PTE_RCCL_LIB=tests/fakerccl/libfakerccl.so); "
@@ -60,9 +73,12 @@ def parse_args():
                     help="watchdog: a rank (or the launcher) that is still running after this many seconds reports it and exits "
                          "non-zero instead of sitting in a collective for ever")
     ap.add_argument("--round-trip-rounds", type=int, default=15,
-                    help="untimed leg after the timed region: rounds 1..R of the reference's round loop with schedule "
+                    help="with --full: untimed leg after the timed region: rounds 1..R of the reference's round loop with schedule "
                          "adaptation; the round-trip rate is read off the last round (2^R scans).  0 = skip")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def launch(args):
@@ -362,6 +378,35 @@ def extra_configs(P):
     return [run_extra_config(P, cfg, static.get(cfg[0])) for cfg in extra_config_list(P)]
 
 
+DUMP_STATE_BYTES = 48 * 1000 * 1000   # --dump-outputs: the replica states up to this size; beyond it a fixed, seeded sample of rows (64 MB in all)
+
+
+def dump_outputs(out_dir, states, red):
+    """--dump-outputs DIR: what the timed scans hand their caller after the last one, as float64 .npy files -- the replica states x
+    (x_rows: which replicas they are), the chain each replica holds, its two RNG words as four exact 32-bit halves, and the recorders
+    of the timed scans as pte_reduce returns them.  The input is seeded (seed=1, synthetic), so two builds compare file for file."""
+    import numpy as np
+    x, chain, rng = states
+    rows = np.arange(x.shape[0])
+    cap = max(1, DUMP_STATE_BYTES // max(8 * x.shape[1], 1))
+    if x.shape[0] > cap:
+        rows = np.sort(np.random.default_rng(20240601).choice(x.shape[0], size=cap, replace=False))
+    rng = np.asarray(rng, dtype=np.uint64)
+    halves = np.stack([rng >> np.uint64(32), rng & np.uint64(0xFFFFFFFF)], axis=-1).reshape(len(rng), -1)
+    f64 = lambda *a: np.stack([np.asarray(v, dtype=np.float64) for v in a])
+    arrays = {
+        "x": x[rows], "x_rows": rows, "chain": chain, "rng_words": halves,
+        "swap_acceptance_pr": f64(*red.swap_acceptance_pr),          # [mean; n] per pair
+        "log_sum_ratio": f64(*red.log_sum_ratio),                    # [up; n up; down; n down] per pair
+        "round_trip": f64(*red.round_trip),                          # [tempered restarts, round trips]
+        "explorer_acceptance_pr": f64(*red.explorer_acceptance_pr),  # [mean; n] per replica
+        "explorer_n_steps": f64(*red.explorer_n_steps),              # [sum; n] per replica
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     args = parse_args()
     world_env = os.environ.get("WORLD_SIZE")
@@ -382,7 +427,7 @@ def main():
     if world != args.gpus:
         raise SystemExit("bench.py: --gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
     # the CPU baseline leg pins one OpenMP thread per physical core; libgomp reads this when it is first mapped
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         os.environ.setdefault("OMP_PLACES", "cores")
         os.environ.setdefault("OMP_PROC_BIND", "close")
 
@@ -453,7 +498,8 @@ def main():
     if world > 1 and "FALLBACK" not in transport:
         path, ver = _engine.comm_library()               # the file ncclSend / ncclRecv really come from, and what it says it is
         transport_library = {"path": path, "nccl_version": ver}
-        invariant = invariance_check(P, d, total_chains, args.explorer, rank, world, local_rank, dist)
+        if args.full:
+            invariant = invariance_check(P, d, total_chains, args.explorer, rank, world, local_rank, dist)
 
     # warmup: W scans (first RCCL transfers open their connections here: at least two even scans per boundary whatever --warmup says),
     # then one reduce + schedule adaptation
@@ -491,49 +537,55 @@ def main():
     samples = np.sort(eng.timing_samples(tkind))
     scans_timed = eng.scan_loop_info()[2] if scan_loop else ex_n
     eng.timing_reset(False)
-    # the same K scans once more WITHOUT HIP events in the stream (an event pair costs stream time per launch): the cross-check of
-    # what the instrumentation costs the timed region above; `value` stays the instrumented, contract-timed pass
-    sync()
-    t0 = time.perf_counter()
-    runner.run_scans(1, K)
-    sync()
-    dt_noev = time.perf_counter() - t0
-    if dist is not None:
-        t = torch.tensor([dt_noev], dtype=torch.float64, device="cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt_noev = float(t.item())
-    # the driver's --steps 20 makes the timed region ~17 ms: when it is shorter than 100 ms the same loop runs once more for 256
-    # scans, bracketed the same way, and the line carries both (`value` stays the requested-K pass)
-    long_run = None
-    if dt < 0.1 and K < 256:
-        K2 = 256
+    red = reduce_recorders(pt)          # the recorders of exactly the K timed scans (and it empties them)
+    ss_sum = red.explorer_n_steps[0]
+    scans_recorded = K
+    if args.dump_outputs:
+        states = runner.states()        # (with N > 1 a gather over the ranks: every rank takes part)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, states, red)
+    dt_noev, long_run, boundary_exchange = None, None, None
+    if args.full:
+        # the same K scans once more WITHOUT HIP events in the stream (an event pair costs stream time per launch): the cross-check of
+        # what the instrumentation costs the timed region above; `value` stays the instrumented, contract-timed pass
         sync()
         t0 = time.perf_counter()
-        runner.run_scans(1, K2)
+        runner.run_scans(1, K)
         sync()
-        dt2 = time.perf_counter() - t0
+        dt_noev = time.perf_counter() - t0
         if dist is not None:
-            t = torch.tensor([dt2], dtype=torch.float64, device="cuda")
+            t = torch.tensor([dt_noev], dtype=torch.float64, device="cuda")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            dt2 = float(t.item())
-        long_run = {"steps": K2, "ms_per_step": dt2 / K2 * 1e3, "value": total_chains * K2 / dt2, "hip_events": False,
-                    "note": "the requested --steps make a timed region under 100 ms; the same scan loop for 256 scans, same barriers"}
-    scans_recorded = 2 * K + (256 if long_run else 0)
-    # the boundary exchange as the engine's stream sees it (HIP events around ncclGroupStart .. ncclGroupEnd, one sample per even scan):
-    # the first thing to read on a real multi-GPU node -- the 8-32 KiB message against the 0.8 / 3 ms kernel
-    boundary_exchange = None
-    if world > 1 and "RCCL" in transport and "FALLBACK" not in transport:
-        eng.timing_reset(True)
-        runner.run_scans(1, 16)
-        bs = np.sort(eng.timing_samples(3))
-        eng.timing_reset(False)
-        scans_recorded += 16
-        if len(bs):
-            boundary_exchange = {"samples": int(len(bs)), "us_min_median_max": [float(bs[0]) * 1e3, float(bs[len(bs) // 2]) * 1e3, float(bs[-1]) * 1e3],
-                                 "message_bytes_per_side": int(8 * (d + 8)),
-                                 "note": "HIP events on the engine's stream around the grouped ncclSend / ncclRecv of the ranks' boundary replicas (rank 0's view)"}
-    red = reduce_recorders(pt)
-    ss_sum, ss_n = red.explorer_n_steps
+            dt_noev = float(t.item())
+        # the driver's --steps 20 makes the timed region ~17 ms: when it is shorter than 100 ms the same loop runs once more for 256
+        # scans, bracketed the same way, and the line carries both (`value` stays the requested-K pass)
+        if dt < 0.1 and K < 256:
+            K2 = 256
+            sync()
+            t0 = time.perf_counter()
+            runner.run_scans(1, K2)
+            sync()
+            dt2 = time.perf_counter() - t0
+            if dist is not None:
+                t = torch.tensor([dt2], dtype=torch.float64, device="cuda")
+                dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                dt2 = float(t.item())
+            long_run = {"steps": K2, "ms_per_step": dt2 / K2 * 1e3, "value": total_chains * K2 / dt2, "hip_events": False,
+                        "note": "the requested --steps make a timed region under 100 ms; the same scan loop for 256 scans, same barriers"}
+        scans_recorded += K + (256 if long_run else 0)
+        # the boundary exchange as the engine's stream sees it (HIP events around ncclGroupStart .. ncclGroupEnd, one sample per even scan):
+        # the first thing to read on a real multi-GPU node -- the 8-32 KiB message against the 0.8 / 3 ms kernel
+        if world > 1 and "RCCL" in transport and "FALLBACK" not in transport:
+            eng.timing_reset(True)
+            runner.run_scans(1, 16)
+            bs = np.sort(eng.timing_samples(3))
+            eng.timing_reset(False)
+            scans_recorded += 16
+            if len(bs):
+                boundary_exchange = {"samples": int(len(bs)), "us_min_median_max": [float(bs[0]) * 1e3, float(bs[len(bs) // 2]) * 1e3, float(bs[-1]) * 1e3],
+                                     "message_bytes_per_side": int(8 * (d + 8)),
+                                     "note": "HIP events on the engine's stream around the grouped ncclSend / ncclRecv of the ranks' boundary replicas (rank 0's view)"}
+        ss_sum = ss_sum + reduce_recorders(pt).explorer_n_steps[0]
     boundary = [int(getattr(runner, "n_boundary_swaps", 0))]
     ranks_seen = int(getattr(runner, "n_ranks_seen", 1))
     if dist is not None:
@@ -544,6 +596,8 @@ def main():
     # round-trip half of the metric (src/recorders/RoundTripRecorder.jl:23): untimed, the reference's own
     # round loop -- rounds 1..R with schedule adaptation after each -- the rate is n_round_trips(last round) / 2^R
     rt = None
+    if not args.full:
+        rt_rounds = 0
     if rt_rounds > 0:          # keep the untimed leg near 90 s whatever the workload: rounds 1..R run 2^(R+1) - 2 scans (same R on every rank: dt is the max over ranks)
         import math
         rt_rounds = max(1, min(rt_rounds, int(math.floor(math.log2(90.0 / max(dt / K, 1e-6)))) - 1))
@@ -597,7 +651,7 @@ def main():
     out = {
         "metric": "replica-steps/sec (explore+swap), toy_mvn d=%d, n_chains=%d; round-trip rate" % (d, total_chains),
         "value": value, "unit": "replica-steps/s", "n_gpus": world, "steps": K, "warmup": W,
-        "ms_per_step": dt / K * 1e3, "ms_per_step_without_hip_events": dt_noev / K * 1e3, "long_run": long_run,
+        "ms_per_step": dt / K * 1e3, "ms_per_step_without_hip_events": dt_noev / K * 1e3 if dt_noev is not None else None, "long_run": long_run,
         "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
         "dtype": "f64", "data": "synthetic",
         "config": {"workload": "toy_mvn_target(%d), n_chains=%d per GPU x %d GPU, %s, seed=1, DEO swaps every scan"
@@ -608,6 +662,7 @@ def main():
                    "preparation": ("untimed, before --warmup: %d scans from the initial states, reduce + schedule adaptation, %d scans under the adapted "
                                    "schedule; then %d warm-up scans, then the %d timed scans (no adaptation in between)" % (prep, prep, W_run, K)) if prep else
                                   "none: %d warm-up scans from the initial states, reduce + schedule adaptation, then the %d timed scans" % (W_run, K),
+                   "full": bool(args.full),      # False: the headline only (the legs --full adds are null or absent)
                    "transport_library": transport_library, "boundary_exchange": boundary_exchange, "parallelism_invariant": invariant,
                    "env_overrides": {k: os.environ[k] for k in ("PTE_RCCL_LIB", "PTE_BENCH_BACKEND") if os.environ.get(k)},      # ($PTE_LIB is not read any more: the bench runs the in-tree library)
                    **({"same_device_test_run": "every rank on HIP device 0 with an RCCL stand-in ($PTE_RCCL_LIB=%s): exercises the "
@@ -637,7 +692,7 @@ def main():
                      "note": "SliceSampler is bound by the instruction issue of ONE wave per replica walking a sequential "
                              "decision chain (3*d coordinate updates, ~6.5 draws each), not by HBM; see DESIGN.md sec. 5"},
     }
-    if rank == 0 and world == 1 and not args.no_extra:
+    if rank == 0 and world == 1 and args.full and not args.no_extra:
         del pt, runner, eng                              # (frees the metric engine's HBM before the 256 MiB one)
         if prep:
             # the order of rounds 1-4 next to the prepared one, in the same line -- a fresh engine, W warm-up scans from the initial
@@ -651,7 +706,7 @@ def main():
         out["hbm_kernels"] = hbm_kernels(P)
         out["extra_configs"] = extra_configs(P)
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1 and args.explorer == "slice":
+        if args.full and not args.no_cpu_baseline and world == 1 and args.explorer == "slice":
             out["cpu_baseline"] = cpu_baseline(d)
             cb = out["cpu_baseline"]
             if cb and cb.get("value"):

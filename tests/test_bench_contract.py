@@ -1,14 +1,45 @@
-"""bench.py's contract with the driver: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line carrying the metric,
-`roofline` and `cpu_baseline`; for N > 1 the process launches its own ranks and fails loudly when a rank fails."""
+"""bench.py's contract with the driver: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line carrying the metric and the
+`roofline` of the timed scans (`--full` adds `cpu_baseline`, `long_run`, the round-trip leg, `hbm_kernels`, `extra_configs`, ...);
+`--dump-outputs DIR` writes what the last timed scan left; for N > 1 the process launches its own ranks and fails loudly when a rank fails."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BASELINE = json.load(open(os.path.join(ROOT, "BASELINE.json")))
+DUMP_NAMES = ("x", "x_rows", "chain", "rng_words", "swap_acceptance_pr", "log_sum_ratio", "round_trip", "explorer_acceptance_pr", "explorer_n_steps")
+
+
+def test_dump_outputs_float64_exact_and_sampled(tmp_path, monkeypatch):
+    """No GPU: --dump-outputs' writer on stand-in arrays -- float64 files only, RNG words exact as 32-bit halves, and states above the size
+    cap reduced to the same seeded sample of rows every time."""
+    import types
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_STATE_BYTES", 40 * 8 * 16)        # 40 rows of 16 coordinates
+    N, d, pairs = 100, 16, 99
+    g = np.random.default_rng(3)
+    x = g.standard_normal((N, d)); chain = g.permutation(N).astype(np.int64)
+    rng = g.integers(0, 2 ** 63, size=(N, 2), dtype=np.int64).astype(np.uint64) * np.uint64(2) + np.uint64(1)
+    red = types.SimpleNamespace(swap_acceptance_pr=(g.random(pairs), np.arange(pairs)), log_sum_ratio=tuple(g.random(pairs) for _ in range(4)),
+                                round_trip=(3, 2), explorer_acceptance_pr=(g.random(N), np.full(N, 5)), explorer_n_steps=(g.random(N), np.full(N, 5)))
+    for out in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / out), (x, chain, rng), red)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(n + ".npy" for n in DUMP_NAMES)
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b), f
+    rows = np.load(tmp_path / "a" / "x_rows.npy").astype(np.int64)
+    assert len(rows) == 40 and len(set(rows)) == 40 and np.array_equal(np.load(tmp_path / "a" / "x.npy"), x[rows])
+    w = np.load(tmp_path / "a" / "rng_words.npy").astype(np.uint64).reshape(N, 2, 2)
+    assert np.array_equal((w[..., 0] << np.uint64(32)) | w[..., 1], rng)
+    assert np.array_equal(np.load(tmp_path / "a" / "chain.npy"), chain.astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "a" / "round_trip.npy"), [3.0, 2.0])
 
 
 def test_launcher_spawns_ranks_and_propagates_their_failure():
@@ -31,7 +62,7 @@ def test_world_size_must_match_gpus():
 
 @pytest.mark.gpu
 def test_single_gpu_line_has_the_contract_fields():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full",
                         "--round-trip-rounds", "4"], capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -66,7 +97,7 @@ def test_single_gpu_line_has_the_contract_fields():
     ratio = j["ms_per_step_without_hip_events"] / j["ms_per_step"]
     if not (0.8 < ratio < 1.25):
         p2 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "64", "--warmup", "4", "--round-trip-rounds", "0",
-                             "--no-extra", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
+                             "--full", "--no-extra", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
         assert p2.returncode == 0, p2.stderr[-3000:]
         j2 = json.loads([ln for ln in p2.stdout.splitlines() if ln.startswith("{")][-1])
         ratio = j2["ms_per_step_without_hip_events"] / j2["ms_per_step"]
@@ -114,3 +145,36 @@ def test_single_gpu_line_has_the_contract_fields():
     assert j["config"]["chains_per_gpu"] == 1024 and j["config"]["waves_per_simd"] == 1.0
     assert j["config"]["env_overrides"] == {k: os.environ[k] for k in ("PTE_RCCL_LIB", "PTE_BENCH_BACKEND") if os.environ.get(k)}
     assert j["config"]["transport_library"] is None and j["config"]["parallelism_invariant"] is None       # (single GPU)
+
+
+def _plain_run(out_dir):
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--dump-outputs", out_dir],
+                       capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_plain_line_is_the_headline_and_its_outputs_repeat(tmp_path):
+    """Without --full: the headline fields, --steps timed scans, none of the legs --full adds; --dump-outputs writes the states and
+    recorders of the timed scans, bit for bit the same in a second run with the same arguments."""
+    j = _plain_run(str(tmp_path / "a"))
+    assert j["metric"] == BASELINE["metric"] and j["unit"] == "replica-steps/s" and j["dtype"] == "f64" and j["higher_is_better"] is True
+    assert j["n_gpus"] == 1 and j["steps"] == 5 and j["warmup"] == 2 and j["config"]["full"] is False
+    assert abs(j["value"] - 1024 * 5 / (j["ms_per_step"] * 5e-3)) < 1e-6 * j["value"]
+    assert j["roofline"]["kernel"] == "k_scans_slice8" and j["roofline"]["scans_per_launch"] == 5
+    assert j["cpu_baseline"] is None and j["long_run"] is None and j["round_trip"] is None and j["ms_per_step_without_hip_events"] is None
+    assert not {"hbm_kernels", "extra_configs", "value_unprepared", "vs_restated_cpu_port"} & set(j)
+    _plain_run(str(tmp_path / "b"))
+    total = 0
+    for n in DUMP_NAMES:
+        a, b = np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, b, equal_nan=True), n
+        total += a.nbytes
+    assert total <= 64e6
+    x, chain = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "a" / "chain.npy")
+    assert x.shape == (1024, 1024) and np.all(np.isfinite(x))
+    assert np.array_equal(np.sort(chain), np.arange(chain.min(), chain.min() + 1024))
+    assert np.load(tmp_path / "a" / "explorer_n_steps.npy").shape == (2, 1024)

@@ -143,7 +143,7 @@ def test_bench_two_ranks_on_one_device(tmp_path):
     """bench.py --gpus 2 end to end (self-launch, RcclShard, agreed transport, timed region, gathers, teardown)."""
     fake = build_fakerccl()
     env = dict(os.environ, PTE_RCCL_LIB=fake)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--same-device", "--steps", "6", "--warmup", "2",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--same-device", "--steps", "6", "--warmup", "2", "--full",
                         "--round-trip-rounds", "4", "--no-cpu-baseline", "--timeout-s", "400"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
     line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])

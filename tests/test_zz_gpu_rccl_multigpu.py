@@ -208,7 +208,7 @@ def test_real_rccl_bench_line_two_gpus():
     for k in ("PTE_RCCL_LIB", "PTE_LIB", "PTE_BENCH_BACKEND"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "16", "--warmup", "4", "--round-trip-rounds", "0",
-                        "--no-cpu-baseline", "--timeout-s", "600"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline", "--timeout-s", "600"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
     line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     c = line["config"]

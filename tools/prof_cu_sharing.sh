@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_cu_sharing; mkdir -p $O
 rocprofv3 -L 2>/dev/null | grep -oE "\b(SQC?_[A-Z0-9_]*(ICACHE|IFETCH|LDS|INST_CYCLES|WAIT_INST|BUSY_CY|INSTS_SMEM|DCACHE)[A-Z0-9_]*)\b" | sort -u | tr '\n' ' ' > $O/counters.txt; echo >> $O/counters.txt
 for N in 256 1024; do
-  A="--no-cpu-baseline --no-extra --round-trip-rounds 0 --steps 64 --warmup 64 --prepare 0 --chains $N"
+  A="--full --no-cpu-baseline --no-extra --round-trip-rounds 0 --steps 64 --warmup 64 --prepare 0 --chains $N"
   rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE -d $O -o lds$N -- python3 $R/bench.py $A > $O/lds$N.log 2>&1
   rocprofv3 --pmc SQ_WAVES SQ_IFETCH SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY -d $O -o if$N -- python3 $R/bench.py $A > $O/if$N.log 2>&1
 done

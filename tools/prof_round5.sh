@@ -5,7 +5,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; TAG=${1:-r05}; S=${2:-256}
 O=$R/gpurun_out/prof_$TAG; mkdir -p $O
-A="--no-cpu-baseline --no-extra --round-trip-rounds 0 --steps $S --warmup $S"
+A="--full --no-cpu-baseline --no-extra --round-trip-rounds 0 --steps $S --warmup $S"
 rocprofv3 --kernel-trace --stats -d $O -o stats -- python3 $R/bench.py $A > $O/stats.log 2>&1
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_BRANCH SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY -d $O -o sq -- python3 $R/bench.py $A > $O/sq.log 2>&1
 rocprofv3 --pmc FETCH_SIZE -d $O -o fetch -- python3 $R/bench.py $A > $O/fetch.log 2>&1

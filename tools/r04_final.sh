@@ -2,7 +2,7 @@
 # every config, chains-per-GPU table, the lone-wave microbenchmarks of round 4.  (The GPU test suite is run separately.)
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r04_final; mkdir -p $O
 cd $R
-python bench.py > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"; python -c "
+python bench.py --full > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"; python -c "
 import json; j=json.load(open('$O/bench_line.json')); print({k:j[k] for k in ('value','ms_per_step','ms_per_step_without_hip_events','round_trip_rate','vs_baseline')}); print(j['long_run']); print(j['hbm_kernels']['k_explore_toy'], j['hbm_kernels']['k_init']); print([(c['config'][:12], round(c['ms_per_scan'],3)) for c in j['extra_configs']])"
 python bench.py --scaling strong --gpus 1 --no-extra --no-cpu-baseline --round-trip-rounds 0 --steps 8 --warmup 2 > $O/bench_strong_1gpu.json 2>> $O/bench.err; python -c "
 import json; j=json.load(open('$O/bench_strong_1gpu.json')); print('strong anchor', j['value'], j['ms_per_step'], j['roofline']['kernel'])"

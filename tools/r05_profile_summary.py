@@ -10,7 +10,7 @@ def main():
     d = int(sys.argv[4]) if len(sys.argv) > 4 else 1024
     def q(db, sql):
         con = sqlite3.connect(os.path.join(O, db)); rows = con.execute(sql).fetchall(); con.close(); return rows
-    print("# rocprofv3 passes of `python3 bench.py --no-cpu-baseline --no-extra --round-trip-rounds 0 --steps %d --warmup %d` (tools/prof_round5.sh):" % (S, S))
+    print("# rocprofv3 passes of `python3 bench.py --full --no-cpu-baseline --no-extra --round-trip-rounds 0 --steps %d --warmup %d` (tools/prof_round5.sh):" % (S, S))
     print("# warm-up, timed and event-free passes are three launches of the fused scan loop, %d scans each (the two shorter dispatches before them: bench.py's untimed preparation, 2 x 64 scans); N = %d chains, d = %d" % (S, N, d))
     for db in ("stats_results.db", "sq_results.db"):
         rows = q(db, "select name, (end-start)/1e6 from kernels where name like '%k_scans%' order by start")

@@ -28,9 +28,9 @@ for mode in weak strong; do
   for g in 1 2 4 8; do
     [ "$g" -gt "$MAXG" ] && continue
     [ "$g" -gt "$NG" ] && { echo "skip $mode $g: only $NG GPU(s)"; continue; }
-    extra="--no-cpu-baseline --no-extra --round-trip-rounds 0 --steps 64 --warmup 8"
+    extra="--full --no-cpu-baseline --no-extra --round-trip-rounds 0 --steps 64 --warmup 8"
     [ "$mode" = strong ] && extra="$extra --scaling strong"
-    [ "$mode" = weak ] && [ "$g" = 1 ] && extra="--steps 64 --warmup 8"          # the full single-GPU line once (CPU baseline, extra configs)
+    [ "$mode" = weak ] && [ "$g" = 1 ] && extra="--full --steps 64 --warmup 8"   # the full single-GPU line once (CPU baseline, extra configs)
     timeout 1500 python bench.py --gpus "$g" $extra > "$OUT/scale_${mode}_${g}.json" 2> "$OUT/scale_${mode}_${g}.err" \
       || echo "FAILED: $mode $g (see $OUT/scale_${mode}_${g}.err)"
   done
