@@ -59,7 +59,9 @@ enum {
                                             pte_create / pte_set_variational_reference refuse those, the caller keeps the CPU path */
     PTE_EXPLORER_AUTOMALA = 3,           /* AutoMALA:     src/explorers/AutoMALA.jl:29-294                 */
     PTE_EXPLORER_ISING_METROPOLIS = 4,   /* IsingMetropolis: examples/ising.jl:91-116 (n_steps in slice_n_passes) */
-    PTE_EXPLORER_MALA     = 5            /* MALA:         src/explorers/MALA.jl:19-105 (am_* fields; step size fixed) */
+    PTE_EXPLORER_MALA     = 5,           /* MALA:         src/explorers/MALA.jl:19-105 (am_* fields; step size fixed) */
+    PTE_EXPLORER_AAPS     = 6            /* AAPS:         src/explorers/AAPS.jl (apogee-to-apogee path sampler; am_step_size, am_preconditioner / am_p0 / am_p1,
+                                            aaps_K; step size fixed; MVN and funnel paths, dim <= 512, single explorer)      */
 };
 enum {                                   /* Inputs.record (src/pt/Inputs.jl:57-62)                         */
     PTE_RECORD_ROUND_TRIP    = 1u << 0,  /* round_trip     src/recorders/RoundTripRecorder.jl              */
@@ -150,7 +152,7 @@ typedef struct pte_config {
     /* Debug / bisecting: PTE_KERNEL_*.  The kernel is chosen by this field only -- the library never reads the
      * environment -- and pte_create fails on a value this build does not contain.  pte_kernel_name reports the choice. */
     int32_t  debug_kernel;
-    int32_t  reserved0;
+    int32_t  aaps_K;             /* AAPS: K, the number of segments besides the current one (AAPS.jl; default 5, 0..64)      */
 } pte_config;
 
 typedef struct pte_engine pte_engine;

@@ -21,10 +21,12 @@
 #include "pte_slice5.hpp"
 #include "pte_slice7.hpp"
 #include "pte_slice8.hpp"
-#ifdef PTE_SPLIT_LANGEVIN          // the product build: the Langevin-family kernels are the library's second translation unit (pte_langevin.hip)
-#include "pte_automala_params.hpp"
+#ifdef PTE_SPLIT_LANGEVIN          // the product build: the Langevin-family kernels are the library's second translation unit (pte_langevin.hip),
+#include "pte_automala_params.hpp" // the AAPS kernels its third (pte_aaps.hip)
+#include "pte_aaps_params.hpp"
 #else                              // tools / development builds: one translation unit
 #include "pte_langevin_launch.hpp"
+#include "pte_aaps.hpp"
 #endif
 #include "pte_ising.hpp"
 #if defined(PTE_PROFILE_AM)               // debug builds only (tools/prof_automala.py): 12 words per wave, section times of k_explore_automala
@@ -267,6 +269,7 @@ int check_device_error(pte_engine *h) {
     case ERR_SLICE_MAX_ITER: return fail(h, "Maximum number of iterations reached in slice_shrink! (chain %d, index %d)", err[1], err[2]);
     case ERR_AM_DENSITY: return fail(h, "AutoMALA can only be called on a configuration of positive density. (chain %d)", err[1]);
     case ERR_AM_STEP: return fail(h, "Could not find a positive step size (chain %d)", err[1]);
+    case ERR_AAPS_DENSITY: return fail(h, "AAPS can only be called on a configuration of positive density. (chain %d)", err[1]);
     case ERR_HANDSHAKE_TIMEOUT: return fail(h, "pte_run_scans: chain %d gave up waiting for its swap partner inside the one-launch scan loop (every workgroup had arrived: "
                                                "a wave died or was descheduled for seconds)", err[1]);
     default: return fail(h, "device error %d", err[0]);
@@ -321,6 +324,14 @@ static int launch_langevin(pte_engine *h, int E, int target, bool slice, bool fu
     if (h->ev_open && h->ev_ext && !h->ev_ext_done) { L.ext = true; L.ev_a = h->events.back().a; L.ev_b = h->events.back().b; h->ev_ext_done = true; }
     if (E == 16 && !slice && !L.one_wave16) HIP_OK(h, hipMemsetAsync(h->dev.pace, 0, sizeof(unsigned int), h->stream));      // k_explore_langevin_mw: its workgroups count their refreshes here
     if (langevin_launch(L, h->dev, ap)) return fail(h, "this build holds no Langevin-family kernels (PTE_DEV_NO_LANGEVIN)");
+    return 0;
+}
+
+// one launch of k_explore_aaps (pte_aaps_params.hpp); like launch_langevin, the open timing bracket's events ride on it
+static int launch_aaps(pte_engine *h, int E, int target, bool full, int64_t N, const AapsParams &ap) {
+    AapsLaunch L{E, target, full, (unsigned)N, h->stream, false, nullptr, nullptr};
+    if (h->ev_open && h->ev_ext && !h->ev_ext_done) { L.ext = true; L.ev_a = h->events.back().a; L.ev_b = h->events.back().b; h->ev_ext_done = true; }
+    if (aaps_launch(L, h->dev, ap)) return fail(h, "this build holds no AAPS kernel for dim %lld", (long long)h->d);
     return 0;
 }
 
@@ -429,6 +440,18 @@ int launch_explorer_kind(pte_engine *h, int64_t scan, int kind) {
         time_begin(h, 0, true);
         const bool full = h->d == 64 * (int64_t)E;       // no ragged last block: the instantiation without per-lane validity masks
         if (launch_langevin(h, E, fun ? TGT_FUNNEL : TGT_MVN, false, full, N, ap)) return 1;
+        time_end(h);
+        break;
+    }
+    case PTE_EXPLORER_AAPS: {                            // one AAPS transition per replica (pte_aaps.hpp); the step size is not adapted
+        AapsParams ap{};
+        ap.step_size = h->cfg.am_step_size; ap.K = h->cfg.aaps_K; ap.precond = h->cfg.am_preconditioner;
+        ap.p0 = h->cfg.am_p0; ap.p1 = h->cfg.am_p1;
+        ap.target_std = h->have_target_std ? h->d_target_std : nullptr;
+        ap.ref_prec = h->cfg.target_params[0]; ap.log3 = std::log(3.0);
+        const int E = h->d <= 64 ? 1 : h->d <= 128 ? 2 : h->d <= 256 ? 4 : 8;
+        time_begin(h, 0, true);
+        if (launch_aaps(h, E, h->cfg.target == PTE_TARGET_FUNNEL ? TGT_FUNNEL : TGT_MVN, h->d == 64 * (int64_t)E, N, ap)) return 1;
         time_end(h);
         break;
     }
@@ -688,6 +711,7 @@ int pte_default_config(pte_config *c) {
     c->slice_w = 10.0; c->slice_p = 20; c->slice_n_passes = 3; c->slice_max_iter = 1024;
     c->am_base_n_refresh = 3; c->am_exponent_n_refresh = 0.35; c->am_step_size = 1.0;
     c->am_p0 = 1.0 / 3.0; c->am_p1 = 1.0 / 3.0; c->am_preconditioner = 2;
+    c->aaps_K = 5;                                   // AAPS.jl
     c->rank = 0; c->world_size = 1;
     return 0;
 }
@@ -708,6 +732,20 @@ int pte_create(const pte_config *cfg, pte_engine **out) {
     const bool swapper = cfg->target == PTE_TARGET_TEST_SWAPPER;
     const bool funnel = cfg->target == PTE_TARGET_FUNNEL;
     const bool ising = cfg->target == PTE_TARGET_ISING;
+    if (cfg->explorer == PTE_EXPLORER_AAPS || cfg->explorer2 == PTE_EXPLORER_AAPS) {       // AAPS (pte_aaps.hpp): one wave per replica, one explorer
+        if (cfg->explorer2 != PTE_EXPLORER_NONE)
+            return fail(nullptr, "pte_create: AAPS is not available as half of a Compose on the device");
+        if (!funnel && cfg->target != PTE_TARGET_MVN_SCALED_PRECISION)
+            return fail(nullptr, "pte_create: AAPS is implemented on the scaled-precision MVN and funnel paths only (got target %d)", cfg->target);
+        if (cfg->dim < 1 || cfg->dim > 512)
+            return fail(nullptr, "pte_create: AAPS keeps the replica in the registers of one wave, dim must be in 1..512 (got %lld)", (long long)cfg->dim);
+        if (cfg->aaps_K < 0 || cfg->aaps_K > 64)
+            return fail(nullptr, "pte_create: AAPS needs aaps_K in 0..64 (got %d)", cfg->aaps_K);
+        if (!(cfg->am_step_size > 0) || !std::isfinite(cfg->am_step_size))
+            return fail(nullptr, "pte_create: AAPS needs a positive finite step size (got %g)", cfg->am_step_size);
+        if (cfg->debug_kernel != 0)
+            return fail(nullptr, "pte_create: AAPS has one kernel; debug_kernel must be 0 (got %d)", cfg->debug_kernel);
+    }
     if (ising) {
         const int64_t L = (int64_t)std::llround(std::sqrt((double)cfg->dim));
         if (L < 2 || L * L != cfg->dim || cfg->dim > 65536) return fail(nullptr, "pte_create: Ising needs dim = base_length^2 <= 65536");
@@ -720,8 +758,9 @@ int pte_create(const pte_config *cfg, pte_engine **out) {
         return fail(nullptr, "pte_create: target %d has no device log-potential; use the reference CPU path", cfg->target);
     auto grad_based = [](int k) { return k == PTE_EXPLORER_AUTOMALA || k == PTE_EXPLORER_MALA; };
     const bool uses_grad = grad_based(cfg->explorer) || grad_based(cfg->explorer2);
+    const bool aaps = cfg->explorer == PTE_EXPLORER_AAPS;
     auto on_path = [&](int k) { return grad_based(k) || k == PTE_EXPLORER_SLICE; };
-    if (funnel && !(on_path(cfg->explorer) && (cfg->explorer2 == PTE_EXPLORER_NONE || on_path(cfg->explorer2))))
+    if (funnel && !aaps && !(on_path(cfg->explorer) && (cfg->explorer2 == PTE_EXPLORER_NONE || on_path(cfg->explorer2))))
         return fail(nullptr, "pte_create: the funnel path is implemented for AutoMALA / MALA / SliceSampler (and Compose of them); use the reference CPU path");
     if ((uses_grad || funnel) && (cfg->dim < 1 || cfg->dim > 1024))
         return fail(nullptr, "pte_create: AutoMALA / MALA (and every explorer of the funnel path) keep the replica in registers, dim must be in 1..1024 (got %lld)", (long long)cfg->dim);
@@ -736,7 +775,7 @@ int pte_create(const pte_config *cfg, pte_engine **out) {
         return fail(nullptr, "pte_create: dim must be in 1..4096 (got %lld)", (long long)cfg->dim);
     if (swapper && cfg->explorer != PTE_EXPLORER_NONE)
         return fail(nullptr, "pte_create: TestSwapper has no explorer");
-    if (!swapper && !ising && cfg->explorer != PTE_EXPLORER_TOY && cfg->explorer != PTE_EXPLORER_SLICE && !grad_based(cfg->explorer))
+    if (!swapper && !ising && cfg->explorer != PTE_EXPLORER_TOY && cfg->explorer != PTE_EXPLORER_SLICE && !grad_based(cfg->explorer) && !aaps)
         return fail(nullptr, "pte_create: explorer %d is not implemented on the device", cfg->explorer);
     if ((cfg->record_flags & PTE_RECORD_TRACES_EXTENDED) && !(cfg->record_flags & PTE_RECORD_TRACES))
         return fail(nullptr, "pte_create: PTE_RECORD_TRACES_EXTENDED needs PTE_RECORD_TRACES");
@@ -858,7 +897,7 @@ int pte_create(const pte_config *cfg, pte_engine **out) {
     h->step_size = cfg->am_step_size;
     // n_refresh = base_n_refresh * ceil(Int, dim^exponent_n_refresh)  (AutoMALA.jl:120)
     h->am_n_refresh = cfg->am_base_n_refresh * (int)std::ceil(std::pow((double)(d > 0 ? d : 1), cfg->am_exponent_n_refresh));
-    if (uses_grad && cfg->am_preconditioner != 0) e.record_flags |= PTE_RECORD_ONLINE;   // _transformed_online (GradientBasedSampler.jl:19-25)
+    if ((uses_grad || aaps) && cfg->am_preconditioner != 0) e.record_flags |= PTE_RECORD_ONLINE;   // _transformed_online (GradientBasedSampler.jl:19-25)
     e.slot_of_chain = h->slot_map[0]; e.slot_of_chain_alt = h->slot_map[1]; h->slot_cur = 0;
 
     // equally_spaced_schedule (reference src/schedules/Schedule.jl:36-44)
@@ -984,7 +1023,7 @@ int pte_set_explorer_adaptation(pte_engine *h, double step_size, const double *t
     if (!h) return 1;
     PTE_ALIVE(h, "pte_set_explorer_adaptation");
     {   // nothing to adapt for SliceSampler / ToyExplorer
-        auto gb = [](int k) { return k == PTE_EXPLORER_AUTOMALA || k == PTE_EXPLORER_MALA; };
+        auto gb = [](int k) { return k == PTE_EXPLORER_AUTOMALA || k == PTE_EXPLORER_MALA || k == PTE_EXPLORER_AAPS; };
         if (!gb(h->cfg.explorer) && !gb(h->cfg.explorer2)) return 0;
     }
     if (!(step_size > 0)) return fail(h, "pte_set_explorer_adaptation: step_size must be > 0");
@@ -1772,6 +1811,7 @@ const char *pte_kernel_name(const pte_engine *h) {
         // "unoptimised" in rounds 1-5 -- survives in the test build as its A/B reference
         if (h->d > 512) return (h->cfg.debug_kernel & PTE_KERNEL_TEST_LANGEVIN_ONE_WAVE) ? "k_explore_automala [test build: one wave, sixteen blocks per lane]" : "k_explore_langevin_mw";
         return "k_explore_automala";
+    case PTE_EXPLORER_AAPS: return "k_explore_aaps";
     case PTE_EXPLORER_ISING_METROPOLIS: {
         const int64_t L = (int64_t)std::llround(std::sqrt((double)h->d));
         return (L % 32 == 0 && h->ising_impl == 0) ? "k_explore_ising_spec" : (L % 32 == 0 && h->ising_impl == 1) ? "k_explore_ising_bits" : "k_explore_ising";
@@ -1994,6 +2034,7 @@ int pte_set_rng_policy(int32_t device, uint32_t policy) {
     if (hipSetDevice(device) != hipSuccess) return fail(nullptr, "pte_set_rng_policy: no HIP device %d", device);
     hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(g_rng_policy), &policy, sizeof policy);
     if (e == hipSuccess) e = (hipError_t)langevin_set_rng_policy(policy);       // the second translation unit's copy of the word
+    if (e == hipSuccess) e = (hipError_t)aaps_set_rng_policy(policy);           // ... and the third's
     if (e == hipSuccess) e = hipDeviceSynchronize();
     return e == hipSuccess ? 0 : fail(nullptr, "pte_set_rng_policy: %s", hipGetErrorString(e));
 }

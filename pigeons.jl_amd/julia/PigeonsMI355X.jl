@@ -35,7 +35,7 @@ const libpte = "libpte.so"
 
 # ---- include/pte.h mirrored ------------------------------------------------------------------------------------------------
 const TARGET_MVN, TARGET_TEST_SWAPPER, TARGET_FUNNEL, TARGET_ISING = Int32(0), Int32(1), Int32(2), Int32(3)
-const EXPLORER_NONE, EXPLORER_TOY, EXPLORER_SLICE, EXPLORER_AUTOMALA, EXPLORER_ISING, EXPLORER_MALA = Int32.((0, 1, 2, 3, 4, 5))
+const EXPLORER_NONE, EXPLORER_TOY, EXPLORER_SLICE, EXPLORER_AUTOMALA, EXPLORER_ISING, EXPLORER_MALA, EXPLORER_AAPS = Int32.((0, 1, 2, 3, 4, 5, 6))
 const RECORD_ROUND_TRIP, RECORD_INDEX_PROCESS, RECORD_ONLINE, RECORD_TRACES, RECORD_ENERGY_AC1, RECORD_TRACES_EXTENDED =
     UInt32.((1, 2, 4, 8, 16, 32))
 const RECORD_REFERENCE_REDUCTION = UInt32(64)   # swap recorders reduced by per-replica Mean / LogSum fits + tree merge, replayed in pte_reduce (include/pte.h)
@@ -69,7 +69,7 @@ Base.@kwdef mutable struct PteConfig
     explorer2::Int32 = EXPLORER_NONE      # Compose(explorer, explorer2)
     n_chains_variational::Int64 = 0       # StabilizedPT with variational == nothing
     debug_kernel::Int32 = 0               # PTE_KERNEL_*: 0 = the default kernel of the explorer (never read from the environment)
-    reserved0::Int32 = 0
+    aaps_K::Int32 = 5                     # AAPS.K (AAPS.jl)
 end
 
 # ---- targets on the device -------------------------------------------------------------------------------------------------
@@ -134,6 +134,14 @@ function set_explorer!(cfg::PteConfig, ex::MALA, slot)
     cfg.am_base_n_refresh = ex.base_n_refresh; cfg.am_exponent_n_refresh = ex.exponent_n_refresh; cfg.am_step_size = ex.step_size
     cfg.am_preconditioner = preconditioner_code(ex.preconditioner)
     return EXPLORER_MALA
+end
+function set_explorer!(cfg::PteConfig, ex::Pigeons.AAPS, slot)       # step size fixed; AAPS alone (pte_create refuses it inside a Compose)
+    cfg.am_step_size = ex.step_size; cfg.aaps_K = ex.K
+    cfg.am_preconditioner = preconditioner_code(ex.preconditioner)
+    if ex.preconditioner isa Pigeons.MixDiagonalPreconditioner
+        cfg.am_p0 = ex.preconditioner.p0; cfg.am_p1 = ex.preconditioner.p1
+    end
+    return EXPLORER_AAPS
 end
 set_explorer!(cfg::PteConfig, ::Nothing, slot) = EXPLORER_NONE
 set_explorer!(cfg::PteConfig, ex, slot) = error("explorer $(typeof(ex)) has no device kernel; keep the CPU path")
@@ -279,7 +287,7 @@ function after_adapt!(pt)
         tempering.schedule.grids
     check(r, ccall((:pte_set_schedule, libpte), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), r.handle, betas, length(betas)))
     for ex in explorers(pt.shared.explorer)
-        ex isa Union{AutoMALA, MALA} || continue
+        ex isa Union{AutoMALA, MALA, Pigeons.AAPS} || continue
         std = ex.estimated_target_std_deviations
         check(r, ccall((:pte_set_explorer_adaptation, libpte), Cint, (Ptr{Cvoid}, Float64, Ptr{Float64}, Int64), r.handle, ex.step_size,
                        std === nothing ? C_NULL : pointer(std), std === nothing ? 0 : length(std)))

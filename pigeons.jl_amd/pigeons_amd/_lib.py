@@ -19,7 +19,7 @@ def use_library(path):
     LIB_PATH = path
 
 TARGET_MVN_SCALED_PRECISION, TARGET_TEST_SWAPPER, TARGET_FUNNEL, TARGET_ISING = 0, 1, 2, 3
-EXPLORER_NONE, EXPLORER_TOY, EXPLORER_SLICE, EXPLORER_AUTOMALA, EXPLORER_ISING_METROPOLIS, EXPLORER_MALA = 0, 1, 2, 3, 4, 5
+EXPLORER_NONE, EXPLORER_TOY, EXPLORER_SLICE, EXPLORER_AUTOMALA, EXPLORER_ISING_METROPOLIS, EXPLORER_MALA, EXPLORER_AAPS = 0, 1, 2, 3, 4, 5, 6
 RECORD_ROUND_TRIP, RECORD_INDEX_PROCESS, RECORD_ONLINE, RECORD_TRACES, RECORD_ENERGY_AC1, RECORD_TRACES_EXTENDED = 1, 2, 4, 8, 16, 32
 RECORD_REFERENCE_REDUCTION = 64      # swap_acceptance_pr / log_sum_ratio by per-replica Mean / LogSum fits and the binary-tree merge, replayed in pte_reduce (include/pte.h)
 ABI_VERSION = 2
@@ -55,7 +55,7 @@ class PteConfig(C.Structure):
         ("am_p0", C.c_double), ("am_p1", C.c_double),
         ("am_preconditioner", C.c_int32),
         ("rank", C.c_int32), ("world_size", C.c_int32), ("explorer2", C.c_int32), ("n_chains_variational", C.c_int64),
-        ("debug_kernel", C.c_int32), ("reserved0", C.c_int32),
+        ("debug_kernel", C.c_int32), ("aaps_K", C.c_int32),
     ]
 
 

@@ -99,7 +99,7 @@ def latest_checkpoint_folder(exec_folder):
 def load_checkpoint(source_exec_folder, round=None, n_rounds_increment=0, **pt_kwargs):
     """PT(source_exec_folder; round) (checkpoint.jl:19-54) [+ increment_n_rounds! :166-189]: a fresh engine whose
     replicas, schedule and explorer adaptation are those of the checkpoint."""
-    from .pt import PT, AutoMALA, MALA, Compose
+    from .pt import PT, AutoMALA, MALA, AAPS, Compose
     round = latest_checkpoint_folder(source_exec_folder) if round is None else round
     if round == 0:
         raise RuntimeError("No checkpoint found for %s (was checkpoint=True set?)" % source_exec_folder)
@@ -131,7 +131,7 @@ def load_checkpoint(source_exec_folder, round=None, n_rounds_increment=0, **pt_k
     def grad_sampler(ex):
         if isinstance(ex, Compose):
             return grad_sampler(ex.first) or grad_sampler(ex.second)
-        return ex if isinstance(ex, (AutoMALA, MALA)) else None
+        return ex if isinstance(ex, (AutoMALA, MALA, AAPS)) else None
     gs = grad_sampler(shared.explorer)
     if gs is not None:
         eng.set_explorer_adaptation(gs.step_size, gs.estimated_target_std_deviations)

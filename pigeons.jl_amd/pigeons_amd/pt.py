@@ -157,6 +157,16 @@ class MALA:
 
 
 @dataclass
+class AAPS:
+    """src/explorers/AAPS.jl: the apogee-to-apogee path sampler (Sherlock, Urbas & Ludkin, JCGS 2023).  One transition per explore!;
+    K segments besides the current one; the step size is NOT adapted, the preconditioner is (as MALA's)."""
+    step_size: float = 1.0
+    K: int = 5
+    preconditioner: Any = field(default_factory=MixDiagonalPreconditioner)
+    estimated_target_std_deviations: Any = None
+
+
+@dataclass
 class Compose:
     """src/explorers/Compose.jl:5-8: deterministic composition, e.g. Compose(SliceSampler(), AutoMALA())"""
     first: Any = None
@@ -372,6 +382,11 @@ class PT:
                             slice_max_iter=ex.max_iter)
             if isinstance(ex, IsingMetropolis):
                 return dict(explorer=_lib.EXPLORER_ISING_METROPOLIS, slice_n_passes=ex.n_steps)
+            if isinstance(ex, AAPS):
+                pc = ex.preconditioner
+                kind = 0 if isinstance(pc, IdentityPreconditioner) else 1 if isinstance(pc, DiagonalPreconditioner) else 2
+                return dict(explorer=_lib.EXPLORER_AAPS, am_step_size=ex.step_size, aaps_K=ex.K, am_preconditioner=kind,
+                            am_p0=getattr(pc, "p0", 0.0), am_p1=getattr(pc, "p1", 0.0))
             if isinstance(ex, (AutoMALA, MALA)):
                 pc = ex.preconditioner
                 kind = 0 if isinstance(pc, IdentityPreconditioner) else 1 if isinstance(pc, DiagonalPreconditioner) else 2
@@ -383,6 +398,8 @@ class PT:
         if isinstance(explorer, Compose):
             if isinstance(explorer.first, Compose) or isinstance(explorer.second, Compose):
                 raise NotImplementedError("nested Compose is not available on the device")
+            if isinstance(explorer.first, AAPS) or isinstance(explorer.second, AAPS):
+                raise NotImplementedError("AAPS is not available as half of a Compose on the device")
             k1, k2 = explorer_kw(explorer.first), explorer_kw(explorer.second)
             shared_keys = (set(k1) & set(k2)) - {"explorer"}
             if any(k1[k] != k2[k] for k in shared_keys):
@@ -513,11 +530,11 @@ def update_variational(pt, reduced):
 
 
 def adapt_explorer(pt, reduced):
-    """adapt_explorer (src/explorers/AutoMALA.jl:70-79, MALA.jl:63-69, Compose.jl:10-14, Preconditioner.jl:54-55)."""
+    """adapt_explorer (src/explorers/AutoMALA.jl:70-79, MALA.jl:63-69, Compose.jl:10-14, Preconditioner.jl:54-55); AAPS as MALA."""
     def adapt_one(ex):
         if isinstance(ex, Compose):
             return Compose(adapt_one(ex.first), adapt_one(ex.second))
-        if not isinstance(ex, (AutoMALA, MALA)) or reduced.am_factors is None:
+        if not isinstance(ex, (AutoMALA, MALA, AAPS)) or reduced.am_factors is None:
             return ex
         std = None
         if not isinstance(ex.preconditioner, IdentityPreconditioner):
@@ -532,6 +549,8 @@ def adapt_explorer(pt, reduced):
                     acc += float(v)
                 new_step = ex.step_size * (acc / float(int(present.sum())))
         adapted.append((new_step, std))
+        if isinstance(ex, AAPS):
+            return AAPS(ex.step_size, ex.K, ex.preconditioner, std)
         return type(ex)(ex.base_n_refresh, ex.exponent_n_refresh, new_step, ex.preconditioner, std)
     adapted = []
     pt.shared.explorer = adapt_one(pt.shared.explorer)

@@ -12,7 +12,8 @@
 #   * rand(rng, a:b) on Int64 ranges and SliceSampler steps on Integer / Bool / mixed states (SliceSampler.jl:65-86, 136-142, 189), which only
 #     the oracle restates (po_rand_range, po_slice_step_mixed): tests/test_oracle_slice_mixed.py::test_*_against_live_reference;
 #   * seeded runs of the real reference: C1 with SliceSampler / ToyExplorer, AutoMALA on the MVN path, a two-leg TestSwapper
-#     run, a C5-shaped Ising run (examples/ising.jl, base_length 8) and a C3-shaped funnel run with AutoMALA.
+#     run, a C5-shaped Ising run (examples/ising.jl, base_length 8) and a C3-shaped funnel run with AutoMALA;
+#   * AAPS: the struct's fields and defaults, a seeded MVN run and single transitions with their momentum and rand(rng, 0:K).
 # Once the file is committed, tests/test_golden.py::test_*_against_live_reference and tests/test_zig_tables.py stop skipping
 # and either go green or name the first differing table entry / draw.
 using Pigeons, SplittableRandoms, Random
@@ -133,6 +134,37 @@ try
     out["slice_mixed"] = slice_mixed(Real[0.25, 3, true], golden_lp_mixed)
 catch err
     out["slice_mixed_error"] = sprint(showerror, err)
+end
+
+# AAPS (src/explorers/AAPS.jl): the device's draw order is this project's specification (DESIGN 4.7, tests/aaps_ref.py), pinned here.  Per
+# transition of a non-reference replica: the stream before the step, the momentum and rand(rng, 0:K) replayed on a copy of that stream
+# (identity preconditioner: no preconditioner draw precedes them), and the state after step!; plus the struct's field names and defaults
+# and a seeded run.  tests/aaps_ref.py replays the transitions from the recorded streams.
+try
+    ex0 = Pigeons.AAPS()
+    out["aaps_struct"] = Dict("fields" => [string(f) for f in fieldnames(typeof(ex0))],
+                              "step_size" => bits(Float64(ex0.step_size)), "K" => Int(ex0.K))
+    out["mvn3_aaps"] = run(target = toy_mvn_target(3), n_chains = 4, n_rounds = 4, explorer = Pigeons.AAPS())
+    pt = pigeons(target = toy_mvn_target(3), n_chains = 4, n_rounds = 1, seed = 1, show_report = false,
+                 explorer = Pigeons.AAPS(preconditioner = Pigeons.IdentityPreconditioner()))
+    ex = pt.shared.explorer
+    transitions = Any[]
+    for t in 1:4, replica in Pigeons.locals(pt.replicas)
+        replica.chain == 1 && continue                      # the reference chain keeps sample_iid!
+        probe = deepcopy(replica.rng)
+        momentum = [randn(probe) for _ in 1:length(replica.state)]
+        kf = rand(probe, 0:ex.K)
+        before = Dict("chain" => replica.chain, "state" => bits(collect(Float64, replica.state)),
+                      "rng" => [string(replica.rng.seed), string(replica.rng.gamma)])
+        Pigeons.step!(ex, replica, pt.shared)
+        push!(transitions, merge(before, Dict("momentum" => bits(momentum), "Kf" => kf,
+                                              "selected" => bits(collect(Float64, replica.state)),
+                                              "final_rng" => [string(replica.rng.seed), string(replica.rng.gamma)])))
+    end
+    out["aaps_transitions"] = Dict("schedule" => bits(pt.shared.tempering.schedule.grids), "step_size" => bits(Float64(ex.step_size)),
+                                   "K" => Int(ex.K), "transitions" => transitions)
+catch err
+    out["aaps_error"] = sprint(showerror, err)
 end
 
 # minimal JSON writer (no extra dependency)
