@@ -45,7 +45,9 @@ enum {
     PTE_TARGET_MVN_SCALED_PRECISION = 0, /* toy_mvn_target: src/paths/ScaledPrecisionNormalPath.jl:5-48   */
     PTE_TARGET_TEST_SWAPPER         = 1, /* TestSwapper:    src/swap/pair_swapper.jl:100-149               */
     PTE_TARGET_FUNNEL               = 2, /* InterpolatingPath(normal ref, Neal's funnel)                   */
-    PTE_TARGET_ISING                = 3  /* InterpolatingPath(Ising(0), Ising(beta)): examples/ising.jl        */
+    PTE_TARGET_ISING                = 3, /* InterpolatingPath(Ising(0), Ising(beta)): examples/ising.jl        */
+    PTE_TARGET_GAUSSIAN_MIXTURE     = 4  /* InterpolatingPath(normal ref, normalised mixture of K <= 8 diagonal Gaussians;
+                                            pte_set_target_mixture): SliceSampler / AutoMALA / MALA / Compose of them, dim <= 512 */
 };
 enum {
     PTE_EXPLORER_NONE     = 0,           /* `nothing` (TestSwapper)                                        */
@@ -214,6 +216,12 @@ int pte_get_traces(const pte_engine *h, double *out, int64_t *n_scans);
  * Funnel target, single engine.  NULL mean / std deactivates. */
 int pte_set_variational_reference(pte_engine *h, const double *mean /*d*/, const double *std_dev /*d*/, int64_t dim,
                                   const int32_t *uses /*N*/);
+/* PTE_TARGET_GAUSSIAN_MIXTURE: the target MixtureModel([MvNormal(means[k], Diagonal(std_devs[k].^2))], weights) (K components of
+ * dimension d, row-major [K][d]; the weights need not sum to 1).  Validates (1 <= K <= 8; weights and std_devs positive and finite; means
+ * finite), uploads and refreshes the swap statistics of the current states; may be called again to replace the mixture.  Until the first
+ * call pte_explore, pte_swap, pte_run_scans and pte_get_state fail.  DESIGN 4.8. */
+int pte_set_target_mixture(pte_engine *h, int64_t n_components, const double *weights /*K*/, const double *means /*K*d*/,
+                           const double *std_devs /*K*d*/);
 int pte_get_state(const pte_engine *h, double *state, int64_t *chain, uint64_t *rng);
 int pte_set_state(pte_engine *h, const double *state, const int64_t *chain, const uint64_t *rng);
 

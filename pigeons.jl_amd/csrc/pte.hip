@@ -24,9 +24,11 @@
 #ifdef PTE_SPLIT_LANGEVIN          // the product build: the Langevin-family kernels are the library's second translation unit (pte_langevin.hip),
 #include "pte_automala_params.hpp" // the AAPS kernels its third (pte_aaps.hip)
 #include "pte_aaps_params.hpp"
+#include "pte_mixture_params.hpp"     // ... and the Gaussian-mixture kernels its fourth (pte_mixture.hip)
 #else                              // tools / development builds: one translation unit
 #include "pte_langevin_launch.hpp"
 #include "pte_aaps.hpp"
+#include "pte_mixture.hpp"
 #endif
 #include "pte_ising.hpp"
 #if defined(PTE_PROFILE_AM)               // debug builds only (tools/prof_automala.py): 12 words per wave, section times of k_explore_automala
@@ -86,6 +88,8 @@ struct pte_engine {
     std::vector<void *> allocs;
     double *d_nhp = nullptr, *d_sd = nullptr, *d_nprec = nullptr, *d_beta = nullptr, *d_target_std = nullptr;
     bool have_target_std = false;
+    double *d_mix = nullptr;        // PTE_TARGET_GAUSSIAN_MIXTURE: [8][ld] means, [8][ld] 1 / std-devs, [8] c_k
+    int mix_K = 0;                  // components; 0 until pte_set_target_mixture
     double step_size = 1.0;
     int am_n_refresh = 0;
     std::vector<double> fac_mean, rev_mean; std::vector<int64_t> fac_n, rev_n;
@@ -209,7 +213,7 @@ int upload_ladder(pte_engine *h) {
             nprec[c] = -prec;
             sd[c] = std::sqrt(prec);
         }
-    } else if (h->cfg.target == PTE_TARGET_FUNNEL) {
+    } else if (h->cfg.target == PTE_TARGET_FUNNEL || h->cfg.target == PTE_TARGET_GAUSSIAN_MIXTURE) {
         for (int64_t c = 0; c < N; ++c) sd[c] = std::sqrt(h->cfg.target_params[0]);   // reference end point
     }
     HIP_OK(h, hipMemcpyAsync(h->d_nhp, nhp.data(), sizeof(double) * N, hipMemcpyHostToDevice, h->stream));
@@ -335,10 +339,30 @@ static int launch_aaps(pte_engine *h, int E, int target, bool full, int64_t N, c
     return 0;
 }
 
+// the mixture's parameters as the kernels read them (d_mix, pte_set_target_mixture)
+static MixParams mixture_params(const pte_engine *h) {
+    MixParams mp;
+    const int64_t ld = h->dev.ld;
+    mp.mu = h->d_mix; mp.inv = h->d_mix + 8 * ld; mp.c = h->d_mix + 16 * ld; mp.K = h->mix_K; mp.ld = ld;
+    return mp;
+}
+// one launch of k_explore_mixture (pte_mixture_params.hpp); like launch_langevin, the open timing bracket's events ride on it
+static int launch_mixture(pte_engine *h, int E, bool slice, bool full, int64_t N, const AmParams &ap) {
+    MixtureLaunch L{E, slice, full, (unsigned)N, h->stream, false, nullptr, nullptr};
+    if (h->ev_open && h->ev_ext && !h->ev_ext_done) { L.ext = true; L.ev_a = h->events.back().a; L.ev_b = h->events.back().b; h->ev_ext_done = true; }
+    if (mixture_launch(L, h->dev, ap, mixture_params(h))) return fail(h, "this build holds no Gaussian-mixture kernel for dim %lld", (long long)h->d);
+    return 0;
+}
+static bool mixture_missing(const pte_engine *h) { return h->cfg.target == PTE_TARGET_GAUSSIAN_MIXTURE && h->mix_K == 0; }
+static int mixture_missing_error(pte_engine *h, const char *what) {
+    return fail(h, "%s: the Gaussian-mixture target has no components yet; call pte_set_target_mixture first", what);
+}
+
 int launch_explorer_kind(pte_engine *h, int64_t scan, int kind);
 int launch_explore(pte_engine *h, int64_t scan) {
     (void)scan;
     const int64_t N = h->K;
+    if (mixture_missing(h)) return mixture_missing_error(h, "pte_explore");
     if ((h->cfg.record_flags & PTE_RECORD_TRACES) && h->scans_in_round >= h->cfg.max_scans_per_round)
         return fail(h, "traces buffer full: %lld scans since the last pte_reduce (max_scans_per_round = %lld)",
                     (long long)h->scans_in_round, (long long)h->cfg.max_scans_per_round);
@@ -385,6 +409,16 @@ int launch_explorer_kind(pte_engine *h, int64_t scan, int kind) {
         time_end(h);
         break;
     case PTE_EXPLORER_SLICE:
+        if (h->cfg.target == PTE_TARGET_GAUSSIAN_MIXTURE) {       // SliceSampler on the mixture's interpolated path: k_explore_mixture's slice mode
+            AmParams ap{};
+            ap.slice = 1; ap.slice_w = h->cfg.slice_w; ap.slice_p = h->cfg.slice_p; ap.slice_n_passes = h->cfg.slice_n_passes;
+            ap.slice_max_iter = h->cfg.slice_max_iter;
+            ap.ref_prec = h->cfg.target_params[0]; ap.log3 = std::log(3.0);
+            time_begin(h, 0, true);
+            if (launch_mixture(h, h->d <= 64 ? 1 : h->d <= 128 ? 2 : h->d <= 256 ? 4 : 8, true, false, N, ap)) return 1;
+            time_end(h);
+            break;
+        }
         if (h->cfg.target == PTE_TARGET_FUNNEL) {
             // SliceSampler on the interpolated path: the register-resident kernel of the Langevin family in its slice mode
             // (full log potential per evaluation, as the reference's slice_sample! does for any log_potential)
@@ -439,7 +473,8 @@ int launch_explorer_kind(pte_engine *h, int64_t scan, int kind) {
         const bool fun = h->cfg.target == PTE_TARGET_FUNNEL;
         time_begin(h, 0, true);
         const bool full = h->d == 64 * (int64_t)E;       // no ragged last block: the instantiation without per-lane validity masks
-        if (launch_langevin(h, E, fun ? TGT_FUNNEL : TGT_MVN, false, full, N, ap)) return 1;
+        if (h->cfg.target == PTE_TARGET_GAUSSIAN_MIXTURE) { if (launch_mixture(h, E, false, full, N, ap)) return 1; }
+        else if (launch_langevin(h, E, fun ? TGT_FUNNEL : TGT_MVN, false, full, N, ap)) return 1;
         time_end(h);
         break;
     }
@@ -732,6 +767,7 @@ int pte_create(const pte_config *cfg, pte_engine **out) {
     const bool swapper = cfg->target == PTE_TARGET_TEST_SWAPPER;
     const bool funnel = cfg->target == PTE_TARGET_FUNNEL;
     const bool ising = cfg->target == PTE_TARGET_ISING;
+    const bool mixture = cfg->target == PTE_TARGET_GAUSSIAN_MIXTURE;
     if (cfg->explorer == PTE_EXPLORER_AAPS || cfg->explorer2 == PTE_EXPLORER_AAPS) {       // AAPS (pte_aaps.hpp): one wave per replica, one explorer
         if (cfg->explorer2 != PTE_EXPLORER_NONE)
             return fail(nullptr, "pte_create: AAPS is not available as half of a Compose on the device");
@@ -746,6 +782,18 @@ int pte_create(const pte_config *cfg, pte_engine **out) {
         if (cfg->debug_kernel != 0)
             return fail(nullptr, "pte_create: AAPS has one kernel; debug_kernel must be 0 (got %d)", cfg->debug_kernel);
     }
+    if (mixture) {          // Gaussian mixture (pte_mixture.hpp): one wave per replica, SliceSampler / AutoMALA / MALA
+        auto on_mix = [](int k) { return k == PTE_EXPLORER_SLICE || k == PTE_EXPLORER_AUTOMALA || k == PTE_EXPLORER_MALA; };
+        if (!on_mix(cfg->explorer) || (cfg->explorer2 != PTE_EXPLORER_NONE && !on_mix(cfg->explorer2)))
+            return fail(nullptr, "pte_create: the Gaussian-mixture path is implemented for SliceSampler / AutoMALA / MALA (and Compose of them) only (got explorers %d, %d)",
+                        cfg->explorer, cfg->explorer2);
+        if (cfg->dim < 1 || cfg->dim > 512)
+            return fail(nullptr, "pte_create: the Gaussian-mixture path keeps the replica in the registers of one wave, dim must be in 1..512 (got %lld)", (long long)cfg->dim);
+        if ((cfg->debug_kernel & ~(PTE_KERNEL_FLAG_BITS | PTE_KERNEL_TEST_BITS)) != 0)
+            return fail(nullptr, "pte_create: debug_kernel %d is not available on the Gaussian-mixture path (one register-resident kernel serves it)", cfg->debug_kernel);
+        if (cfg->n_chains_variational > 0)
+            return fail(nullptr, "pte_create: two-leg tempering (n_chains_variational > 0) is not available on the Gaussian-mixture path");
+    }
     if (ising) {
         const int64_t L = (int64_t)std::llround(std::sqrt((double)cfg->dim));
         if (L < 2 || L * L != cfg->dim || cfg->dim > 65536) return fail(nullptr, "pte_create: Ising needs dim = base_length^2 <= 65536");
@@ -754,7 +802,7 @@ int pte_create(const pte_config *cfg, pte_engine **out) {
                                  "the Ising path is explored by IsingMetropolis only -- use the reference CPU path for Bool / Integer states");
         if (cfg->explorer != PTE_EXPLORER_ISING_METROPOLIS) return fail(nullptr, "pte_create: the Ising path is explored by IsingMetropolis only");
     } else if (cfg->explorer == PTE_EXPLORER_ISING_METROPOLIS) return fail(nullptr, "pte_create: IsingMetropolis needs the Ising target");
-    if (!swapper && !funnel && !ising && cfg->target != PTE_TARGET_MVN_SCALED_PRECISION)
+    if (!swapper && !funnel && !ising && !mixture && cfg->target != PTE_TARGET_MVN_SCALED_PRECISION)
         return fail(nullptr, "pte_create: target %d has no device log-potential; use the reference CPU path", cfg->target);
     auto grad_based = [](int k) { return k == PTE_EXPLORER_AUTOMALA || k == PTE_EXPLORER_MALA; };
     const bool uses_grad = grad_based(cfg->explorer) || grad_based(cfg->explorer2);
@@ -834,7 +882,8 @@ int pte_create(const pte_config *cfg, pte_engine **out) {
         const int64_t lw = (d + 31) / 32;
         e.ld = (lw + 1) / 2; e.sw = e.ld;
     }
-    e.record_flags = cfg->record_flags; e.target = cfg->target; e.test_swapper_pr = cfg->target_params[0];
+    // (the swap and recorder kernels see the mixture as the funnel's interpolated path: suff = sum x^2 for the reference, suff2 = the target's log density)
+    e.record_flags = cfg->record_flags; e.target = mixture ? PTE_TARGET_FUNNEL : cfg->target; e.test_swapper_pr = cfg->target_params[0];
     const int64_t dd = d > 0 ? d : 1;
     int rc = 0;
     rc |= dev_alloc(h, &e.x, (size_t)(K * (e.ld > 0 ? e.ld : 1)));
@@ -941,8 +990,8 @@ int pte_create(const pte_config *cfg, pte_engine **out) {
         if (hipEventElapsedTime(&ms, init_a, init_b) == hipSuccess) h->init_ms = ms;
         hipEventDestroy(init_a); hipEventDestroy(init_b);
     }
-    if (funnel || ising) {
-        // funnel: initialization(::LogDensity, rng, i) = zeros(dim); Ising: falses(L, L) (examples/ising.jl:85) (test/supporting/dimensional-analysis.jl:24): the streams
+    if (funnel || ising || mixture) {
+        // funnel, Gaussian mixture: initialization(::LogDensity, rng, i) = zeros(dim); Ising: falses(L, L) (examples/ising.jl:85) (test/supporting/dimensional-analysis.jl:24): the streams
         // stay untouched; suff2 = funnel(0) = d terms evaluated on the host exactly like the kernels' tree of equal terms
         std::vector<uint64_t> rngs((size_t)(2 * K));
         const uint64_t G = 0x9e3779b97f4a7c15ULL;
@@ -1049,6 +1098,7 @@ int pte_explore(pte_engine *h, int64_t scan) {
 int pte_swap(pte_engine *h, int64_t scan) {
     if (!h) return 1;
     PTE_ALIVE(h, "pte_swap");
+    if (mixture_missing(h)) return mixture_missing_error(h, "pte_swap");
     HIP_OK(h, hipSetDevice(h->cfg.device));
     if (launch_swap(h, scan)) return 1;
     return check_device_error(h);
@@ -1058,6 +1108,7 @@ int pte_run_scans(pte_engine *h, int64_t first_scan, int64_t n_scans) {
     if (!h) return 1;
     HIP_OK(h, hipSetDevice(h->cfg.device));
     PTE_ALIVE(h, "pte_run_scans");
+    if (mixture_missing(h)) return mixture_missing_error(h, "pte_run_scans");
     if (h->world != 1) return run_scans_sharded(h, first_scan, n_scans);
     if (fused_scans_eligible(h, n_scans)) {
         if (h->fused_skip > 0) h->fused_skip -= 1;         // a recent launch found the device shared: not this call (run_scans_fused)
@@ -1748,6 +1799,8 @@ int pte_comm_allgather(pte_engine *h, const void *send, int64_t bytes, void *rec
 int pte_group_run_scans(pte_engine *const *hs, int32_t G, int64_t first_scan, int64_t n_scans) {
     if (!hs || G < 1 || !hs[0]) return fail(nullptr, "pte_group_run_scans: null argument");
     pte_engine *h0 = hs[0];
+    for (int32_t g = 0; g < G; ++g)
+        if (hs[g] && mixture_missing(hs[g])) return mixture_missing_error(h0, "pte_group_run_scans");
     for (int g = 0; g < G; ++g) {
         pte_engine *h = hs[g];
         if (!h) return fail(h0, "pte_group_run_scans: engine %d is null", g);
@@ -1799,6 +1852,7 @@ const char *pte_kernel_name(const pte_engine *h) {
         // SliceSampler on the interpolated path: the one-wave Langevin-family kernel in its slice mode (no momentum, gradient or trial copies:
         // its sixteen-block instantiation for d > 512 holds 255 VGPRs + 7 AGPRs and does not touch scratch)
         if (h->cfg.target == PTE_TARGET_FUNNEL) return "k_explore_automala";
+        if (h->cfg.target == PTE_TARGET_GAUSSIAN_MIXTURE) return "k_explore_mixture";
         switch (h->slice_impl) {
         case 1: return "k_explore_slice"; case 2: return "k_explore_slice2"; case 5: return "k_explore_slice5";
         case 7: return "k_explore_slice7";
@@ -1809,6 +1863,7 @@ const char *pte_kernel_name(const pte_engine *h) {
     case PTE_EXPLORER_AUTOMALA: case PTE_EXPLORER_MALA:
         // d > 512: four waves per replica (pte_automala_mw.hpp, round 6); the one-wave kernel with sixteen blocks per lane -- 250-300 spilled VGPRs,
         // "unoptimised" in rounds 1-5 -- survives in the test build as its A/B reference
+        if (h->cfg.target == PTE_TARGET_GAUSSIAN_MIXTURE) return "k_explore_mixture";
         if (h->d > 512) return (h->cfg.debug_kernel & PTE_KERNEL_TEST_LANGEVIN_ONE_WAVE) ? "k_explore_automala [test build: one wave, sixteen blocks per lane]" : "k_explore_langevin_mw";
         return "k_explore_automala";
     case PTE_EXPLORER_AAPS: return "k_explore_aaps";
@@ -1863,7 +1918,61 @@ int refresh_funnel_stats(pte_engine *h) {
     HIP_OK(h, hipStreamSynchronize(h->stream));
     return 0;
 }
+int refresh_mixture_stats(pte_engine *h) {
+    const int E = h->d <= 64 ? 1 : h->d <= 128 ? 2 : h->d <= 256 ? 4 : 8;
+    if (mixture_refresh_stats(E, (unsigned)h->K, h->stream, h->dev, mixture_params(h))) return fail(h, "this build holds no Gaussian-mixture kernel for dim %lld", (long long)h->d);
+    HIP_OK(h, hipGetLastError());
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
 }  // namespace
+
+// The Gaussian-mixture target.  Host, once per call: lw_k = log w_k - logsumexp(log w), c_k = lw_k - sum_i log sigma_ki - (d/2) log 2 pi
+// (index order), inv_ki = 1 / sigma_ki; uploaded as [8][ld] means, [8][ld] inverses (zero-padded), [8] constants.
+int pte_set_target_mixture(pte_engine *h, int64_t n_components, const double *weights, const double *means, const double *std_devs) {
+    if (!h) return 1;
+    PTE_ALIVE(h, "pte_set_target_mixture");
+    if (h->cfg.target != PTE_TARGET_GAUSSIAN_MIXTURE)
+        return fail(h, "pte_set_target_mixture: this engine's target is %d, not PTE_TARGET_GAUSSIAN_MIXTURE", h->cfg.target);
+    if (n_components < 1 || n_components > 8)
+        return fail(h, "pte_set_target_mixture: the device holds 1..8 components (got %lld)", (long long)n_components);
+    if (!weights || !means || !std_devs) return fail(h, "pte_set_target_mixture: null argument");
+    const int64_t K = n_components, d = h->d, ld = h->dev.ld;
+    for (int64_t k = 0; k < K; ++k) {
+        if (!(weights[k] > 0) || !std::isfinite(weights[k]))
+            return fail(h, "pte_set_target_mixture: weight %lld must be positive and finite (got %g)", (long long)k, weights[k]);
+        for (int64_t i = 0; i < d; ++i) {
+            const double sd = std_devs[k * d + i], mu = means[k * d + i];
+            if (!(sd > 0) || !std::isfinite(sd))
+                return fail(h, "pte_set_target_mixture: std_devs[%lld][%lld] must be positive and finite (got %g)", (long long)k, (long long)i, sd);
+            if (!std::isfinite(mu))
+                return fail(h, "pte_set_target_mixture: means[%lld][%lld] must be finite (got %g)", (long long)k, (long long)i, mu);
+        }
+    }
+    HIP_OK(h, hipSetDevice(h->cfg.device));
+    const double LOG2PI = 1.8378770664093453;
+    double lmax = -INFINITY;
+    for (int64_t k = 0; k < K; ++k) lmax = std::max(lmax, std::log(weights[k]));
+    double se = 0.0;
+    for (int64_t k = 0; k < K; ++k) se += std::exp(std::log(weights[k]) - lmax);
+    const double lse = lmax + std::log(se);
+    std::vector<double> buf((size_t)(16 * ld + 8), 0.0);
+    for (int64_t k = 0; k < K; ++k) {
+        double sl = 0.0;
+        for (int64_t i = 0; i < d; ++i) {
+            const double sd = std_devs[k * d + i];
+            sl += std::log(sd);
+            buf[(size_t)(k * ld + i)] = means[k * d + i];
+            buf[(size_t)(8 * ld + k * ld + i)] = 1.0 / sd;
+        }
+        buf[(size_t)(16 * ld + k)] = (std::log(weights[k]) - lse) - sl - ((double)d / 2.0) * LOG2PI;
+    }
+    if (!h->d_mix && dev_alloc(h, &h->d_mix, buf.size(), false)) return 1;
+    HIP_OK(h, hipMemcpyAsync(h->d_mix, buf.data(), sizeof(double) * buf.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    h->mix_K = (int)K;
+    return refresh_mixture_stats(h);                               // suff / suff2 of the current states
+}
 
 // update_reference! + update_path_variational (src/variational/variational.jl:28-41, GaussianReference.jl:24-31): from now on
 // the chains with uses[c] != 0 run InterpolatingPath(GaussianReference(mean, std), target).  mean = std = NULL deactivates.
@@ -1900,6 +2009,7 @@ int pte_get_state(const pte_engine *hc, double *state, int64_t *chain, uint64_t 
     pte_engine *h = const_cast<pte_engine *>(hc);
     if (!h) return 1;
     PTE_ALIVE(h, "pte_get_state");
+    if (mixture_missing(h)) return mixture_missing_error(h, "pte_get_state");
     HIP_OK(h, hipSetDevice(h->cfg.device));
     const int64_t N = h->K, d = h->d;
     const bool ising = h->cfg.target == PTE_TARGET_ISING;
@@ -1987,6 +2097,7 @@ int pte_set_state(pte_engine *h, const double *state, const int64_t *chain, cons
         hipFree(tmp);
         HIP_OK(h, e1);
         if (h->cfg.target == PTE_TARGET_FUNNEL && refresh_funnel_stats(h)) return 1;   // + the target (and variational) log densities
+        if (h->cfg.target == PTE_TARGET_GAUSSIAN_MIXTURE && h->mix_K > 0 && refresh_mixture_stats(h)) return 1;   // + the mixture's log densities
     }
     return 0;
 }
@@ -2035,6 +2146,7 @@ int pte_set_rng_policy(int32_t device, uint32_t policy) {
     hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(g_rng_policy), &policy, sizeof policy);
     if (e == hipSuccess) e = (hipError_t)langevin_set_rng_policy(policy);       // the second translation unit's copy of the word
     if (e == hipSuccess) e = (hipError_t)aaps_set_rng_policy(policy);           // ... and the third's
+    if (e == hipSuccess) e = (hipError_t)mixture_set_rng_policy(policy);        // ... and the fourth's
     if (e == hipSuccess) e = hipDeviceSynchronize();
     return e == hipSuccess ? 0 : fail(nullptr, "pte_set_rng_policy: %s", hipGetErrorString(e));
 }

@@ -9,6 +9,7 @@
 //   TGT_MVN    ScaledPrecisionNormalLogPotential, analytic gradient (src/paths/ScaledPrecisionNormalPath.jl:19-34)
 //   TGT_FUNNEL InterpolatedAD of {ScaledPrecisionNormal(p0) reference, Neal's funnel}
 //              (src/explorers/BufferedAD.jl:89-112; funnel test/supporting/dimensional-analysis.jl:36-48)
+//   TGT_MIXTURE the same path with a normalised mixture of KB (or fewer) diagonal Gaussians as the target (pte_mixture.hpp)
 #pragma once
 #include "pte_automala_params.hpp"
 
@@ -93,7 +94,7 @@ __device__ __forceinline__ double sqr_norm_regs(const double (&v)[E]) {
 
 // FULL: d == 64 E, every lane of every block holds an element -- the masks, selects and EXEC-guarded divisions of a ragged last
 // block vanish (25 instructions of ~600 per leapfrog at E = 2)
-template <int E, int TGT, bool FULL = false>
+template <int E, int TGT, bool FULL = false, int KB = 1>
 struct AmTarget {
     int64_t d; int lane;
     double nhp, nprec;          // MVN: -0.5*prec, -prec of this chain
@@ -186,9 +187,75 @@ struct AmTarget {
         if (WITH_Q) Q = out[KQ % K];
         return out[1];
     }
+    __device__ __forceinline__ void load_mixture(const MixParams &m) {
+        mx = m;
+#pragma unroll
+        for (int k = 0; k < KB; ++k) mxc[k] = k < m.K ? m.c[k] : 0.0;
+    }
+    // (x_i - mu_ki) inv_ki of component k, block j (0 outside the state / the components)
+    __device__ __forceinline__ double mix_z(const double (&x)[E], int k, int j) const {
+        if (k >= mx.K || !valid(j)) return 0.0;
+        const int64_t i = k * mx.ld + 64 * (int64_t)j + lane;
+        return (x[j] - mx.mu[i]) * mx.inv[i];
+    }
+    // the mixture's log density: q_k = sum_i ((x_i - mu_ki) inv_ki)^2 for every component, S = sum x^2 (and, WITH_Q, Q = sum q^2)
+    // reduced in lockstep over the fixed tree; a_k = c_k - q_k / 2, lp = m + log(sum_k exp(a_k - m)) in component order.  GRAD: g = its gradient,
+    // sum_k r_k (-(x - mu_k) inv_k^2) with r_k = exp(a_k - lp), in component order
+    template <bool GRAD, bool WITH_Q>
+    __device__ __forceinline__ double mixture_and_sqr_norm(const double (&x)[E], double (&g)[E], double &S, const double (&q)[E], double &Q) const {
+        constexpr int NS = KB + 1 + (WITH_Q ? 1 : 0);
+        double t[NS][E], out[NS];
+#pragma unroll
+        for (int j = 0; j < E; ++j) {
+            t[0][j] = x[j] * x[j];
+#pragma unroll
+            for (int k = 0; k < KB; ++k) { const double z = mix_z(x, k, j); t[1 + k][j] = z * z; }
+            if (WITH_Q) t[(NS - 1) % NS][j] = q[j] * q[j];
+        }
+        tree_sum_regs_multi<E, NS>(t, out);
+        S = out[0];
+        if (WITH_Q) Q = out[(NS - 1) % NS];
+        double a[KB];
+        double m = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < KB; ++k) { a[k] = mxc[k] - out[1 + k] / 2.0; if (k < mx.K) m = (k == 0 || a[k] > m) ? a[k] : m; }
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < KB; ++k) if (k < mx.K) s += exp(a[k] - m);
+        const double lp = m + log(s);
+        if (GRAD) {
+#pragma unroll
+            for (int k = 0; k < KB; ++k) {
+                if (k >= mx.K) break;
+                const double r = exp(a[k] - lp);
+#pragma unroll
+                for (int j = 0; j < E; ++j) {
+                    double gk = 0.0;
+                    if (valid(j)) {
+                        const int64_t i = k * mx.ld + 64 * (int64_t)j + lane;
+                        const double iv = mx.inv[i];
+                        gk = -((x[j] - mx.mu[i]) * (iv * iv));
+                    }
+                    g[j] = k == 0 ? r * gk : g[j] + r * gk;
+                }
+            }
+        }
+        return lp;
+    }
+    __device__ __forceinline__ double mixture(const double (&x)[E]) const {
+        double S, Q, dummy[E];
+        return mixture_and_sqr_norm<false, false>(x, dummy, S, x, Q);
+    }
     // log_potentials[chain](x) as a plain callable: InterpolatedLogPotential(x) (src/paths/InterpolatedLogPotential.jl:9-16)
     // WITH its beta == 0 / beta == 1 short-circuits -- what SliceSampler evaluates (the AD form below has none)
     __device__ __forceinline__ double path_lp(const double (&x)[E]) const {
+        if (TGT == TGT_MIXTURE) {
+            if (beta == 0.0) return ref_nhp * sqr_norm_regs<E>(x);
+            double S, Q, dummy[E];
+            const double l2 = mixture_and_sqr_norm<false, false>(x, dummy, S, x, Q);
+            if (beta == 1.0) return l2;
+            return omb * (ref_nhp * S) + beta * l2;
+        }
         const double S = sqr_norm_regs<E>(x);
         if (TGT == TGT_MVN) return nhp * S;
         if (beta == 0.0) return ref_lp(x, S);
@@ -201,6 +268,10 @@ struct AmTarget {
     __device__ __forceinline__ double logdensity(const double (&x)[E]) const {
         if (TGT == TGT_MVN) return nhp * sqr_norm_regs<E>(x);
         double S, l2, dummy[E], dq;
+        if (TGT == TGT_MIXTURE) {
+            l2 = mixture_and_sqr_norm<false, false>(x, dummy, S, x, dq);
+            return omb * (ref_nhp * S) + beta * l2;
+        }
         if (E <= 4) l2 = funnel_and_sqr_norm<false, false>(x, dummy, S, x, dq);
         else { S = sqr_norm_regs<E>(x); l2 = funnel(x, nullptr); }
         const double l1 = ref_lp(x, S);
@@ -225,6 +296,14 @@ struct AmTarget {
         double logdens = 0.0;
         double g2[E];
         double l2;
+        if (TGT == TGT_MIXTURE) {
+            l2 = mixture_and_sqr_norm<true, WITH_Q>(x, g2, S, q, Q);
+            logdens += (ref_nhp * S) * omb;
+            logdens += l2 * beta;
+#pragma unroll
+            for (int j = 0; j < E; ++j) g[j] = (ref_nprec * x[j]) * omb + g2[j] * beta;
+            return logdens;
+        }
         if (E <= 4) l2 = funnel_and_sqr_norm<true, WITH_Q>(x, g2, S, q, Q);
         else { S = sqr_norm_regs<E>(x); l2 = funnel(x, &g2); if (WITH_Q) Q = sqr_norm_regs<E>(q); }
         const double l1 = ref_lp(x, S);
@@ -243,6 +322,9 @@ struct AmTarget {
         double dq;
         return logdensity_and_gradient_q<false>(x, g, x, dq);
     }
+    // (last: the members above keep their order -- and the MVN / funnel instantiations their generated code)
+    MixParams mx;               // TGT_MIXTURE: the components (K <= KB), their constants c_k in registers
+    double mxc[KB];
 };
 
 // SLICE = true instantiates the same prologue (reference-chain refresh, state load) and epilogue (swap statistics, recorders)
@@ -258,8 +340,9 @@ __device__ __forceinline__ int64_t am_chain_of_workgroup(int64_t K, int64_t wg) 
 
 // DIRECT (the scan loop with several chains per workgroup, k_scans_automala_wg): `wg` IS the local chain, and the table staging ends in a
 // wave-level wait instead of a workgroup barrier -- every wave writes all the (identical) entries itself, so it only has to see its own stores
-template <int E, int TGT, bool SLICE = false, bool FULL = false, bool DIRECT = false>
-__device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const int64_t wg) {      // wg: blockIdx.x
+// KB, mp: TGT_MIXTURE only -- the components' bucket (K <= KB) and parameters
+template <int E, int TGT, bool SLICE = false, bool FULL = false, bool DIRECT = false, int KB = 1>
+__device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const int64_t wg, const MixParams &mp = MixParams{}) {      // wg: blockIdx.x
     constexpr int NLU = (E == 1 ? 0 : E == 2 ? 1 : E == 4 ? 2 : E == 8 ? 3 : 4);
     const int lane = lane_id();
     // the ziggurat tables of the momentum draws, staged once: a global gather per block of draws costs a memory round trip each time
@@ -277,8 +360,9 @@ __device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const in
     const int slot = e.slot_of_chain[cl];
     const int64_t d = e.d;
     double *xrow = e.x + (int64_t)slot * e.ld;
-    AmTarget<E, TGT, FULL> T;
+    AmTarget<E, TGT, FULL, KB> T;
     T.d = d; T.lane = lane;
+    if (TGT == TGT_MIXTURE) T.load_mixture(mp);
     T.nhp = e.nhp[c]; T.nprec = e.nprec[c];
     T.beta = e.beta[c]; T.omb = 1.0 - T.beta;
     T.ref_nhp = -0.5 * ap.ref_prec; T.ref_nprec = -ap.ref_prec; T.log3 = ap.log3;
@@ -316,6 +400,10 @@ __device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const in
             l20 = T.funnel(x, nullptr);
             if (lane == 0) e.suff2[slot] = l20;
             if (v_on) { l30 = T.variational_lp(x); if (lane == 0) e.suff3[slot] = l30; }
+        }
+        if (TGT == TGT_MIXTURE) {
+            l20 = T.mixture(x);
+            if (lane == 0) e.suff2[slot] = l20;
         }
         record_after_explore_impl(e, cl, c, slot, lane, lp0, S0, l20, l30);
         return;
@@ -633,10 +721,11 @@ __device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const in
     const double S = sqr_norm_regs<E>(x);
     double l2 = 0.0, l3 = 0.0;
     if (TGT == TGT_FUNNEL) l2 = T.funnel(x, nullptr);
+    if (TGT == TGT_MIXTURE) l2 = T.mixture(x);
     if (v_on) l3 = T.variational_lp(x);
     if (lane == 0) {
         e.suff[slot] = S;
-        if (TGT == TGT_FUNNEL) e.suff2[slot] = l2;
+        if (TGT == TGT_FUNNEL || TGT == TGT_MIXTURE) e.suff2[slot] = l2;
         if (v_on) e.suff3[slot] = l3;
         e.rng[2 * slot] = r.seed;
         e.expl_steps_sum[cl] += (double)steps_sum; e.expl_steps_n[cl] += steps_n;

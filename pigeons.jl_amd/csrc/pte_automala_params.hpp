@@ -8,7 +8,15 @@
 
 namespace pte {
 
-enum { TGT_MVN = 0, TGT_FUNNEL = 2 };
+enum { TGT_MVN = 0, TGT_FUNNEL = 2, TGT_MIXTURE = 4 };
+
+// TGT_MIXTURE (pte_mixture.hpp): the normalised mixture of K diagonal Gaussians, shared by every replica.  mu / inv: [K][ld]
+// (ld = the state row's stride, zero-padded), c: [K]; the kernels read mu and inv as lane-coalesced global loads.
+struct MixParams {
+    const double *mu = nullptr, *inv = nullptr, *c = nullptr;
+    int K = 0;
+    int64_t ld = 0;
+};
 enum { ERR_AM_DENSITY = 5, ERR_AM_STEP = 6 };
 
 struct AmParams {

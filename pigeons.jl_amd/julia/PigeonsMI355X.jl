@@ -34,7 +34,7 @@ using Random: AbstractRNG
 const libpte = "libpte.so"
 
 # ---- include/pte.h mirrored ------------------------------------------------------------------------------------------------
-const TARGET_MVN, TARGET_TEST_SWAPPER, TARGET_FUNNEL, TARGET_ISING = Int32(0), Int32(1), Int32(2), Int32(3)
+const TARGET_MVN, TARGET_TEST_SWAPPER, TARGET_FUNNEL, TARGET_ISING, TARGET_GAUSSIAN_MIXTURE = Int32(0), Int32(1), Int32(2), Int32(3), Int32(4)
 const EXPLORER_NONE, EXPLORER_TOY, EXPLORER_SLICE, EXPLORER_AUTOMALA, EXPLORER_ISING, EXPLORER_MALA, EXPLORER_AAPS = Int32.((0, 1, 2, 3, 4, 5, 6))
 const RECORD_ROUND_TRIP, RECORD_INDEX_PROCESS, RECORD_ONLINE, RECORD_TRACES, RECORD_ENERGY_AC1, RECORD_TRACES_EXTENDED =
     UInt32.((1, 2, 4, 8, 16, 32))
@@ -100,6 +100,10 @@ struct DeviceFunnel; dim::Int; end
 """The Ising model of examples/ising.jl:13-37 (`IsingLogPotential(beta, base_length)`, defined in user code there):
 PTE_TARGET_ISING, explorer = the Metropolis sweeps of examples/ising.jl:91-116 (n_sweeps passes)."""
 struct DeviceIsing; beta::Float64; base_length::Int; n_sweeps::Int; end
+"""A normalised mixture of K <= 8 diagonal Gaussians, the device family PTE_TARGET_GAUSSIAN_MIXTURE (DESIGN 4.8): the device form of
+`DistributionLogPotential(MixtureModel([MvNormal(means[k], Diagonal(std_devs[k] .^ 2)) for k in 1:K], weights))`.  `means` and
+`std_devs` are K x dim.  Used as `Inputs(target = on_mi355x(DeviceGaussianMixture(w, m, s)), reference = ScaledPrecisionNormalLogPotential(p, dim))`."""
+struct DeviceGaussianMixture; weights::Vector{Float64}; means::Matrix{Float64}; std_devs::Matrix{Float64}; end
 
 # (target code, dim, target_params, reference precision check) of a wrapped target
 device_family(t::ScaledPrecisionNormalPath, inputs) = (TARGET_MVN, t.dim, (t.precision0, t.precision1, 0.0, 0.0))
@@ -111,6 +115,14 @@ function device_family(t::DeviceFunnel, inputs)
     return (TARGET_FUNNEL, t.dim, (ref.precision, 0.0, 0.0, 0.0))
 end
 device_family(t::DeviceIsing, inputs) = (TARGET_ISING, t.base_length^2, (t.beta, 0.0, 0.0, 0.0))
+function device_family(t::DeviceGaussianMixture, inputs)
+    K, dim = size(t.means)
+    length(t.weights) == K && size(t.std_devs) == (K, dim) || error("DeviceGaussianMixture: weights [K], means and std_devs K x dim")
+    ref = inputs.reference
+    ref isa ScaledPrecisionNormalLogPotential && ref.dim == dim ||
+        error("the device Gaussian-mixture path needs reference = ScaledPrecisionNormalLogPotential(precision, $dim); keep the CPU path otherwise")
+    return (TARGET_GAUSSIAN_MIXTURE, dim, (ref.precision, 0.0, 0.0, 0.0))
+end
 device_family(t, inputs) = error("target $(typeof(t)) has no device log-potential family (closed set: include/pte.h PTE_TARGET_*); keep the CPU path")
 
 # explorer structs -> pte_config fields (SliceSampler.jl:8-20, AutoMALA.jl:29-68, MALA.jl:19-40, Compose.jl:5-9)
@@ -218,6 +230,11 @@ function Pigeons.create_replicas(inputs::Inputs{<:OnDevice}, shared::Shared, sou
     r = DeviceReplicas(h[], N + inputs.n_chains_variational, dim, info[1], info[2], t.world_size, cfg.record_flags,
                        Pigeons.create_recorders(inputs, shared))
     finalizer(x -> ccall((:pte_destroy, libpte), Cint, (Ptr{Cvoid},), x.handle), r)
+    if t.target isa DeviceGaussianMixture           # the components, row-major [K][dim] as pte_set_target_mixture reads them
+        m = t.target
+        check(r, ccall((:pte_set_target_mixture, libpte), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                       r.handle, length(m.weights), m.weights, collect(vec(permutedims(m.means))), collect(vec(permutedims(m.std_devs)))))
+    end
     source === nothing || restore!(r, source)          # FromCheckpoint: pte_set_state from the deserialised Replica structs
     return r
 end

@@ -86,6 +86,13 @@ class Engine:
         u = np.ascontiguousarray(uses, dtype=np.int32)
         self._chk(self.L.pte_set_variational_reference(self.h, _dp(m), _dp(sd), len(m), u.ctypes.data_as(C.POINTER(C.c_int32))))
 
+    def set_target_mixture(self, weights, means, std_devs):
+        """pte_set_target_mixture: weights [K], means / std_devs [K][d]"""
+        w = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+        m = np.ascontiguousarray(means, dtype=np.float64).reshape(len(w), -1)
+        sd = np.ascontiguousarray(std_devs, dtype=np.float64).reshape(len(w), -1)
+        self._chk(self.L.pte_set_target_mixture(self.h, len(w), _dp(w), _dp(m), _dp(sd)))
+
     # --- hot path
     def explore(self, scan):
         self._chk(self.L.pte_explore(self.h, scan))

@@ -33,8 +33,13 @@ def toy_mvn_target(dim):
     return ScaledPrecisionNormalPath(1.0, 10.0, dim)
 
 
-def analytic_lognormalization(path):
-    """src/paths/ScaledPrecisionNormalPath.jl:66-71"""
+def analytic_lognormalization(path, reference=None):
+    """src/paths/ScaledPrecisionNormalPath.jl:66-71.  GaussianMixture (with its reference ScaledPrecisionNormalLogPotential(prec, dim), which
+    is unnormalised): log Z1 / Z0 = -(dim / 2) log(2 pi / prec)."""
+    if isinstance(path, GaussianMixture):
+        if not isinstance(reference, ScaledPrecisionNormalLogPotential):
+            raise ValueError("GaussianMixture: pass reference=ScaledPrecisionNormalLogPotential(prec, dim)")
+        return -(path.dim / 2.0) * math.log(2.0 * math.pi / reference.precision)
     return 0.5 * path.dim * (math.log(path.precision0) - math.log(path.precision1))
 
 
@@ -63,6 +68,41 @@ class Funnel:
     z[1] ~ Normal(0, 3), z[i] ~ Normal(0, exp(z[1]/2)); initialization = zeros(dim).  Tempered through the
     default InterpolatingPath(reference, target) (src/targets/target.jl:72-75)."""
     dim: int = 2
+
+
+class GaussianMixture:
+    """A normalised mixture of K <= 8 Gaussians with diagonal covariance, the device's multimodal target.  The Julia form is
+        DistributionLogPotential(MixtureModel([MvNormal(means[k], Diagonal(std_devs[k] .^ 2)) for k in 1:K], weights))
+    weights: K positive numbers (normalised here as by MixtureModel); means, std_devs: K x dim.  Tempered through the default
+    InterpolatingPath(reference, target) (src/targets/target.jl:72-75) with reference=ScaledPrecisionNormalLogPotential(prec, dim);
+    initialization = zeros(dim); default explorer SliceSampler (target.jl:20)."""
+
+    def __init__(self, weights, means, std_devs):
+        w = np.array(weights, dtype=np.float64).ravel()
+        m = np.array(means, dtype=np.float64)
+        s = np.array(std_devs, dtype=np.float64)
+        if w.size < 1 or w.size > 8:
+            raise ValueError("GaussianMixture: the device holds 1..8 components (got %d)" % w.size)
+        if m.ndim != 2 or m.shape[0] != w.size or s.shape != m.shape or m.shape[1] < 1:
+            raise ValueError("GaussianMixture: means and std_devs must both be K x dim arrays with K = len(weights)")
+        if not np.all(np.isfinite(w)) or np.any(w <= 0):
+            raise ValueError("GaussianMixture: weights must be positive and finite")
+        if not np.all(np.isfinite(s)) or np.any(s <= 0):
+            raise ValueError("GaussianMixture: std_devs must be positive and finite")
+        if not np.all(np.isfinite(m)):
+            raise ValueError("GaussianMixture: means must be finite")
+        self.weights, self.means, self.std_devs = w, m, s
+
+    @property
+    def n_components(self):
+        return self.weights.size
+
+    @property
+    def dim(self):
+        return self.means.shape[1]
+
+    def __repr__(self):
+        return "GaussianMixture(K=%d, dim=%d)" % (self.n_components, self.dim)
 
 
 @dataclass
@@ -369,6 +409,11 @@ class PT:
             if not isinstance(ref, ScaledPrecisionNormalLogPotential) or ref.dim != target.dim:
                 raise NotImplementedError("the device funnel path needs reference=ScaledPrecisionNormalLogPotential(prec, dim)")
             kw.update(target=_lib.TARGET_FUNNEL, dim=target.dim, target_params=[ref.precision])
+        elif isinstance(target, GaussianMixture):
+            ref = inputs.reference
+            if not isinstance(ref, ScaledPrecisionNormalLogPotential) or ref.dim != target.dim:
+                raise NotImplementedError("the device Gaussian-mixture path needs reference=ScaledPrecisionNormalLogPotential(prec, dim)")
+            kw.update(target=_lib.TARGET_GAUSSIAN_MIXTURE, dim=target.dim, target_params=[ref.precision])
         else:
             raise NotImplementedError(
                 "target %r has no device log-potential; use the reference CPU path (Pigeons.jl)" % (target,))
@@ -427,6 +472,9 @@ class PT:
                 self.shards = DistShard(self.replicas, rank, world, device=dist_device)
         else:
             self.replicas = make(**kw)
+        if isinstance(target, GaussianMixture):          # every engine (rank) holds the components
+            for eng in (self.shards.engines if hasattr(self.shards, "engines") else [self.replicas]):
+                eng.set_target_mixture(target.weights, target.means, target.std_devs)
 
 
 def next_round(pt):

@@ -1,0 +1,240 @@
+"""The Gaussian-mixture family on the device (k_explore_mixture, pigeons.jl_amd/csrc/pte_mixture.hpp) against its NumPy restatement
+(tests/mixture_ref.py): the log density at every chain's beta, one SliceSampler and one MALA transition of every replica from random states,
+invariance where the interpolated densities are Gaussian (K = 1), whole runs on a bimodal mixture, determinism, Compose, the chain-sharded
+engine and checkpoint / resume.
+
+RNG words are compared exactly; states and recorders to 1e-9 relative -- the device's exp / log differ from libm by an ulp."""
+import math
+
+import numpy as np
+import pytest
+
+import aaps_ref as A
+import mixture_ref as R
+import oracle as O
+
+pytestmark = pytest.mark.gpu
+
+RTOL = 1e-9
+
+
+@pytest.fixture(scope="module")
+def P():
+    import pigeons_amd
+    return pigeons_amd
+
+
+def _mixture(K, d, seed=1, spread=2.0):
+    g = np.random.default_rng(seed)
+    return g.uniform(0.3, 2.0, K), g.normal(0.0, spread, (K, d)), g.uniform(0.5, 1.5, (K, d))
+
+
+def _random_states(P, pt, N, d, seed, scale=1.5):
+    eng = pt.replicas
+    g = np.random.default_rng(seed)
+    betas = np.concatenate([[0.0], np.sort(g.uniform(0.0, 1.0, N - 2)), [1.0]])
+    eng.set_schedule(betas)
+    x = g.normal(0.0, scale, (N, d))
+    chain = g.permutation(N).astype(np.int64)
+    _, _, rng = eng.states()
+    eng.set_states(x, chain, rng)
+    return betas, x, chain, rng
+
+
+def test_state_calls_need_the_mixture(P):
+    eng = P.Engine(n_chains=4, target=P._lib.TARGET_GAUSSIAN_MIXTURE, dim=3, explorer=P._lib.EXPLORER_SLICE, target_params=[1.0])
+    for call in (lambda: eng.explore(1), lambda: eng.swap(1), lambda: eng.run_scans(1, 2), lambda: eng.states()):
+        with pytest.raises(P.PteError, match="call pte_set_target_mixture first"):
+            call()
+    with pytest.raises(P.PteError, match=r"1\.\.8 components"):
+        eng.set_target_mixture(np.ones(9), np.zeros((9, 3)), np.ones((9, 3)))
+    with pytest.raises(P.PteError, match="must be positive and finite"):
+        eng.set_target_mixture([1.0, -1.0], np.zeros((2, 3)), np.ones((2, 3)))
+    with pytest.raises(P.PteError, match="must be finite"):
+        eng.set_target_mixture([1.0], [[0.0, np.nan, 0.0]], np.ones((1, 3)))
+    eng.set_target_mixture([1.0, 2.0], np.zeros((2, 3)), np.ones((2, 3)))
+    eng.explore(1)
+    assert eng.states()[0].shape == (4, 3) and eng.kernel_name() == "k_explore_mixture" and eng.scan_loop_name() == ""
+
+
+@pytest.mark.parametrize("K,d", [(1, 5), (3, 64), (8, 100), (5, 512)])
+def test_log_density_at_every_beta(P, K, d):
+    """the device's log density (extended traces of one explore step) against the restatement at the state the step left, every chain's beta"""
+    w, mu, sd = _mixture(K, d, seed=K + d)
+    N = 12
+    t = P.GaussianMixture(w, mu, sd)
+    pt = P.PT(P.Inputs(target=t, reference=P.ScaledPrecisionNormalLogPotential(0.25, d), n_chains=N, n_rounds=2, explorer=P.SliceSampler(n_passes=1),
+                       record=[P.traces], extended_traces=True, show_report=False))
+    betas, _, _, _ = _random_states(P, pt, N, d, seed=d)
+    eng = pt.replicas
+    eng.explore(1)
+    eng.swap(1)                                   # (a scan ends at its swap: the traces count it from there)
+    eng.reduce()
+    tr = eng.traces()
+    assert tr.shape == (1, N, d + 1)
+    mix = R.Mixture(w, mu, sd)
+    for c in range(N):
+        want = R.MixtureChain(mix, betas[c], 0.25).path_lp(tr[0, c, :d])
+        assert math.isclose(tr[0, c, d], want, rel_tol=1e-12, abs_tol=1e-12), (c, betas[c], tr[0, c, d], want)
+
+
+@pytest.mark.parametrize("K,d", [(2, 3), (4, 40), (8, 70)])
+def test_one_slice_transition_parity(P, K, d):
+    w, mu, sd = _mixture(K, d, seed=7 * K + d)
+    N = 10
+    pt = P.PT(P.Inputs(target=P.GaussianMixture(w, mu, sd), reference=P.ScaledPrecisionNormalLogPotential(0.5, d), n_chains=N, n_rounds=2,
+                       explorer=P.SliceSampler(), show_report=False))
+    betas, x, chain, rng = _random_states(P, pt, N, d, seed=K)
+    eng = pt.replicas
+    eng.explore(1)
+    x1, c1, r1 = eng.states()
+    eng.reduce()
+    am, an, ss, sn = eng.explorer_stats()
+    assert np.array_equal(c1, chain)
+    mix = R.Mixture(w, mu, sd)
+    for i in range(N):
+        c = int(chain[i])
+        if c == 0:
+            continue
+        r = O.OracleRng(state=(int(rng[i, 0]), int(rng[i, 1])))
+        s = O.MixedSliceSampler(R.MixtureChain(mix, betas[c], 0.5).path_lp, np.zeros(d, dtype=np.int32))
+        y = x[i].copy()
+        s.step(r, y)
+        assert int(r1[i, 0]) == r.state[0] and int(r1[i, 1]) == r.state[1], (i, c)
+        np.testing.assert_allclose(x1[i], y, rtol=RTOL, atol=1e-12, err_msg="replica %d chain %d" % (i, c))
+        assert an[c] == s.stats.acc_n and sn[c] == s.stats.steps_n and ss[c] == s.stats.steps_sum, (i, c)
+        np.testing.assert_allclose(am[c], s.stats.acc_mean, rtol=RTOL)
+
+
+@pytest.mark.parametrize("K,d,precond", [(2, 6, "mix"), (3, 64, "diagonal"), (8, 128, "identity"), (4, 300, "mix")])
+def test_one_mala_transition_parity(P, K, d, precond):
+    mode, pc = {"identity": (0, P.IdentityPreconditioner()), "diagonal": (1, P.DiagonalPreconditioner()),
+                "mix": (2, P.MixDiagonalPreconditioner())}[precond]
+    w, mu, sd = _mixture(K, d, seed=3 * K + d, spread=1.0)
+    N, step = 10, 0.3
+    ex = P.MALA(step_size=step, preconditioner=pc)
+    pt = P.PT(P.Inputs(target=P.GaussianMixture(w, mu, sd), reference=P.ScaledPrecisionNormalLogPotential(1.0, d), n_chains=N, n_rounds=2,
+                       explorer=ex, show_report=False))
+    betas, x, chain, rng = _random_states(P, pt, N, d, seed=d, scale=1.0)
+    eng = pt.replicas
+    std = np.random.default_rng(d).uniform(0.5, 2.0, d)
+    eng.set_explorer_adaptation(step, std)
+    eng.explore(2)
+    x1, c1, r1 = eng.states()
+    eng.reduce()
+    am, an, ss, sn = eng.explorer_stats()
+    n_refresh = ex.base_n_refresh * int(math.ceil(d ** ex.exponent_n_refresh))
+    mix = R.Mixture(w, mu, sd)
+    moved = 0
+    for i in range(N):
+        c = int(chain[i])
+        if c == 0:
+            continue
+        r = O.OracleRng(state=(int(rng[i, 0]), int(rng[i, 1])))
+        M = A.build_preconditioner(r, d, mode, 1.0 / 3.0, 1.0 / 3.0, std)
+        res = R.mala_transition(x[i], r, R.MixtureChain(mix, betas[c], 1.0), step, n_refresh, M)
+        assert int(r1[i, 0]) == r.state[0] and int(r1[i, 1]) == r.state[1], (i, c)
+        np.testing.assert_allclose(x1[i], res["x"], rtol=RTOL, atol=1e-12, err_msg="replica %d chain %d" % (i, c))
+        assert an[c] == res["acc_n"] and sn[c] == n_refresh and ss[c] == res["steps"], (i, c)
+        np.testing.assert_allclose(am[c], res["acc_sum"] / res["acc_n"], rtol=RTOL, atol=1e-12)
+        moved += int(not np.array_equal(res["x"], x[i]))
+    assert moved > 0
+
+
+@pytest.mark.parametrize("explorer", ["slice", "mala", "automala"])
+def test_invariance_with_one_component(P, explorer):
+    """K = 1: chain beta's density is the Gaussian of precision (1 - beta) prec + beta / s^2 per coordinate.  1024 chains set to exact draws
+    at their own beta, three explore steps without swaps: mean and variance of the standardised states stay inside sampling bands"""
+    from scipy import stats
+    N, d, prec = 1024, 8, 0.5
+    g = np.random.default_rng(21)
+    mu, sd = g.normal(0.0, 1.0, (1, d)), g.uniform(0.6, 1.4, (1, d))
+    ex = {"slice": P.SliceSampler(), "mala": P.MALA(step_size=0.4), "automala": P.AutoMALA()}[explorer]
+    pt = P.PT(P.Inputs(target=P.GaussianMixture([1.0], mu, sd), reference=P.ScaledPrecisionNormalLogPotential(prec, d), n_chains=N, n_rounds=2,
+                       explorer=ex, seed=9, show_report=False))
+    eng = pt.replicas
+    betas = np.linspace(0.0, 1.0, N)
+    eng.set_schedule(betas)
+    p = (1.0 - betas)[:, None] * prec + betas[:, None] / sd ** 2
+    m = betas[:, None] * mu / sd ** 2 / p
+    chain = g.permutation(N).astype(np.int64)
+    x = g.standard_normal((N, d)) / np.sqrt(p[chain]) + m[chain]
+    _, _, rng = eng.states()
+    eng.set_states(x, chain, rng)
+    for s in (2, 3, 4):                           # scan 1 of a round has no MH step for AutoMALA (AutoMALA.jl:87)
+        eng.explore(s)
+    x1, c1, _ = eng.states()
+    keep = c1 != 0
+    Z = (x1[keep] - m[c1[keep]]) * np.sqrt(p[c1[keep]])
+    assert np.mean(np.any(x1[keep] != x[keep], axis=1)) > 0.9
+    n = Z.size
+    assert abs(Z.mean()) * math.sqrt(n) < 4.0, Z.mean()
+    assert abs(Z.var() - 1.0) / math.sqrt(2.0 / n) < 4.0, Z.var()
+    for j in (0, d - 1):
+        assert stats.kstest(Z[:, j], "norm").pvalue > 1e-3, j
+
+
+def _bimodal(P, seed=1, explorer=None, n_rounds=10, checkpoint=False, **kw):
+    d = 8
+    mu = np.stack([np.full(d, -2.5), np.full(d, 2.5)])
+    return P.Inputs(target=P.GaussianMixture([0.25, 0.75], mu, np.ones((2, d))), reference=P.ScaledPrecisionNormalLogPotential(1.0 / 16.0, d),
+                    n_chains=16, n_rounds=n_rounds, seed=seed, explorer=explorer or P.SliceSampler(), checkpoint=checkpoint,
+                    record=[P.round_trip, P.traces, P.log_sum_ratio, P.index_process, P.swap_acceptance_pr, P.energy_ac1], show_report=False, **kw)
+
+
+def test_whole_run_on_a_bimodal_mixture(P):
+    """weights 0.25 / 0.75, modes 14 standard deviations apart: only swaps move the target chain between them.  Over the last round's traces
+    the target chain spends 0.75 +- 0.15 of its scans in the heavier mode; stepping_stone is within 0.2 of -(d/2) log(2 pi / prec) = -18.44
+    (measured, seeds 1-3: occupancy 0.752, 0.729, 0.773; stepping_stone -18.441, -18.435, -18.403; 85-104 round trips)"""
+    pt = P.pigeons(P.PT(_bimodal(P)))
+    tr = pt.reduced_recorders.traces
+    occ = float(np.mean(tr[:, :8].sum(axis=1) > 0))
+    assert 0.6 < occ < 0.9, occ
+    exact = R.analytic_lognormalization(8, 1.0 / 16.0)
+    assert exact == P.analytic_lognormalization(pt.inputs.target, pt.inputs.reference)
+    assert abs(P.stepping_stone(pt) - exact) < 0.2, (P.stepping_stone(pt), exact)
+    assert P.n_round_trips(pt) > 0
+
+
+def test_two_runs_are_equal_bit_for_bit(P):
+    a, b = P.pigeons(P.PT(_bimodal(P, seed=3, n_rounds=6))), P.pigeons(P.PT(_bimodal(P, seed=3, n_rounds=6)))
+    xa, ca, ga = a.replicas.states(); xb, cb, gb = b.replicas.states()
+    assert np.array_equal(xa, xb) and np.array_equal(ca, cb) and np.array_equal(ga, gb)
+    assert np.array_equal(a.reduced_recorders.traces, b.reduced_recorders.traces)
+    assert np.array_equal(a.shared.tempering.schedule.grids, b.shared.tempering.schedule.grids)
+    assert P.stepping_stone(a) == P.stepping_stone(b)
+
+
+def test_compose_slice_automala_runs(P):
+    pt = P.pigeons(P.PT(_bimodal(P, seed=2, n_rounds=6, explorer=P.Compose(P.SliceSampler(), P.AutoMALA()))))
+    assert pt.replicas.kernel_name() == "k_explore_mixture"
+    assert np.all(np.isfinite(pt.reduced_recorders.traces)) and np.isfinite(P.stepping_stone(pt))
+    m, n = pt.reduced_recorders.explorer_acceptance_pr
+    assert np.all(n[1:] > 0)
+
+
+@pytest.mark.parametrize("explorer", ["slice", "automala"])
+def test_sharded_equals_single_engine(P, explorer):
+    mk = lambda: _bimodal(P, seed=4, n_rounds=4, explorer=P.SliceSampler() if explorer == "slice" else P.AutoMALA())
+    one, many = P.PT(mk()), P.PT(mk(), n_shards=2)
+    for _ in range(4):
+        assert P.next_round(one) and P.next_round(many)
+        ra = P.run_one_round(one); P.adapt(one, ra)
+        rb = P.run_one_round(many); P.adapt(many, rb)
+        assert np.array_equal(ra.index_process, rb.index_process) and np.array_equal(ra.traces, rb.traces)
+    xa, ca, ga = one.replicas.states(); xb, cb, gb = many.shards.states()
+    assert np.array_equal(xa, xb) and np.array_equal(ca, cb) and np.array_equal(ga, gb)
+
+
+def test_checkpoint_resume_equals_uninterrupted(P, tmp_path):
+    import dataclasses
+    straight = P.pigeons(P.PT(_bimodal(P, seed=5, n_rounds=6, explorer=P.MALA(step_size=0.5))))
+    folder = str(tmp_path / "exec")
+    P.pigeons(P.PT(_bimodal(P, seed=5, n_rounds=3, explorer=P.MALA(step_size=0.5), checkpoint=True)), exec_folder=folder)
+    resumed = P.pigeons(P.load_checkpoint(folder, n_rounds_increment=3))
+    ra, rb = straight.reduced_recorders, resumed.reduced_recorders
+    assert np.array_equal(ra.index_process, rb.index_process) and np.array_equal(ra.traces, rb.traces)
+    assert np.array_equal(straight.shared.tempering.schedule.grids, resumed.shared.tempering.schedule.grids)
+    xa, ca, ga = straight.replicas.states(); xb, cb, gb = resumed.replicas.states()
+    assert np.array_equal(xa, xb) and np.array_equal(ca, cb) and np.array_equal(ga, gb)
+    assert dataclasses.is_dataclass(resumed.inputs)
