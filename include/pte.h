@@ -46,8 +46,15 @@ enum {
     PTE_TARGET_TEST_SWAPPER         = 1, /* TestSwapper:    src/swap/pair_swapper.jl:100-149               */
     PTE_TARGET_FUNNEL               = 2, /* InterpolatingPath(normal ref, Neal's funnel)                   */
     PTE_TARGET_ISING                = 3, /* InterpolatingPath(Ising(0), Ising(beta)): examples/ising.jl        */
-    PTE_TARGET_GAUSSIAN_MIXTURE     = 4  /* InterpolatingPath(normal ref, normalised mixture of K <= 8 diagonal Gaussians;
+    PTE_TARGET_GAUSSIAN_MIXTURE     = 4, /* InterpolatingPath(normal ref, normalised mixture of K <= 8 diagonal Gaussians;
                                             pte_set_target_mixture): SliceSampler / AutoMALA / MALA / Compose of them, dim <= 512 */
+    PTE_TARGET_BAYESIAN_GLM         = 5  /* InterpolatingPath(normal ref = the prior, prior x GLM likelihood of data X, y;
+                                            pte_set_target_glm): SliceSampler / AutoMALA / MALA / Compose of them, dim <= 512 */
+};
+/* PTE_TARGET_BAYESIAN_GLM: the likelihood of each observation */
+enum {
+    PTE_GLM_BERNOULLI_LOGIT = 0,         /* logistic regression: y_i in {0, 1}, l_i = y_i eta_i - softplus(eta_i)                  */
+    PTE_GLM_NORMAL_IDENTITY = 1          /* linear regression with known noise sd sigma: l_i = log N(y_i; eta_i, sigma^2)          */
 };
 enum {
     PTE_EXPLORER_NONE     = 0,           /* `nothing` (TestSwapper)                                        */
@@ -222,6 +229,13 @@ int pte_set_variational_reference(pte_engine *h, const double *mean /*d*/, const
  * call pte_explore, pte_swap, pte_run_scans and pte_get_state fail.  DESIGN 4.8. */
 int pte_set_target_mixture(pte_engine *h, int64_t n_components, const double *weights /*K*/, const double *means /*K*d*/,
                            const double *std_devs /*K*d*/);
+/* PTE_TARGET_BAYESIAN_GLM: the data of the target N(theta; 0, I / p) prod_i p(y_i | eta_i = X[i] . theta) (p = target_params[0], the
+ * reference's precision; X row-major [n_obs][d]; noise_sd is read by PTE_GLM_NORMAL_IDENTITY only).  Validates (the likelihood; 1 <= n_obs
+ * <= 4096 and n_obs * d <= 131072; X and y finite; y in {0, 1} for the logit; noise_sd positive and finite for the normal), uploads and
+ * refreshes the swap statistics of the current states; may be called again to replace the data.  Until the first call pte_explore,
+ * pte_swap, pte_run_scans, pte_group_run_scans and pte_get_state fail.  stepping_stone estimates log p(y) - (d/2) log(2 pi / p).  DESIGN 4.9. */
+int pte_set_target_glm(pte_engine *h, int32_t likelihood, int64_t n_obs, const double *X /*[n_obs][d]*/, const double *y /*[n_obs]*/,
+                       double noise_sd);
 int pte_get_state(const pte_engine *h, double *state, int64_t *chain, uint64_t *rng);
 int pte_set_state(pte_engine *h, const double *state, const int64_t *chain, const uint64_t *rng);
 

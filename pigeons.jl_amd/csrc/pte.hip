@@ -25,10 +25,12 @@
 #include "pte_automala_params.hpp" // the AAPS kernels its third (pte_aaps.hip)
 #include "pte_aaps_params.hpp"
 #include "pte_mixture_params.hpp"     // ... and the Gaussian-mixture kernels its fourth (pte_mixture.hip)
+#include "pte_glm_params.hpp"         // ... and the Bayesian-GLM kernels its fifth (pte_glm.hip)
 #else                              // tools / development builds: one translation unit
 #include "pte_langevin_launch.hpp"
 #include "pte_aaps.hpp"
 #include "pte_mixture.hpp"
+#include "pte_glm.hpp"
 #endif
 #include "pte_ising.hpp"
 #if defined(PTE_PROFILE_AM)               // debug builds only (tools/prof_automala.py): 12 words per wave, section times of k_explore_automala
@@ -90,6 +92,9 @@ struct pte_engine {
     bool have_target_std = false;
     double *d_mix = nullptr;        // PTE_TARGET_GAUSSIAN_MIXTURE: [8][ld] means, [8][ld] 1 / std-devs, [8] c_k
     int mix_K = 0;                  // components; 0 until pte_set_target_mixture
+    double *d_glm = nullptr;        // PTE_TARGET_BAYESIAN_GLM: Xc [d][n_pad], Xr [n][ld] + 512 zeros, y [n_pad], sized for the largest n of this d
+    GlmParams glm{};                // the uploaded data as the kernels read it; glm.n = 0 until pte_set_target_glm
+    int glm_lik = 0;
     double step_size = 1.0;
     int am_n_refresh = 0;
     std::vector<double> fac_mean, rev_mean; std::vector<int64_t> fac_n, rev_n;
@@ -213,7 +218,7 @@ int upload_ladder(pte_engine *h) {
             nprec[c] = -prec;
             sd[c] = std::sqrt(prec);
         }
-    } else if (h->cfg.target == PTE_TARGET_FUNNEL || h->cfg.target == PTE_TARGET_GAUSSIAN_MIXTURE) {
+    } else if (h->cfg.target == PTE_TARGET_FUNNEL || h->cfg.target == PTE_TARGET_GAUSSIAN_MIXTURE || h->cfg.target == PTE_TARGET_BAYESIAN_GLM) {
         for (int64_t c = 0; c < N; ++c) sd[c] = std::sqrt(h->cfg.target_params[0]);   // reference end point
     }
     HIP_OK(h, hipMemcpyAsync(h->d_nhp, nhp.data(), sizeof(double) * N, hipMemcpyHostToDevice, h->stream));
@@ -357,12 +362,24 @@ static bool mixture_missing(const pte_engine *h) { return h->cfg.target == PTE_T
 static int mixture_missing_error(pte_engine *h, const char *what) {
     return fail(h, "%s: the Gaussian-mixture target has no components yet; call pte_set_target_mixture first", what);
 }
+// one launch of k_explore_glm (pte_glm_params.hpp); like launch_langevin, the open timing bracket's events ride on it
+static int launch_glm(pte_engine *h, int E, bool slice, bool full, int64_t N, const AmParams &ap) {
+    GlmLaunch L{E, h->glm_lik, slice, full, (unsigned)N, h->stream, false, nullptr, nullptr};
+    if (h->ev_open && h->ev_ext && !h->ev_ext_done) { L.ext = true; L.ev_a = h->events.back().a; L.ev_b = h->events.back().b; h->ev_ext_done = true; }
+    if (glm_launch(L, h->dev, ap, h->glm)) return fail(h, "this build holds no Bayesian-GLM kernel for dim %lld", (long long)h->d);
+    return 0;
+}
+static bool glm_missing(const pte_engine *h) { return h->cfg.target == PTE_TARGET_BAYESIAN_GLM && h->glm.n == 0; }
+static int glm_missing_error(pte_engine *h, const char *what) {
+    return fail(h, "%s: the Bayesian-GLM target has no data yet; call pte_set_target_glm first", what);
+}
 
 int launch_explorer_kind(pte_engine *h, int64_t scan, int kind);
 int launch_explore(pte_engine *h, int64_t scan) {
     (void)scan;
     const int64_t N = h->K;
     if (mixture_missing(h)) return mixture_missing_error(h, "pte_explore");
+    if (glm_missing(h)) return glm_missing_error(h, "pte_explore");
     if ((h->cfg.record_flags & PTE_RECORD_TRACES) && h->scans_in_round >= h->cfg.max_scans_per_round)
         return fail(h, "traces buffer full: %lld scans since the last pte_reduce (max_scans_per_round = %lld)",
                     (long long)h->scans_in_round, (long long)h->cfg.max_scans_per_round);
@@ -416,6 +433,16 @@ int launch_explorer_kind(pte_engine *h, int64_t scan, int kind) {
             ap.ref_prec = h->cfg.target_params[0]; ap.log3 = std::log(3.0);
             time_begin(h, 0, true);
             if (launch_mixture(h, h->d <= 64 ? 1 : h->d <= 128 ? 2 : h->d <= 256 ? 4 : 8, true, false, N, ap)) return 1;
+            time_end(h);
+            break;
+        }
+        if (h->cfg.target == PTE_TARGET_BAYESIAN_GLM) {           // SliceSampler on the GLM's interpolated path: k_explore_glm's slice mode
+            AmParams ap{};
+            ap.slice = 1; ap.slice_w = h->cfg.slice_w; ap.slice_p = h->cfg.slice_p; ap.slice_n_passes = h->cfg.slice_n_passes;
+            ap.slice_max_iter = h->cfg.slice_max_iter;
+            ap.ref_prec = h->cfg.target_params[0]; ap.log3 = std::log(3.0);
+            time_begin(h, 0, true);
+            if (launch_glm(h, h->d <= 64 ? 1 : h->d <= 128 ? 2 : h->d <= 256 ? 4 : 8, true, false, N, ap)) return 1;
             time_end(h);
             break;
         }
@@ -474,6 +501,7 @@ int launch_explorer_kind(pte_engine *h, int64_t scan, int kind) {
         time_begin(h, 0, true);
         const bool full = h->d == 64 * (int64_t)E;       // no ragged last block: the instantiation without per-lane validity masks
         if (h->cfg.target == PTE_TARGET_GAUSSIAN_MIXTURE) { if (launch_mixture(h, E, false, full, N, ap)) return 1; }
+        else if (h->cfg.target == PTE_TARGET_BAYESIAN_GLM) { if (launch_glm(h, E, false, full, N, ap)) return 1; }
         else if (launch_langevin(h, E, fun ? TGT_FUNNEL : TGT_MVN, false, full, N, ap)) return 1;
         time_end(h);
         break;
@@ -768,6 +796,7 @@ int pte_create(const pte_config *cfg, pte_engine **out) {
     const bool funnel = cfg->target == PTE_TARGET_FUNNEL;
     const bool ising = cfg->target == PTE_TARGET_ISING;
     const bool mixture = cfg->target == PTE_TARGET_GAUSSIAN_MIXTURE;
+    const bool glm = cfg->target == PTE_TARGET_BAYESIAN_GLM;
     if (cfg->explorer == PTE_EXPLORER_AAPS || cfg->explorer2 == PTE_EXPLORER_AAPS) {       // AAPS (pte_aaps.hpp): one wave per replica, one explorer
         if (cfg->explorer2 != PTE_EXPLORER_NONE)
             return fail(nullptr, "pte_create: AAPS is not available as half of a Compose on the device");
@@ -794,6 +823,18 @@ int pte_create(const pte_config *cfg, pte_engine **out) {
         if (cfg->n_chains_variational > 0)
             return fail(nullptr, "pte_create: two-leg tempering (n_chains_variational > 0) is not available on the Gaussian-mixture path");
     }
+    if (glm) {              // Bayesian GLM (pte_glm.hpp): one wave per replica, SliceSampler / AutoMALA / MALA (AAPS: refused above)
+        auto on_glm = [](int k) { return k == PTE_EXPLORER_SLICE || k == PTE_EXPLORER_AUTOMALA || k == PTE_EXPLORER_MALA; };
+        if (!on_glm(cfg->explorer) || (cfg->explorer2 != PTE_EXPLORER_NONE && !on_glm(cfg->explorer2)))
+            return fail(nullptr, "pte_create: the Bayesian-GLM path is implemented for SliceSampler / AutoMALA / MALA (and Compose of them) only (got explorers %d, %d)",
+                        cfg->explorer, cfg->explorer2);
+        if (cfg->dim < 1 || cfg->dim > 512)
+            return fail(nullptr, "pte_create: the Bayesian-GLM path keeps the replica in the registers of one wave, dim must be in 1..512 (got %lld)", (long long)cfg->dim);
+        if ((cfg->debug_kernel & ~(PTE_KERNEL_FLAG_BITS | PTE_KERNEL_TEST_BITS)) != 0)
+            return fail(nullptr, "pte_create: debug_kernel %d is not available on the Bayesian-GLM path (one kernel serves it)", cfg->debug_kernel);
+        if (cfg->n_chains_variational > 0)
+            return fail(nullptr, "pte_create: two-leg tempering (n_chains_variational > 0) is not available on the Bayesian-GLM path");
+    }
     if (ising) {
         const int64_t L = (int64_t)std::llround(std::sqrt((double)cfg->dim));
         if (L < 2 || L * L != cfg->dim || cfg->dim > 65536) return fail(nullptr, "pte_create: Ising needs dim = base_length^2 <= 65536");
@@ -802,7 +843,7 @@ int pte_create(const pte_config *cfg, pte_engine **out) {
                                  "the Ising path is explored by IsingMetropolis only -- use the reference CPU path for Bool / Integer states");
         if (cfg->explorer != PTE_EXPLORER_ISING_METROPOLIS) return fail(nullptr, "pte_create: the Ising path is explored by IsingMetropolis only");
     } else if (cfg->explorer == PTE_EXPLORER_ISING_METROPOLIS) return fail(nullptr, "pte_create: IsingMetropolis needs the Ising target");
-    if (!swapper && !funnel && !ising && !mixture && cfg->target != PTE_TARGET_MVN_SCALED_PRECISION)
+    if (!swapper && !funnel && !ising && !mixture && !glm && cfg->target != PTE_TARGET_MVN_SCALED_PRECISION)
         return fail(nullptr, "pte_create: target %d has no device log-potential; use the reference CPU path", cfg->target);
     auto grad_based = [](int k) { return k == PTE_EXPLORER_AUTOMALA || k == PTE_EXPLORER_MALA; };
     const bool uses_grad = grad_based(cfg->explorer) || grad_based(cfg->explorer2);
@@ -883,7 +924,8 @@ int pte_create(const pte_config *cfg, pte_engine **out) {
         e.ld = (lw + 1) / 2; e.sw = e.ld;
     }
     // (the swap and recorder kernels see the mixture as the funnel's interpolated path: suff = sum x^2 for the reference, suff2 = the target's log density)
-    e.record_flags = cfg->record_flags; e.target = mixture ? PTE_TARGET_FUNNEL : cfg->target; e.test_swapper_pr = cfg->target_params[0];
+    // (and the Bayesian GLM too: suff2 = its target log density, prior included)
+    e.record_flags = cfg->record_flags; e.target = (mixture || glm) ? PTE_TARGET_FUNNEL : cfg->target; e.test_swapper_pr = cfg->target_params[0];
     const int64_t dd = d > 0 ? d : 1;
     int rc = 0;
     rc |= dev_alloc(h, &e.x, (size_t)(K * (e.ld > 0 ? e.ld : 1)));
@@ -990,8 +1032,8 @@ int pte_create(const pte_config *cfg, pte_engine **out) {
         if (hipEventElapsedTime(&ms, init_a, init_b) == hipSuccess) h->init_ms = ms;
         hipEventDestroy(init_a); hipEventDestroy(init_b);
     }
-    if (funnel || ising || mixture) {
-        // funnel, Gaussian mixture: initialization(::LogDensity, rng, i) = zeros(dim); Ising: falses(L, L) (examples/ising.jl:85) (test/supporting/dimensional-analysis.jl:24): the streams
+    if (funnel || ising || mixture || glm) {
+        // funnel, Gaussian mixture, Bayesian GLM: initialization(::LogDensity, rng, i) = zeros(dim); Ising: falses(L, L) (examples/ising.jl:85) (test/supporting/dimensional-analysis.jl:24): the streams
         // stay untouched; suff2 = funnel(0) = d terms evaluated on the host exactly like the kernels' tree of equal terms
         std::vector<uint64_t> rngs((size_t)(2 * K));
         const uint64_t G = 0x9e3779b97f4a7c15ULL;
@@ -1099,6 +1141,7 @@ int pte_swap(pte_engine *h, int64_t scan) {
     if (!h) return 1;
     PTE_ALIVE(h, "pte_swap");
     if (mixture_missing(h)) return mixture_missing_error(h, "pte_swap");
+    if (glm_missing(h)) return glm_missing_error(h, "pte_swap");
     HIP_OK(h, hipSetDevice(h->cfg.device));
     if (launch_swap(h, scan)) return 1;
     return check_device_error(h);
@@ -1109,6 +1152,7 @@ int pte_run_scans(pte_engine *h, int64_t first_scan, int64_t n_scans) {
     HIP_OK(h, hipSetDevice(h->cfg.device));
     PTE_ALIVE(h, "pte_run_scans");
     if (mixture_missing(h)) return mixture_missing_error(h, "pte_run_scans");
+    if (glm_missing(h)) return glm_missing_error(h, "pte_run_scans");
     if (h->world != 1) return run_scans_sharded(h, first_scan, n_scans);
     if (fused_scans_eligible(h, n_scans)) {
         if (h->fused_skip > 0) h->fused_skip -= 1;         // a recent launch found the device shared: not this call (run_scans_fused)
@@ -1801,6 +1845,8 @@ int pte_group_run_scans(pte_engine *const *hs, int32_t G, int64_t first_scan, in
     pte_engine *h0 = hs[0];
     for (int32_t g = 0; g < G; ++g)
         if (hs[g] && mixture_missing(hs[g])) return mixture_missing_error(h0, "pte_group_run_scans");
+    for (int32_t g = 0; g < G; ++g)
+        if (hs[g] && glm_missing(hs[g])) return glm_missing_error(h0, "pte_group_run_scans");
     for (int g = 0; g < G; ++g) {
         pte_engine *h = hs[g];
         if (!h) return fail(h0, "pte_group_run_scans: engine %d is null", g);
@@ -1853,6 +1899,7 @@ const char *pte_kernel_name(const pte_engine *h) {
         // its sixteen-block instantiation for d > 512 holds 255 VGPRs + 7 AGPRs and does not touch scratch)
         if (h->cfg.target == PTE_TARGET_FUNNEL) return "k_explore_automala";
         if (h->cfg.target == PTE_TARGET_GAUSSIAN_MIXTURE) return "k_explore_mixture";
+        if (h->cfg.target == PTE_TARGET_BAYESIAN_GLM) return "k_explore_glm";
         switch (h->slice_impl) {
         case 1: return "k_explore_slice"; case 2: return "k_explore_slice2"; case 5: return "k_explore_slice5";
         case 7: return "k_explore_slice7";
@@ -1864,6 +1911,7 @@ const char *pte_kernel_name(const pte_engine *h) {
         // d > 512: four waves per replica (pte_automala_mw.hpp, round 6); the one-wave kernel with sixteen blocks per lane -- 250-300 spilled VGPRs,
         // "unoptimised" in rounds 1-5 -- survives in the test build as its A/B reference
         if (h->cfg.target == PTE_TARGET_GAUSSIAN_MIXTURE) return "k_explore_mixture";
+        if (h->cfg.target == PTE_TARGET_BAYESIAN_GLM) return "k_explore_glm";
         if (h->d > 512) return (h->cfg.debug_kernel & PTE_KERNEL_TEST_LANGEVIN_ONE_WAVE) ? "k_explore_automala [test build: one wave, sixteen blocks per lane]" : "k_explore_langevin_mw";
         return "k_explore_automala";
     case PTE_EXPLORER_AAPS: return "k_explore_aaps";
@@ -1925,6 +1973,14 @@ int refresh_mixture_stats(pte_engine *h) {
     HIP_OK(h, hipStreamSynchronize(h->stream));
     return 0;
 }
+int refresh_glm_stats(pte_engine *h) {
+    const int E = h->d <= 64 ? 1 : h->d <= 128 ? 2 : h->d <= 256 ? 4 : 8;
+    if (glm_refresh_stats(E, h->glm_lik, (unsigned)h->K, h->stream, h->dev, h->glm, h->cfg.target_params[0]))
+        return fail(h, "this build holds no Bayesian-GLM kernel for dim %lld", (long long)h->d);
+    HIP_OK(h, hipGetLastError());
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
 }  // namespace
 
 // The Gaussian-mixture target.  Host, once per call: lw_k = log w_k - logsumexp(log w), c_k = lw_k - sum_i log sigma_ki - (d/2) log 2 pi
@@ -1974,6 +2030,57 @@ int pte_set_target_mixture(pte_engine *h, int64_t n_components, const double *we
     return refresh_mixture_stats(h);                               // suff / suff2 of the current states
 }
 
+// The Bayesian GLM.  Host, once per call: c_prior = -(d/2) log(2 pi / p), c_obs = 0 (logit) or -n (log sigma + log(2 pi) / 2)
+// (normal), 1 / sigma^2, 1 / (2 sigma^2); uploaded as Xc [d][n_pad] (column-major), Xr [n][ld] (row-major, the state row's stride) and
+// y [n_pad], zero-padded, into one allocation sized once for the largest n this d admits.
+int pte_set_target_glm(pte_engine *h, int32_t likelihood, int64_t n_obs, const double *X, const double *y, double noise_sd) {
+    if (!h) return 1;
+    PTE_ALIVE(h, "pte_set_target_glm");
+    if (h->cfg.target != PTE_TARGET_BAYESIAN_GLM)
+        return fail(h, "pte_set_target_glm: this engine's target is %d, not PTE_TARGET_BAYESIAN_GLM", h->cfg.target);
+    if (likelihood != PTE_GLM_BERNOULLI_LOGIT && likelihood != PTE_GLM_NORMAL_IDENTITY)
+        return fail(h, "pte_set_target_glm: likelihood must be PTE_GLM_BERNOULLI_LOGIT (0) or PTE_GLM_NORMAL_IDENTITY (1) (got %d)", likelihood);
+    const int64_t d = h->d, ld = h->dev.ld;
+    if (n_obs < 1 || n_obs > 4096)
+        return fail(h, "pte_set_target_glm: the device holds 1..4096 observations (got %lld)", (long long)n_obs);
+    if (n_obs * d > 131072)
+        return fail(h, "pte_set_target_glm: n_obs * dim must be <= 131072 (got %lld * %lld)", (long long)n_obs, (long long)d);
+    if (!X || !y) return fail(h, "pte_set_target_glm: null argument");
+    for (int64_t i = 0; i < n_obs; ++i) {
+        for (int64_t j = 0; j < d; ++j)
+            if (!std::isfinite(X[i * d + j]))
+                return fail(h, "pte_set_target_glm: X[%lld][%lld] must be finite (got %g)", (long long)i, (long long)j, X[i * d + j]);
+        if (!std::isfinite(y[i])) return fail(h, "pte_set_target_glm: y[%lld] must be finite (got %g)", (long long)i, y[i]);
+        if (likelihood == PTE_GLM_BERNOULLI_LOGIT && y[i] != 0.0 && y[i] != 1.0)
+            return fail(h, "pte_set_target_glm: the Bernoulli-logit likelihood needs y in {0, 1} (y[%lld] = %g)", (long long)i, y[i]);
+    }
+    if (likelihood == PTE_GLM_NORMAL_IDENTITY && (!(noise_sd > 0) || !std::isfinite(noise_sd)))
+        return fail(h, "pte_set_target_glm: the normal-identity likelihood needs noise_sd positive and finite (got %g)", noise_sd);
+    HIP_OK(h, hipSetDevice(h->cfg.device));
+    const int64_t n = n_obs, n_pad = (n + 63) & ~(int64_t)63;
+    const int64_t n_max = std::min<int64_t>(4096, 131072 / d), n_pad_max = (n_max + 63) & ~(int64_t)63;
+    const int64_t xc_len = d * n_pad_max, xr_len = n_max * ld + 512;        // (512 zeros behind the last row: lanes past d read them)
+    std::vector<double> buf((size_t)(xc_len + xr_len + n_pad_max), 0.0);
+    double *xc = buf.data(), *xr = xc + xc_len, *yy = xr + xr_len;
+    for (int64_t i = 0; i < n; ++i) {
+        for (int64_t j = 0; j < d; ++j) { xc[j * n_pad + i] = X[i * d + j]; xr[i * ld + j] = X[i * d + j]; }
+        yy[i] = y[i];
+    }
+    const double p = h->cfg.target_params[0], LOG2PI = 1.8378770664093453;
+    if (!h->d_glm && dev_alloc(h, &h->d_glm, buf.size(), false)) return 1;
+    HIP_OK(h, hipMemcpyAsync(h->d_glm, buf.data(), sizeof(double) * buf.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    GlmParams &g = h->glm;
+    g.xc = h->d_glm; g.xr = h->d_glm + xc_len; g.y = h->d_glm + xc_len + xr_len;
+    g.n = (int)n; g.n_pad = (int)n_pad; g.ld = ld;
+    g.c_prior = -((double)d / 2.0) * std::log(2.0 * M_PI / p);
+    g.c_obs = likelihood == PTE_GLM_NORMAL_IDENTITY ? -(double)n * (std::log(noise_sd) + 0.5 * LOG2PI) : 0.0;
+    g.w1 = likelihood == PTE_GLM_NORMAL_IDENTITY ? 1.0 / (noise_sd * noise_sd) : 0.0;
+    g.w2 = likelihood == PTE_GLM_NORMAL_IDENTITY ? 1.0 / (2.0 * (noise_sd * noise_sd)) : 0.0;
+    h->glm_lik = likelihood;
+    return refresh_glm_stats(h);                                   // suff / suff2 of the current states
+}
+
 // update_reference! + update_path_variational (src/variational/variational.jl:28-41, GaussianReference.jl:24-31): from now on
 // the chains with uses[c] != 0 run InterpolatingPath(GaussianReference(mean, std), target).  mean = std = NULL deactivates.
 int pte_set_variational_reference(pte_engine *h, const double *mean, const double *std_dev, int64_t dim, const int32_t *uses) {
@@ -2010,6 +2117,7 @@ int pte_get_state(const pte_engine *hc, double *state, int64_t *chain, uint64_t 
     if (!h) return 1;
     PTE_ALIVE(h, "pte_get_state");
     if (mixture_missing(h)) return mixture_missing_error(h, "pte_get_state");
+    if (glm_missing(h)) return glm_missing_error(h, "pte_get_state");
     HIP_OK(h, hipSetDevice(h->cfg.device));
     const int64_t N = h->K, d = h->d;
     const bool ising = h->cfg.target == PTE_TARGET_ISING;
@@ -2098,6 +2206,7 @@ int pte_set_state(pte_engine *h, const double *state, const int64_t *chain, cons
         HIP_OK(h, e1);
         if (h->cfg.target == PTE_TARGET_FUNNEL && refresh_funnel_stats(h)) return 1;   // + the target (and variational) log densities
         if (h->cfg.target == PTE_TARGET_GAUSSIAN_MIXTURE && h->mix_K > 0 && refresh_mixture_stats(h)) return 1;   // + the mixture's log densities
+        if (h->cfg.target == PTE_TARGET_BAYESIAN_GLM && h->glm.n > 0 && refresh_glm_stats(h)) return 1;           // + the GLM's target log densities
     }
     return 0;
 }
@@ -2147,6 +2256,7 @@ int pte_set_rng_policy(int32_t device, uint32_t policy) {
     if (e == hipSuccess) e = (hipError_t)langevin_set_rng_policy(policy);       // the second translation unit's copy of the word
     if (e == hipSuccess) e = (hipError_t)aaps_set_rng_policy(policy);           // ... and the third's
     if (e == hipSuccess) e = (hipError_t)mixture_set_rng_policy(policy);        // ... and the fourth's
+    if (e == hipSuccess) e = (hipError_t)glm_set_rng_policy(policy);            // ... and the fifth's
     if (e == hipSuccess) e = hipDeviceSynchronize();
     return e == hipSuccess ? 0 : fail(nullptr, "pte_set_rng_policy: %s", hipGetErrorString(e));
 }

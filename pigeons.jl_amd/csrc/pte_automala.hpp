@@ -10,8 +10,11 @@
 //   TGT_FUNNEL InterpolatedAD of {ScaledPrecisionNormal(p0) reference, Neal's funnel}
 //              (src/explorers/BufferedAD.jl:89-112; funnel test/supporting/dimensional-analysis.jl:36-48)
 //   TGT_MIXTURE the same path with a normalised mixture of KB (or fewer) diagonal Gaussians as the target (pte_mixture.hpp)
+//   TGT_GLM    the same path with prior x likelihood of a Bayesian GLM as the target, LIK = GLM_* (pte_glm.hpp): the one family
+//              that reads data -- through LDS, outside the register-only scheme above
 #pragma once
 #include "pte_automala_params.hpp"
+#include "pte_glm_params.hpp"
 
 namespace pte {
 
@@ -94,8 +97,13 @@ __device__ __forceinline__ double sqr_norm_regs(const double (&v)[E]) {
 
 // FULL: d == 64 E, every lane of every block holds an element -- the masks, selects and EXEC-guarded divisions of a ragged last
 // block vanish (25 instructions of ~600 per leapfrog at E = 2)
-template <int E, int TGT, bool FULL = false, int KB = 1>
-struct AmTarget {
+// TGT_GLM's data and this wave's LDS (theta [64 E], then r [n_pad]): an empty base everywhere else, so that the other families' AmTarget
+// keeps its layout -- and their instantiations their generated code (a larger AmTarget moved k_explore_aaps<4, TGT_FUNNEL>'s)
+template <bool ON> struct AmGlmData {};
+template <> struct AmGlmData<true> { GlmParams gl; double *glds; };
+
+template <int E, int TGT, bool FULL = false, int KB = 1, int LIK = 0>
+struct AmTarget : AmGlmData<TGT == TGT_GLM> {
     int64_t d; int lane;
     double nhp, nprec;          // MVN: -0.5*prec, -prec of this chain
     double beta, omb, ref_nhp, ref_nprec, log3;   // funnel path
@@ -246,9 +254,94 @@ struct AmTarget {
         double S, Q, dummy[E];
         return mixture_and_sqr_norm<false, false>(x, dummy, S, x, Q);
     }
+    // the GLM's target log density: target = -(p/2) S + c_prior + sum_i l_i(eta_i) + c_obs, eta = X theta.  Two passes through
+    // this wave's LDS: theta is broadcast from it to lanes that run over observations (eta_i sequential in j, one fused multiply-add per
+    // block of 64 observations; lane l sums its own l_i in increasing i), then, GRAD, r_i = dl_i / deta_i goes back through it to lanes that
+    // run over coordinates (sum_i X_ij r_i sequential in i).  The 64 lane sums are reduced over the fixed tree in lockstep with S (and Q).
+    template <bool GRAD, bool WITH_Q>
+    __device__ __forceinline__ double glm_and_sqr_norm(const double (&x)[E], double (&g)[E], double &S, const double (&q)[E], double &Q) const {
+        constexpr int CH = 4;                           // blocks of observations per pass over theta (the last chunk re-reads its last block)
+        const GlmParams &gl = this->gl;
+        double *th = this->glds, *rr = this->glds + 64 * E;
+        const int n = gl.n, nb = gl.n_pad >> 6;
+        __syncthreads();                                // the last evaluation's reads of theta and r are done
+#pragma unroll
+        for (int j = 0; j < E; ++j) th[64 * j + lane] = x[j];
+        __syncthreads();
+        double lsum = 0.0;
+        for (int m0 = 0; m0 < nb; m0 += CH) {
+            int off[CH];
+            double eta[CH];
+#pragma unroll
+            for (int c = 0; c < CH; ++c) { off[c] = 64 * min(m0 + c, nb - 1) + lane; eta[c] = 0.0; }
+            const double *col = gl.xc;
+            for (int64_t j = 0; j < d; ++j, col += gl.n_pad) {
+                const double t = th[j];                 // one address: a broadcast
+#pragma unroll
+                for (int c = 0; c < CH; ++c) eta[c] = __builtin_fma(col[off[c]], t, eta[c]);
+            }
+#pragma unroll
+            for (int c = 0; c < CH; ++c) {
+                if (m0 + c >= nb) break;
+                const int i = 64 * (m0 + c) + lane;
+                const bool ok = i < n;                  // padded observations contribute exactly 0 (a zero row would give -log 2 under the logit)
+                const double yi = gl.y[i], e = eta[c];
+                double l, r;
+                if constexpr (LIK == GLM_BERNOULLI_LOGIT) {
+                    const double t = exp(-fabs(e));     // softplus(e) = max(e, 0) + log1p(exp(-|e|)); sigmoid in the sign-split form
+                    l = yi * e - (fmax(e, 0.0) + log1p(t));
+                    r = yi - (e >= 0.0 ? 1.0 : t) / (1.0 + t);
+                } else {
+                    const double res = yi - e;
+                    l = -(res * res) * gl.w2;
+                    r = res * gl.w1;
+                }
+                if (ok) lsum = lsum + l;
+                if (GRAD) rr[i] = ok ? r : 0.0;
+            }
+        }
+        constexpr int NS = 2 + (WITH_Q ? 1 : 0);
+        double t[NS][E], out[NS];
+#pragma unroll
+        for (int j = 0; j < E; ++j) {
+            t[0][j] = x[j] * x[j];
+            t[1][j] = j == 0 ? lsum : 0.0;
+            if (WITH_Q) t[(NS - 1) % NS][j] = q[j] * q[j];
+        }
+        tree_sum_regs_multi<E, NS>(t, out);
+        S = out[0];
+        if (WITH_Q) Q = out[(NS - 1) % NS];
+        const double lp = (((ref_nhp * S) + gl.c_prior) + out[1]) + gl.c_obs;
+        if (GRAD) {
+            __syncthreads();                            // every r_i is in LDS
+            double acc[E];
+#pragma unroll
+            for (int j = 0; j < E; ++j) acc[j] = 0.0;
+            const double *row = gl.xr + lane;           // (lanes past d read the zero padding or the next row: discarded below)
+            for (int i = 0; i < n; ++i, row += gl.ld) {
+                const double ri = rr[i];
+#pragma unroll
+                for (int j = 0; j < E; ++j) acc[j] = __builtin_fma(row[64 * j], ri, acc[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < E; ++j) g[j] = valid(j) ? (ref_nprec * x[j]) + acc[j] : 0.0;
+        }
+        return lp;
+    }
+    __device__ __forceinline__ double glm(const double (&x)[E]) const {
+        double S, Q, dummy[E];
+        return glm_and_sqr_norm<false, false>(x, dummy, S, x, Q);
+    }
     // log_potentials[chain](x) as a plain callable: InterpolatedLogPotential(x) (src/paths/InterpolatedLogPotential.jl:9-16)
     // WITH its beta == 0 / beta == 1 short-circuits -- what SliceSampler evaluates (the AD form below has none)
     __device__ __forceinline__ double path_lp(const double (&x)[E]) const {
+        if constexpr (TGT == TGT_GLM) {
+            if (beta == 0.0) return ref_nhp * sqr_norm_regs<E>(x);
+            double S, Q, dummy[E];
+            const double l2 = glm_and_sqr_norm<false, false>(x, dummy, S, x, Q);
+            if (beta == 1.0) return l2;
+            return omb * (ref_nhp * S) + beta * l2;
+        }
         if (TGT == TGT_MIXTURE) {
             if (beta == 0.0) return ref_nhp * sqr_norm_regs<E>(x);
             double S, Q, dummy[E];
@@ -268,6 +361,10 @@ struct AmTarget {
     __device__ __forceinline__ double logdensity(const double (&x)[E]) const {
         if (TGT == TGT_MVN) return nhp * sqr_norm_regs<E>(x);
         double S, l2, dummy[E], dq;
+        if constexpr (TGT == TGT_GLM) {
+            l2 = glm_and_sqr_norm<false, false>(x, dummy, S, x, dq);
+            return omb * (ref_nhp * S) + beta * l2;
+        }
         if (TGT == TGT_MIXTURE) {
             l2 = mixture_and_sqr_norm<false, false>(x, dummy, S, x, dq);
             return omb * (ref_nhp * S) + beta * l2;
@@ -296,6 +393,14 @@ struct AmTarget {
         double logdens = 0.0;
         double g2[E];
         double l2;
+        if constexpr (TGT == TGT_GLM) {
+            l2 = glm_and_sqr_norm<true, WITH_Q>(x, g2, S, q, Q);
+            logdens += (ref_nhp * S) * omb;
+            logdens += l2 * beta;
+#pragma unroll
+            for (int j = 0; j < E; ++j) g[j] = (ref_nprec * x[j]) * omb + g2[j] * beta;
+            return logdens;
+        }
         if (TGT == TGT_MIXTURE) {
             l2 = mixture_and_sqr_norm<true, WITH_Q>(x, g2, S, q, Q);
             logdens += (ref_nhp * S) * omb;
@@ -340,9 +445,11 @@ __device__ __forceinline__ int64_t am_chain_of_workgroup(int64_t K, int64_t wg) 
 
 // DIRECT (the scan loop with several chains per workgroup, k_scans_automala_wg): `wg` IS the local chain, and the table staging ends in a
 // wave-level wait instead of a workgroup barrier -- every wave writes all the (identical) entries itself, so it only has to see its own stores
-// KB, mp: TGT_MIXTURE only -- the components' bucket (K <= KB) and parameters
-template <int E, int TGT, bool SLICE = false, bool FULL = false, bool DIRECT = false, int KB = 1>
-__device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const int64_t wg, const MixParams &mp = MixParams{}) {      // wg: blockIdx.x
+// KB, mp: TGT_MIXTURE only -- the components' bucket (K <= KB) and parameters.  LIK, gp: TGT_GLM only -- the likelihood and the data
+// (the workgroup's dynamic LDS holds theta and r: pte_glm.hpp)
+template <int E, int TGT, bool SLICE = false, bool FULL = false, bool DIRECT = false, int KB = 1, int LIK = 0>
+__device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const int64_t wg, const MixParams &mp = MixParams{},
+                                              const GlmParams &gp = GlmParams{}) {      // wg: blockIdx.x
     constexpr int NLU = (E == 1 ? 0 : E == 2 ? 1 : E == 4 ? 2 : E == 8 ? 3 : 4);
     const int lane = lane_id();
     // the ziggurat tables of the momentum draws, staged once: a global gather per block of draws costs a memory round trip each time
@@ -360,9 +467,13 @@ __device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const in
     const int slot = e.slot_of_chain[cl];
     const int64_t d = e.d;
     double *xrow = e.x + (int64_t)slot * e.ld;
-    AmTarget<E, TGT, FULL, KB> T;
+    AmTarget<E, TGT, FULL, KB, LIK> T;
     T.d = d; T.lane = lane;
     if (TGT == TGT_MIXTURE) T.load_mixture(mp);
+    if constexpr (TGT == TGT_GLM) {
+        extern __shared__ __attribute__((aligned(16))) double glm_lds[];      // after s_wi / s_ki / s_fi (6 KiB: the base stays 16-B aligned)
+        T.gl = gp; T.glds = glm_lds;
+    }
     T.nhp = e.nhp[c]; T.nprec = e.nprec[c];
     T.beta = e.beta[c]; T.omb = 1.0 - T.beta;
     T.ref_nhp = -0.5 * ap.ref_prec; T.ref_nprec = -ap.ref_prec; T.log3 = ap.log3;
@@ -403,6 +514,10 @@ __device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const in
         }
         if (TGT == TGT_MIXTURE) {
             l20 = T.mixture(x);
+            if (lane == 0) e.suff2[slot] = l20;
+        }
+        if constexpr (TGT == TGT_GLM) {
+            l20 = T.glm(x);
             if (lane == 0) e.suff2[slot] = l20;
         }
         record_after_explore_impl(e, cl, c, slot, lane, lp0, S0, l20, l30);
@@ -722,10 +837,11 @@ __device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const in
     double l2 = 0.0, l3 = 0.0;
     if (TGT == TGT_FUNNEL) l2 = T.funnel(x, nullptr);
     if (TGT == TGT_MIXTURE) l2 = T.mixture(x);
+    if constexpr (TGT == TGT_GLM) l2 = T.glm(x);
     if (v_on) l3 = T.variational_lp(x);
     if (lane == 0) {
         e.suff[slot] = S;
-        if (TGT == TGT_FUNNEL || TGT == TGT_MIXTURE) e.suff2[slot] = l2;
+        if (TGT == TGT_FUNNEL || TGT == TGT_MIXTURE || TGT == TGT_GLM) e.suff2[slot] = l2;
         if (v_on) e.suff3[slot] = l3;
         e.rng[2 * slot] = r.seed;
         e.expl_steps_sum[cl] += (double)steps_sum; e.expl_steps_n[cl] += steps_n;

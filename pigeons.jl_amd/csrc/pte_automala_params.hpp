@@ -8,7 +8,7 @@
 
 namespace pte {
 
-enum { TGT_MVN = 0, TGT_FUNNEL = 2, TGT_MIXTURE = 4 };
+enum { TGT_MVN = 0, TGT_FUNNEL = 2, TGT_MIXTURE = 4, TGT_GLM = 5 };
 
 // TGT_MIXTURE (pte_mixture.hpp): the normalised mixture of K diagonal Gaussians, shared by every replica.  mu / inv: [K][ld]
 // (ld = the state row's stride, zero-padded), c: [K]; the kernels read mu and inv as lane-coalesced global loads.

@@ -35,6 +35,8 @@ const libpte = "libpte.so"
 
 # ---- include/pte.h mirrored ------------------------------------------------------------------------------------------------
 const TARGET_MVN, TARGET_TEST_SWAPPER, TARGET_FUNNEL, TARGET_ISING, TARGET_GAUSSIAN_MIXTURE = Int32(0), Int32(1), Int32(2), Int32(3), Int32(4)
+const TARGET_BAYESIAN_GLM = Int32(5)
+const GLM_BERNOULLI_LOGIT, GLM_NORMAL_IDENTITY = Int32(0), Int32(1)
 const EXPLORER_NONE, EXPLORER_TOY, EXPLORER_SLICE, EXPLORER_AUTOMALA, EXPLORER_ISING, EXPLORER_MALA, EXPLORER_AAPS = Int32.((0, 1, 2, 3, 4, 5, 6))
 const RECORD_ROUND_TRIP, RECORD_INDEX_PROCESS, RECORD_ONLINE, RECORD_TRACES, RECORD_ENERGY_AC1, RECORD_TRACES_EXTENDED =
     UInt32.((1, 2, 4, 8, 16, 32))
@@ -104,6 +106,12 @@ struct DeviceIsing; beta::Float64; base_length::Int; n_sweeps::Int; end
 `DistributionLogPotential(MixtureModel([MvNormal(means[k], Diagonal(std_devs[k] .^ 2)) for k in 1:K], weights))`.  `means` and
 `std_devs` are K x dim.  Used as `Inputs(target = on_mi355x(DeviceGaussianMixture(w, m, s)), reference = ScaledPrecisionNormalLogPotential(p, dim))`."""
 struct DeviceGaussianMixture; weights::Vector{Float64}; means::Matrix{Float64}; std_devs::Matrix{Float64}; end
+"""The posterior of a Bayesian GLM, the device family PTE_TARGET_BAYESIAN_GLM (DESIGN 4.9): prior N(0, I / p) on the d coefficients times
+the likelihood of y given eta = X * theta, `likelihood` = :bernoulli_logit (logistic regression, y in {0, 1}) or :normal_identity (linear
+regression with known `noise_sd`).  X is n x dim.  Used as `Inputs(target = on_mi355x(DeviceBayesianGLM(X, y, :bernoulli_logit, 1.0)),
+reference = ScaledPrecisionNormalLogPotential(p, dim))` -- the reference is the prior.  stepping_stone(pt) + (dim/2) log(2 pi / p) is the
+log evidence."""
+struct DeviceBayesianGLM; X::Matrix{Float64}; y::Vector{Float64}; likelihood::Symbol; noise_sd::Float64; end
 
 # (target code, dim, target_params, reference precision check) of a wrapped target
 device_family(t::ScaledPrecisionNormalPath, inputs) = (TARGET_MVN, t.dim, (t.precision0, t.precision1, 0.0, 0.0))
@@ -122,6 +130,15 @@ function device_family(t::DeviceGaussianMixture, inputs)
     ref isa ScaledPrecisionNormalLogPotential && ref.dim == dim ||
         error("the device Gaussian-mixture path needs reference = ScaledPrecisionNormalLogPotential(precision, $dim); keep the CPU path otherwise")
     return (TARGET_GAUSSIAN_MIXTURE, dim, (ref.precision, 0.0, 0.0, 0.0))
+end
+function device_family(t::DeviceBayesianGLM, inputs)
+    n, dim = size(t.X)
+    length(t.y) == n || error("DeviceBayesianGLM: X is n x dim, y has the n observations")
+    t.likelihood in (:bernoulli_logit, :normal_identity) || error("DeviceBayesianGLM: likelihood :bernoulli_logit or :normal_identity")
+    ref = inputs.reference
+    ref isa ScaledPrecisionNormalLogPotential && ref.dim == dim ||
+        error("the device Bayesian-GLM path needs reference = ScaledPrecisionNormalLogPotential(precision, $dim) (the prior); keep the CPU path otherwise")
+    return (TARGET_BAYESIAN_GLM, dim, (ref.precision, 0.0, 0.0, 0.0))
 end
 device_family(t, inputs) = error("target $(typeof(t)) has no device log-potential family (closed set: include/pte.h PTE_TARGET_*); keep the CPU path")
 
@@ -234,6 +251,12 @@ function Pigeons.create_replicas(inputs::Inputs{<:OnDevice}, shared::Shared, sou
         m = t.target
         check(r, ccall((:pte_set_target_mixture, libpte), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
                        r.handle, length(m.weights), m.weights, collect(vec(permutedims(m.means))), collect(vec(permutedims(m.std_devs)))))
+    end
+    if t.target isa DeviceBayesianGLM               # the data, X row-major [n][dim] as pte_set_target_glm reads it
+        g = t.target
+        lik = g.likelihood === :normal_identity ? GLM_NORMAL_IDENTITY : GLM_BERNOULLI_LOGIT
+        check(r, ccall((:pte_set_target_glm, libpte), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Float64),
+                       r.handle, lik, length(g.y), collect(vec(permutedims(g.X))), g.y, g.noise_sd))
     end
     source === nothing || restore!(r, source)          # FromCheckpoint: pte_set_state from the deserialised Replica structs
     return r

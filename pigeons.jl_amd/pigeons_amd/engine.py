@@ -93,6 +93,14 @@ class Engine:
         sd = np.ascontiguousarray(std_devs, dtype=np.float64).reshape(len(w), -1)
         self._chk(self.L.pte_set_target_mixture(self.h, len(w), _dp(w), _dp(m), _dp(sd)))
 
+    def set_target_glm(self, likelihood, X, y, noise_sd=1.0):
+        """pte_set_target_glm: likelihood GLM_*, X [n][d] (row-major), y [n]"""
+        Xa = np.ascontiguousarray(X, dtype=np.float64)
+        ya = np.ascontiguousarray(y, dtype=np.float64).ravel()
+        if Xa.size != ya.size * self.d:
+            raise ValueError("set_target_glm: X must be n x %d with n = len(y) = %d (got shape %s)" % (self.d, ya.size, Xa.shape))
+        self._chk(self.L.pte_set_target_glm(self.h, int(likelihood), ya.size, _dp(Xa), _dp(ya), float(noise_sd)))
+
     # --- hot path
     def explore(self, scan):
         self._chk(self.L.pte_explore(self.h, scan))

@@ -105,6 +105,63 @@ class GaussianMixture:
         return "GaussianMixture(K=%d, dim=%d)" % (self.n_components, self.dim)
 
 
+class BayesianGLM:
+    """The posterior of a Bayesian generalised linear model, the device's data-reading target: prior N(0, I / p) on the
+    coefficients theta (d of them) times the likelihood of n observations y_i given eta_i = X[i] . theta,
+        likelihood="bernoulli_logit"   y_i in {0, 1}, log p(y_i | eta_i) = y_i eta_i - softplus(eta_i)     (logistic regression)
+        likelihood="normal_identity"   log p(y_i | eta_i) = log N(y_i; eta_i, noise_sd^2)                   (linear regression, known noise)
+    X: n x d, y: n (1 <= n <= 4096, 1 <= d <= 512, n d <= 131072).  Tempered through the default InterpolatingPath(reference, target)
+    (src/targets/target.jl:72-75) from reference=ScaledPrecisionNormalLogPotential(p, d) -- the prior, unnormalised -- to prior x likelihood
+    with the prior normalised; initialization = zeros(d); default explorer SliceSampler (target.jl:20).
+
+    Evidence: stepping_stone(pt) estimates log Z1 / Z0 = log p(y) - (d/2) log(2 pi / p), so the log evidence (marginal likelihood) is
+    stepping_stone(pt) + (d/2) log(2 pi / p)."""
+
+    LIKELIHOODS = {"bernoulli_logit": 0, "normal_identity": 1}
+
+    def __init__(self, X, y, likelihood="bernoulli_logit", noise_sd=1.0):
+        if likelihood not in self.LIKELIHOODS:
+            raise ValueError("BayesianGLM: likelihood must be 'bernoulli_logit' or 'normal_identity' (got %r)" % (likelihood,))
+        X = np.array(X, dtype=np.float64)
+        y = np.array(y, dtype=np.float64)
+        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+            raise ValueError("BayesianGLM: X must be an n x d array")
+        n, d = X.shape
+        if n > 4096:
+            raise ValueError("BayesianGLM: the device holds 1..4096 observations (got %d)" % n)
+        if d > 512:
+            raise ValueError("BayesianGLM: the device keeps theta in one wave's registers, d must be in 1..512 (got %d)" % d)
+        if n * d > 131072:
+            raise ValueError("BayesianGLM: n * d must be <= 131072 (got %d * %d)" % (n, d))
+        if y.ndim != 1 or y.size != n:
+            raise ValueError("BayesianGLM: y must be a vector of the n = %d observations" % n)
+        if not np.all(np.isfinite(X)):
+            raise ValueError("BayesianGLM: X must be finite")
+        if not np.all(np.isfinite(y)):
+            raise ValueError("BayesianGLM: y must be finite")
+        if likelihood == "bernoulli_logit" and not np.all((y == 0.0) | (y == 1.0)):
+            raise ValueError("BayesianGLM: the Bernoulli-logit likelihood needs y in {0, 1}")
+        noise_sd = float(noise_sd)
+        if likelihood == "normal_identity" and not (noise_sd > 0 and math.isfinite(noise_sd)):
+            raise ValueError("BayesianGLM: noise_sd must be positive and finite (got %r)" % (noise_sd,))
+        self.X, self.y, self.likelihood, self.noise_sd = X, y, likelihood, noise_sd
+
+    @property
+    def n_obs(self):
+        return self.X.shape[0]
+
+    @property
+    def dim(self):
+        return self.X.shape[1]
+
+    @property
+    def likelihood_code(self):
+        return self.LIKELIHOODS[self.likelihood]
+
+    def __repr__(self):
+        return "BayesianGLM(%s, n=%d, dim=%d)" % (self.likelihood, self.n_obs, self.dim)
+
+
 @dataclass
 class GaussianReference:
     """src/variational/GaussianReference.jl:4-17: mean-field Gaussian variational reference, refitted every round from
@@ -414,6 +471,11 @@ class PT:
             if not isinstance(ref, ScaledPrecisionNormalLogPotential) or ref.dim != target.dim:
                 raise NotImplementedError("the device Gaussian-mixture path needs reference=ScaledPrecisionNormalLogPotential(prec, dim)")
             kw.update(target=_lib.TARGET_GAUSSIAN_MIXTURE, dim=target.dim, target_params=[ref.precision])
+        elif isinstance(target, BayesianGLM):
+            ref = inputs.reference
+            if not isinstance(ref, ScaledPrecisionNormalLogPotential) or ref.dim != target.dim:
+                raise NotImplementedError("the device Bayesian-GLM path needs reference=ScaledPrecisionNormalLogPotential(prec, dim) -- the prior")
+            kw.update(target=_lib.TARGET_BAYESIAN_GLM, dim=target.dim, target_params=[ref.precision])
         else:
             raise NotImplementedError(
                 "target %r has no device log-potential; use the reference CPU path (Pigeons.jl)" % (target,))
@@ -475,6 +537,9 @@ class PT:
         if isinstance(target, GaussianMixture):          # every engine (rank) holds the components
             for eng in (self.shards.engines if hasattr(self.shards, "engines") else [self.replicas]):
                 eng.set_target_mixture(target.weights, target.means, target.std_devs)
+        if isinstance(target, BayesianGLM):              # every engine (rank) holds the data
+            for eng in (self.shards.engines if hasattr(self.shards, "engines") else [self.replicas]):
+                eng.set_target_glm(target.likelihood_code, target.X, target.y, target.noise_sd)
 
 
 def next_round(pt):
