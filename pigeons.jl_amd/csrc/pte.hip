@@ -21,11 +21,11 @@
 #include "pte_slice5.hpp"
 #include "pte_slice7.hpp"
 #include "pte_slice8.hpp"
-#ifdef PTE_SPLIT_LANGEVIN          // the product build: the Langevin-family kernels are the library's second translation unit (pte_langevin.hip),
-#include "pte_automala_params.hpp" // the AAPS kernels its third (pte_aaps.hip)
+#ifdef PTE_SPLIT_LANGEVIN          // the product build: these kernel families are translation units of their own (pte_automala_params.hpp)
+#include "pte_automala_params.hpp"
 #include "pte_aaps_params.hpp"
-#include "pte_mixture_params.hpp"     // ... and the Gaussian-mixture kernels its fourth (pte_mixture.hip)
-#include "pte_glm_params.hpp"         // ... and the Bayesian-GLM kernels its fifth (pte_glm.hip)
+#include "pte_mixture_params.hpp"
+#include "pte_glm_params.hpp"
 #else                              // tools / development builds: one translation unit
 #include "pte_langevin_launch.hpp"
 #include "pte_aaps.hpp"
@@ -154,17 +154,21 @@ int dev_alloc(pte_engine *h, T **p, size_t n, bool zero = true) {
 }
 
 int next_pow2_log(int64_t n) { int l = 0; while (((int64_t)1 << l) < n) ++l; return l; }
+// 64-coordinate blocks per lane of the register-resident kernels (their template parameter E); the families that stop at d = 512 have no E = 16
+// instantiation: pte_create refuses such an engine, and their launch entry points answer "no such kernel"
+int blocks_per_lane(int64_t d) { return d <= 64 ? 1 : d <= 128 ? 2 : d <= 256 ? 4 : d <= 512 ? 8 : 16; }
+// n_refresh = base_n_refresh * ceil(Int, dim^exponent_n_refresh)  (AutoMALA.jl:120)
+int am_n_refresh(const pte_config *cfg, int64_t d) { return cfg->am_base_n_refresh * (int)std::ceil(std::pow((double)(d > 0 ? d : 1), cfg->am_exponent_n_refresh)); }
 
-// One kernel launch that may carry the timing events of the bracket it stands in (time_begin(h, kind, true) ... time_end(h)): with
-// hipExtLaunchKernelGGL the start / stop events take the kernel's own begin / end timestamps -- what rocprofv3's kernel trace reports --
-// instead of bracketing it with two event-record commands, which add the stream's hand-over time around a ~85 us kernel (~7 us).
-#define PTE_LAUNCH1(KERNEL, grid, block, shmem, stream, ...)                                                                      \
-    do {                                                                                                                          \
-        if (h->ev_open && h->ev_ext && !h->ev_ext_done) {                                                                         \
-            hipExtLaunchKernelGGL(KERNEL, grid, block, shmem, stream, h->events.back().a, h->events.back().b, 0, __VA_ARGS__);    \
-            h->ev_ext_done = true;                                                                                                \
-        } else hipLaunchKernelGGL(KERNEL, grid, block, shmem, stream, __VA_ARGS__);                                               \
-    } while (0)
+// Where the engine's next kernel launch goes: its stream, and -- inside a timing bracket opened for ONE launch (time_begin(h, kind, true) ...
+// time_end(h)) that no launch has taken yet -- the bracket's events, which then ride on that launch (LaunchSite, pte_automala_params.hpp).
+LaunchSite launch_site(pte_engine *h, dim3 grid) {
+    LaunchSite at{grid, h->stream};
+    if (h->ev_open && h->ev_ext && !h->ev_ext_done) { at.ev_a = h->events.back().a; at.ev_b = h->events.back().b; h->ev_ext_done = true; }
+    return at;
+}
+// (`stream` is h->stream at every use)
+#define PTE_LAUNCH1(KERNEL, grid, block, shmem, stream, ...) launch_on(launch_site(h, grid), KERNEL, block, shmem, __VA_ARGS__)
 
 #ifdef PTE_DEV_FEW_NLU   // development builds only (tools/build_variant.sh): the tree depths of d = 1024 and d = 4096, a fifth of the compile time
 #define DISPATCH_NLU_M(nlu, KERNEL, MM, grid, block, stream, ...)                                 \
@@ -204,6 +208,84 @@ int next_pow2_log(int64_t n) { int l = 0; while (((int64_t)1 << l) < n) ++l; ret
 
 #endif
 
+// ---- the target families on a register-resident interpolated path: (1 - beta) ScaledPrecisionNormal(p) + beta target ---------------------
+// Zero initial state, sd = sqrt(target_params[0]) on the ladder, and the swap and recorder kernels see PTE_TARGET_FUNNEL: suff = sum x^2 for
+// the reference, suff2 = the target's log density.  What differs between the families is here, launch_path_kernel and refresh_path_stats
+// below, and the family's pte_set_target_* call.
+struct PathFamily {
+    const char *name;           // in messages: "the <name> path", "the <name> target"
+    const char *data, *setter;  // what pte_<setter> uploads; nullptr: the family needs no data
+    const char *one_kernel;     // why debug_kernel chooses nothing here
+    const char *kernel;         // pte_kernel_name: its one-wave kernel
+};
+const PathFamily *path_family(int target) {
+    static const PathFamily funnel{"funnel", nullptr, nullptr, "one register-resident kernel serves it", "k_explore_automala"},
+                            mixture{"Gaussian-mixture", "components", "pte_set_target_mixture", "one register-resident kernel serves it", "k_explore_mixture"},
+                            glm{"Bayesian-GLM", "data", "pte_set_target_glm", "one kernel serves it", "k_explore_glm"};
+    switch (target) {
+    case PTE_TARGET_FUNNEL: return &funnel;
+    case PTE_TARGET_GAUSSIAN_MIXTURE: return &mixture;
+    case PTE_TARGET_BAYESIAN_GLM: return &glm;
+    default: return nullptr;
+    }
+}
+bool on_interpolated_path(int target) { return path_family(target) != nullptr; }
+// the family's data has been uploaded (true for every target that needs none)
+bool family_ready(const pte_engine *h) {
+    switch (h->cfg.target) {
+    case PTE_TARGET_GAUSSIAN_MIXTURE: return h->mix_K > 0;
+    case PTE_TARGET_BAYESIAN_GLM: return h->glm.n > 0;
+    default: return true;
+    }
+}
+// (`h` reports; `of` is the engine that is not ready -- another one in pte_group_run_scans)
+int family_missing_error(pte_engine *h, const char *what, const pte_engine *of = nullptr) {
+    const PathFamily *f = path_family((of ? of : h)->cfg.target);
+    return fail(h, "%s: the %s target has no %s yet; call %s first", what, f->name, f->data, f->setter);
+}
+int family_no_kernel_error(pte_engine *h) {
+    return fail(h, "this build holds no %s kernel for dim %lld", path_family(h->cfg.target)->name, (long long)h->d);
+}
+
+// the mixture's parameters as the kernels read them (d_mix, pte_set_target_mixture)
+MixParams mixture_params(const pte_engine *h) {
+    MixParams mp;
+    const int64_t ld = h->dev.ld;
+    mp.mu = h->d_mix; mp.inv = h->d_mix + 8 * ld; mp.c = h->d_mix + 16 * ld; mp.K = h->mix_K; mp.ld = ld;
+    return mp;
+}
+
+// One launch of the engine's AutoMALA / MALA / SliceSampler-on-the-path kernel over N replicas (one workgroup each): the family's own on the
+// mixture and GLM paths, the Langevin family's on the funnel and scaled-precision MVN paths.  The open timing bracket's events ride on it.
+int launch_path_kernel(pte_engine *h, int E, bool slice, bool full, int64_t N, const AmParams &ap) {
+    const LaunchSite at = launch_site(h, (unsigned)N);
+    switch (h->cfg.target) {
+    case PTE_TARGET_GAUSSIAN_MIXTURE: return mixture_launch(MixtureLaunch{E, slice, full, at}, h->dev, ap, mixture_params(h)) ? family_no_kernel_error(h) : 0;
+    case PTE_TARGET_BAYESIAN_GLM: return glm_launch(GlmLaunch{E, h->glm_lik, slice, full, at}, h->dev, ap, h->glm) ? family_no_kernel_error(h) : 0;
+    default: break;
+    }
+    LangevinLaunch L{E, h->cfg.target == PTE_TARGET_FUNNEL ? TGT_FUNNEL : TGT_MVN, slice, full, at};
+    L.one_wave16 = (h->cfg.debug_kernel & PTE_KERNEL_TEST_LANGEVIN_ONE_WAVE) != 0;       // (test build only: pte_create refuses the flag otherwise)
+    if (E == 16 && !slice && !L.one_wave16) HIP_OK(h, hipMemsetAsync(h->dev.pace, 0, sizeof(unsigned int), h->stream));      // k_explore_langevin_mw: its workgroups count their refreshes here
+    if (langevin_launch(L, h->dev, ap)) return fail(h, "this build holds no Langevin-family kernels (PTE_DEV_NO_LANGEVIN)");
+    return 0;
+}
+
+// swap statistics of every slot recomputed from the stored states: suff2 (and the funnel's suff3) = the target's (and variational) log densities
+int refresh_path_stats(pte_engine *h) {
+    const int E = blocks_per_lane(h->d);
+    const unsigned N = (unsigned)h->K;
+    switch (h->cfg.target) {
+    case PTE_TARGET_FUNNEL: langevin_refresh_funnel_stats(E, N, h->stream, h->dev, std::log(3.0)); break;
+    case PTE_TARGET_GAUSSIAN_MIXTURE: if (mixture_refresh_stats(E, N, h->stream, h->dev, mixture_params(h))) return family_no_kernel_error(h); break;
+    case PTE_TARGET_BAYESIAN_GLM: if (glm_refresh_stats(E, h->glm_lik, N, h->stream, h->dev, h->glm, h->cfg.target_params[0])) return family_no_kernel_error(h); break;
+    default: return 0;
+    }
+    HIP_OK(h, hipGetLastError());
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
 // discretize(path, schedule): per-chain constants of ScaledPrecisionNormalLogPotential
 // (reference src/paths/ScaledPrecisionNormalPath.jl:45-48, src/schedules/discretize.jl:6-7).
 int upload_ladder(pte_engine *h) {
@@ -218,7 +300,7 @@ int upload_ladder(pte_engine *h) {
             nprec[c] = -prec;
             sd[c] = std::sqrt(prec);
         }
-    } else if (h->cfg.target == PTE_TARGET_FUNNEL || h->cfg.target == PTE_TARGET_GAUSSIAN_MIXTURE || h->cfg.target == PTE_TARGET_BAYESIAN_GLM) {
+    } else if (on_interpolated_path(h->cfg.target)) {
         for (int64_t c = 0; c < N; ++c) sd[c] = std::sqrt(h->cfg.target_params[0]);   // reference end point
     }
     HIP_OK(h, hipMemcpyAsync(h->d_nhp, nhp.data(), sizeof(double) * N, hipMemcpyHostToDevice, h->stream));
@@ -326,60 +408,52 @@ static int langevin_mw_paced(pte_engine *h) {
     return (h->n_cus > 0 && h->K > (int64_t)h->n_cus && h->K <= 4 * (int64_t)h->n_cus) ? 1 : 0;
 }
 
-// one launch of the Langevin-family kernel (pte_automala_params.hpp); like PTE_LAUNCH1, the open timing bracket's events ride on it
-static int launch_langevin(pte_engine *h, int E, int target, bool slice, bool full, int64_t N, const AmParams &ap) {
-    LangevinLaunch L{E, target, slice, full, (unsigned)N, h->stream, false, nullptr, nullptr};
-    L.one_wave16 = (h->cfg.debug_kernel & PTE_KERNEL_TEST_LANGEVIN_ONE_WAVE) != 0;       // (test build only: pte_create refuses the flag otherwise)
-    if (h->ev_open && h->ev_ext && !h->ev_ext_done) { L.ext = true; L.ev_a = h->events.back().a; L.ev_b = h->events.back().b; h->ev_ext_done = true; }
-    if (E == 16 && !slice && !L.one_wave16) HIP_OK(h, hipMemsetAsync(h->dev.pace, 0, sizeof(unsigned int), h->stream));      // k_explore_langevin_mw: its workgroups count their refreshes here
-    if (langevin_launch(L, h->dev, ap)) return fail(h, "this build holds no Langevin-family kernels (PTE_DEV_NO_LANGEVIN)");
-    return 0;
+// ---- kernel parameters from the engine's configuration -----------------------------------------------------------------------------------
+// SliceSampler on an interpolated path: the family's register-resident kernel in its slice mode (full log potential per evaluation, as the
+// reference's slice_sample! does for any log_potential)
+AmParams slice_path_params(const pte_engine *h) {
+    AmParams ap{};
+    ap.slice = 1; ap.slice_w = h->cfg.slice_w; ap.slice_p = h->cfg.slice_p; ap.slice_n_passes = h->cfg.slice_n_passes;
+    ap.slice_max_iter = h->cfg.slice_max_iter;
+    ap.ref_prec = h->cfg.target_params[0]; ap.log3 = std::log(3.0);
+    return ap;
 }
-
-// one launch of k_explore_aaps (pte_aaps_params.hpp); like launch_langevin, the open timing bracket's events ride on it
-static int launch_aaps(pte_engine *h, int E, int target, bool full, int64_t N, const AapsParams &ap) {
-    AapsLaunch L{E, target, full, (unsigned)N, h->stream, false, nullptr, nullptr};
-    if (h->ev_open && h->ev_ext && !h->ev_ext_done) { L.ext = true; L.ev_a = h->events.back().a; L.ev_b = h->events.back().b; h->ev_ext_done = true; }
-    if (aaps_launch(L, h->dev, ap)) return fail(h, "this build holds no AAPS kernel for dim %lld", (long long)h->d);
-    return 0;
+// AutoMALA / MALA (`kind`); use_mh: scan != 1 (AutoMALA.jl:87,96-102) -- the one-launch scan loop decides it per scan inside and is given 1
+AmParams langevin_params(pte_engine *h, int kind, int use_mh) {
+    AmParams ap{};
+    ap.mala = (kind == PTE_EXPLORER_MALA) ? 1 : 0;
+    ap.step_size = ap.mala ? h->cfg.am_step_size : h->step_size; ap.n_refresh = h->am_n_refresh; ap.precond = h->cfg.am_preconditioner;
+    ap.p0 = h->cfg.am_p0; ap.p1 = h->cfg.am_p1;
+    ap.target_std = h->have_target_std ? h->d_target_std : nullptr;
+    ap.use_mh = use_mh;
+    ap.ref_prec = h->cfg.target_params[0]; ap.log3 = std::log(3.0);
+    ap.pace = h->d > 512 ? langevin_mw_paced(h) : 0;
+    return ap;
 }
-
-// the mixture's parameters as the kernels read them (d_mix, pte_set_target_mixture)
-static MixParams mixture_params(const pte_engine *h) {
-    MixParams mp;
-    const int64_t ld = h->dev.ld;
-    mp.mu = h->d_mix; mp.inv = h->d_mix + 8 * ld; mp.c = h->d_mix + 16 * ld; mp.K = h->mix_K; mp.ld = ld;
-    return mp;
-}
-// one launch of k_explore_mixture (pte_mixture_params.hpp); like launch_langevin, the open timing bracket's events ride on it
-static int launch_mixture(pte_engine *h, int E, bool slice, bool full, int64_t N, const AmParams &ap) {
-    MixtureLaunch L{E, slice, full, (unsigned)N, h->stream, false, nullptr, nullptr};
-    if (h->ev_open && h->ev_ext && !h->ev_ext_done) { L.ext = true; L.ev_a = h->events.back().a; L.ev_b = h->events.back().b; h->ev_ext_done = true; }
-    if (mixture_launch(L, h->dev, ap, mixture_params(h))) return fail(h, "this build holds no Gaussian-mixture kernel for dim %lld", (long long)h->d);
-    return 0;
-}
-static bool mixture_missing(const pte_engine *h) { return h->cfg.target == PTE_TARGET_GAUSSIAN_MIXTURE && h->mix_K == 0; }
-static int mixture_missing_error(pte_engine *h, const char *what) {
-    return fail(h, "%s: the Gaussian-mixture target has no components yet; call pte_set_target_mixture first", what);
-}
-// one launch of k_explore_glm (pte_glm_params.hpp); like launch_langevin, the open timing bracket's events ride on it
-static int launch_glm(pte_engine *h, int E, bool slice, bool full, int64_t N, const AmParams &ap) {
-    GlmLaunch L{E, h->glm_lik, slice, full, (unsigned)N, h->stream, false, nullptr, nullptr};
-    if (h->ev_open && h->ev_ext && !h->ev_ext_done) { L.ext = true; L.ev_a = h->events.back().a; L.ev_b = h->events.back().b; h->ev_ext_done = true; }
-    if (glm_launch(L, h->dev, ap, h->glm)) return fail(h, "this build holds no Bayesian-GLM kernel for dim %lld", (long long)h->d);
-    return 0;
-}
-static bool glm_missing(const pte_engine *h) { return h->cfg.target == PTE_TARGET_BAYESIAN_GLM && h->glm.n == 0; }
-static int glm_missing_error(pte_engine *h, const char *what) {
-    return fail(h, "%s: the Bayesian-GLM target has no data yet; call pte_set_target_glm first", what);
+// AAPS (pte_aaps.hpp); the step size is not adapted
+AapsParams aaps_params(const pte_engine *h) {
+    AapsParams ap{};
+    ap.step_size = h->cfg.am_step_size; ap.K = h->cfg.aaps_K; ap.precond = h->cfg.am_preconditioner;
+    ap.p0 = h->cfg.am_p0; ap.p1 = h->cfg.am_p1;
+    ap.target_std = h->have_target_std ? h->d_target_std : nullptr;
+    ap.ref_prec = h->cfg.target_params[0]; ap.log3 = std::log(3.0);
+    return ap;
 }
 
 int launch_explorer_kind(pte_engine *h, int64_t scan, int kind);
+// the explorer kernel(s) of one scan; Compose(first, second), src/explorers/Compose.jl:16-19: two kernels back to back on the replica's stream
+int launch_explorers(pte_engine *h, int64_t scan) {
+    if (h->cfg.explorer2 == PTE_EXPLORER_NONE) { h->dev.compose_phase = 0; return launch_explorer_kind(h, scan, h->cfg.explorer); }
+    h->dev.compose_phase = 1;
+    int rc = launch_explorer_kind(h, scan, h->cfg.explorer);
+    h->dev.compose_phase = 2;
+    if (!rc) rc = launch_explorer_kind(h, scan, h->cfg.explorer2);
+    h->dev.compose_phase = 0;
+    return rc;
+}
 int launch_explore(pte_engine *h, int64_t scan) {
-    (void)scan;
     const int64_t N = h->K;
-    if (mixture_missing(h)) return mixture_missing_error(h, "pte_explore");
-    if (glm_missing(h)) return glm_missing_error(h, "pte_explore");
+    if (!family_ready(h)) return family_missing_error(h, "pte_explore");
     if ((h->cfg.record_flags & PTE_RECORD_TRACES) && h->scans_in_round >= h->cfg.max_scans_per_round)
         return fail(h, "traces buffer full: %lld scans since the last pte_reduce (max_scans_per_round = %lld)",
                     (long long)h->scans_in_round, (long long)h->cfg.max_scans_per_round);
@@ -392,28 +466,13 @@ int launch_explore(pte_engine *h, int64_t scan) {
         return fail(h, "energy log full: %lld scans since the last pte_reduce (max_scans_per_round = %lld)",
                     (long long)h->scans_in_round, (long long)h->cfg.max_scans_per_round);
     h->dev.trace_idx = h->scans_in_round;
-    if (h->dev.eac_log && h->cfg.explorer != PTE_EXPLORER_NONE) {            // the energy pairs of the scan, logged around its explorer kernel(s) (k_log_energy)
-        hipLaunchKernelGGL(k_log_energy, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, h->dev, 0);
-        int rc;
-        if (h->cfg.explorer2 == PTE_EXPLORER_NONE) { h->dev.compose_phase = 0; rc = launch_explorer_kind(h, scan, h->cfg.explorer); }
-        else {
-            h->dev.compose_phase = 1; rc = launch_explorer_kind(h, scan, h->cfg.explorer);
-            if (!rc) { h->dev.compose_phase = 2; rc = launch_explorer_kind(h, scan, h->cfg.explorer2); }
-            h->dev.compose_phase = 0;
-        }
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_log_energy, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, h->dev, 1);
-        HIP_OK(h, hipGetLastError());
-        return 0;
-    }
-    if (h->cfg.explorer2 == PTE_EXPLORER_NONE) { h->dev.compose_phase = 0; return launch_explorer_kind(h, scan, h->cfg.explorer); }
-    // Compose(first, second), src/explorers/Compose.jl:16-19: two kernels back to back on the replica's stream
-    h->dev.compose_phase = 1;
-    int rc = launch_explorer_kind(h, scan, h->cfg.explorer);
-    h->dev.compose_phase = 2;
-    if (!rc) rc = launch_explorer_kind(h, scan, h->cfg.explorer2);
-    h->dev.compose_phase = 0;
-    return rc;
+    if (!h->dev.eac_log || h->cfg.explorer == PTE_EXPLORER_NONE) return launch_explorers(h, scan);
+    // the energy pairs of the scan, logged around its explorer kernel(s) (k_log_energy)
+    hipLaunchKernelGGL(k_log_energy, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, h->dev, 0);
+    if (int rc = launch_explorers(h, scan)) return rc;
+    hipLaunchKernelGGL(k_log_energy, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, h->dev, 1);
+    HIP_OK(h, hipGetLastError());
+    return 0;
 }
 
 int launch_explorer_kind(pte_engine *h, int64_t scan, int kind) {
@@ -426,36 +485,10 @@ int launch_explorer_kind(pte_engine *h, int64_t scan, int kind) {
         time_end(h);
         break;
     case PTE_EXPLORER_SLICE:
-        if (h->cfg.target == PTE_TARGET_GAUSSIAN_MIXTURE) {       // SliceSampler on the mixture's interpolated path: k_explore_mixture's slice mode
-            AmParams ap{};
-            ap.slice = 1; ap.slice_w = h->cfg.slice_w; ap.slice_p = h->cfg.slice_p; ap.slice_n_passes = h->cfg.slice_n_passes;
-            ap.slice_max_iter = h->cfg.slice_max_iter;
-            ap.ref_prec = h->cfg.target_params[0]; ap.log3 = std::log(3.0);
+        if (on_interpolated_path(h->cfg.target)) {
+            const AmParams ap = slice_path_params(h);
             time_begin(h, 0, true);
-            if (launch_mixture(h, h->d <= 64 ? 1 : h->d <= 128 ? 2 : h->d <= 256 ? 4 : 8, true, false, N, ap)) return 1;
-            time_end(h);
-            break;
-        }
-        if (h->cfg.target == PTE_TARGET_BAYESIAN_GLM) {           // SliceSampler on the GLM's interpolated path: k_explore_glm's slice mode
-            AmParams ap{};
-            ap.slice = 1; ap.slice_w = h->cfg.slice_w; ap.slice_p = h->cfg.slice_p; ap.slice_n_passes = h->cfg.slice_n_passes;
-            ap.slice_max_iter = h->cfg.slice_max_iter;
-            ap.ref_prec = h->cfg.target_params[0]; ap.log3 = std::log(3.0);
-            time_begin(h, 0, true);
-            if (launch_glm(h, h->d <= 64 ? 1 : h->d <= 128 ? 2 : h->d <= 256 ? 4 : 8, true, false, N, ap)) return 1;
-            time_end(h);
-            break;
-        }
-        if (h->cfg.target == PTE_TARGET_FUNNEL) {
-            // SliceSampler on the interpolated path: the register-resident kernel of the Langevin family in its slice mode
-            // (full log potential per evaluation, as the reference's slice_sample! does for any log_potential)
-            AmParams ap{};
-            ap.slice = 1; ap.slice_w = h->cfg.slice_w; ap.slice_p = h->cfg.slice_p; ap.slice_n_passes = h->cfg.slice_n_passes;
-            ap.slice_max_iter = h->cfg.slice_max_iter;
-            ap.ref_prec = h->cfg.target_params[0]; ap.log3 = std::log(3.0);
-            const int E = h->d <= 64 ? 1 : h->d <= 128 ? 2 : h->d <= 256 ? 4 : h->d <= 512 ? 8 : 16;
-            time_begin(h, 0, true);
-            if (launch_langevin(h, E, TGT_FUNNEL, true, false, N, ap)) return 1;
+            if (launch_path_kernel(h, blocks_per_lane(h->d), true, false, N, ap)) return 1;
             time_end(h);
             break;
         }
@@ -488,33 +521,20 @@ int launch_explorer_kind(pte_engine *h, int64_t scan, int kind) {
     }
     case PTE_EXPLORER_MALA:
     case PTE_EXPLORER_AUTOMALA: {
-        AmParams ap{};
-        ap.mala = (kind == PTE_EXPLORER_MALA) ? 1 : 0;
-        ap.step_size = ap.mala ? h->cfg.am_step_size : h->step_size; ap.n_refresh = h->am_n_refresh; ap.precond = h->cfg.am_preconditioner;
-        ap.p0 = h->cfg.am_p0; ap.p1 = h->cfg.am_p1;
-        ap.target_std = h->have_target_std ? h->d_target_std : nullptr;
-        ap.use_mh = (scan != 1) ? 1 : 0;                 // AutoMALA.jl:87,96-102
-        ap.ref_prec = h->cfg.target_params[0]; ap.log3 = std::log(3.0);
-        ap.pace = h->d > 512 ? langevin_mw_paced(h) : 0;
-        const int E = h->d <= 64 ? 1 : h->d <= 128 ? 2 : h->d <= 256 ? 4 : h->d <= 512 ? 8 : 16;
-        const bool fun = h->cfg.target == PTE_TARGET_FUNNEL;
+        const AmParams ap = langevin_params(h, kind, (scan != 1) ? 1 : 0);
+        const int E = blocks_per_lane(h->d);
         time_begin(h, 0, true);
         const bool full = h->d == 64 * (int64_t)E;       // no ragged last block: the instantiation without per-lane validity masks
-        if (h->cfg.target == PTE_TARGET_GAUSSIAN_MIXTURE) { if (launch_mixture(h, E, false, full, N, ap)) return 1; }
-        else if (h->cfg.target == PTE_TARGET_BAYESIAN_GLM) { if (launch_glm(h, E, false, full, N, ap)) return 1; }
-        else if (launch_langevin(h, E, fun ? TGT_FUNNEL : TGT_MVN, false, full, N, ap)) return 1;
+        if (launch_path_kernel(h, E, false, full, N, ap)) return 1;
         time_end(h);
         break;
     }
-    case PTE_EXPLORER_AAPS: {                            // one AAPS transition per replica (pte_aaps.hpp); the step size is not adapted
-        AapsParams ap{};
-        ap.step_size = h->cfg.am_step_size; ap.K = h->cfg.aaps_K; ap.precond = h->cfg.am_preconditioner;
-        ap.p0 = h->cfg.am_p0; ap.p1 = h->cfg.am_p1;
-        ap.target_std = h->have_target_std ? h->d_target_std : nullptr;
-        ap.ref_prec = h->cfg.target_params[0]; ap.log3 = std::log(3.0);
-        const int E = h->d <= 64 ? 1 : h->d <= 128 ? 2 : h->d <= 256 ? 4 : 8;
+    case PTE_EXPLORER_AAPS: {                            // one AAPS transition per replica (pte_aaps.hpp)
+        const AapsParams ap = aaps_params(h);
+        const int E = blocks_per_lane(h->d);
         time_begin(h, 0, true);
-        if (launch_aaps(h, E, h->cfg.target == PTE_TARGET_FUNNEL ? TGT_FUNNEL : TGT_MVN, h->d == 64 * (int64_t)E, N, ap)) return 1;
+        AapsLaunch L{E, h->cfg.target == PTE_TARGET_FUNNEL ? TGT_FUNNEL : TGT_MVN, h->d == 64 * (int64_t)E, launch_site(h, (unsigned)N)};
+        if (aaps_launch(L, h->dev, ap)) return fail(h, "this build holds no AAPS kernel for dim %lld", (long long)h->d);
         time_end(h);
         break;
     }
@@ -627,7 +647,6 @@ int fused_kind(const pte_engine *h) {
     }
     return 0;
 }
-int langevin_E(const pte_engine *h) { return h->d <= 64 ? 1 : h->d <= 128 ? 2 : h->d <= 256 ? 4 : h->d <= 512 ? 8 : 16; }
 
 bool fused_scans_eligible(pte_engine *h, int64_t n_scans) {
     if (!h->fused_allowed || h->world != 1 || n_scans < 1) return false;
@@ -643,7 +662,7 @@ bool fused_scans_eligible(pte_engine *h, int64_t n_scans) {
             if (fused_slice_variant(h) == 0) { OCC_NLU_M(h->nlu, k_scans_slice8, PTE_S8_BS, per_cu); }
             else { OCC_NLU_M(h->nlu, k_scans_slice8_generic, PTE_S8_BS, per_cu); }
         } else {
-            per_cu = langevin_scan_loop_blocks_per_cu(langevin_E(h), h->cfg.target == PTE_TARGET_FUNNEL ? TGT_FUNNEL : TGT_MVN, h->d == 64 * (int64_t)langevin_E(h));
+            per_cu = langevin_scan_loop_blocks_per_cu(blocks_per_lane(h->d), h->cfg.target == PTE_TARGET_FUNNEL ? TGT_FUNNEL : TGT_MVN, h->d == 64 * (int64_t)blocks_per_lane(h->d));
         }
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->cfg.device) != hipSuccess) cus = 0;
         (void)hipGetLastError();
@@ -654,7 +673,7 @@ bool fused_scans_eligible(pte_engine *h, int64_t n_scans) {
         h->fused_wg = 1;
         if (kind == 2 && h->fused_wg_allowed) {
             const int wgn = langevin_scan_wg();
-            const int per_cu_wg = wgn > 1 && wgn <= 4 ? langevin_scan_loop_blocks_per_cu(langevin_E(h), h->cfg.target == PTE_TARGET_FUNNEL ? TGT_FUNNEL : TGT_MVN, h->d == 64 * (int64_t)langevin_E(h), wgn) : 0;
+            const int per_cu_wg = wgn > 1 && wgn <= 4 ? langevin_scan_loop_blocks_per_cu(blocks_per_lane(h->d), h->cfg.target == PTE_TARGET_FUNNEL ? TGT_FUNNEL : TGT_MVN, h->d == 64 * (int64_t)blocks_per_lane(h->d), wgn) : 0;
             (void)hipGetLastError();
             if (per_cu_wg >= 1 && h->K <= (int64_t)wgn * cus) { h->fused_wg = wgn; h->fused_limit = std::max(h->fused_limit, (int64_t)wgn * cus); }
         }
@@ -699,18 +718,10 @@ int run_scans_fused(pte_engine *h, int64_t first_scan, int64_t n_scans) {
         if (fused_slice_variant(h) == 0) { DISPATCH_NLU_M(h->nlu, k_scans_slice8, PTE_S8_BS, dim3((unsigned)N), dim3(64), h->stream, h->dev, sp, sl); }
         else { DISPATCH_NLU_M(h->nlu, k_scans_slice8_generic, PTE_S8_BS, dim3((unsigned)N), dim3(64), h->stream, h->dev, sp, sl); }
     } else {
-        // the parameters launch_explorer_kind gives the per-scan kernel; use_mh (scan != 1, AutoMALA.jl:87,96-102) is decided per scan inside
-        AmParams ap{};
-        ap.mala = (h->cfg.explorer == PTE_EXPLORER_MALA) ? 1 : 0;
-        ap.step_size = ap.mala ? h->cfg.am_step_size : h->step_size; ap.n_refresh = h->am_n_refresh; ap.precond = h->cfg.am_preconditioner;
-        ap.p0 = h->cfg.am_p0; ap.p1 = h->cfg.am_p1;
-        ap.target_std = h->have_target_std ? h->d_target_std : nullptr;
-        ap.use_mh = 1;
-        ap.ref_prec = h->cfg.target_params[0]; ap.log3 = std::log(3.0);
-        ap.pace = h->d > 512 ? langevin_mw_paced(h) : 0;
-        const int E = langevin_E(h);
-        LangevinLaunch L{E, h->cfg.target == PTE_TARGET_FUNNEL ? TGT_FUNNEL : TGT_MVN, false, h->d == 64 * (int64_t)E, (unsigned)N, h->stream, false, nullptr, nullptr, &sl, h->fused_wg};
-        if (h->ev_open && h->ev_ext && !h->ev_ext_done) { L.ext = true; L.ev_a = h->events.back().a; L.ev_b = h->events.back().b; h->ev_ext_done = true; }
+        const AmParams ap = langevin_params(h, h->cfg.explorer, 1);
+        const int E = blocks_per_lane(h->d);
+        LangevinLaunch L{E, h->cfg.target == PTE_TARGET_FUNNEL ? TGT_FUNNEL : TGT_MVN, false, h->d == 64 * (int64_t)E, launch_site(h, (unsigned)wgs)};
+        L.scans = &sl; L.scan_wg = h->fused_wg;
         if (E == 16) HIP_OK(h, hipMemsetAsync(h->dev.pace, 0, sizeof(unsigned int), h->stream));      // k_scans_langevin_mw: its workgroups count their refreshes here
         if (langevin_launch(L, h->dev, ap)) { time_end(h); return fail(h, "this build holds no fused Langevin-family kernel"); }
     }
@@ -749,173 +760,13 @@ int run_scans_fused(pte_engine *h, int64_t first_scan, int64_t n_scans) {
     return rc;
 }
 
-int poisoned_error(pte_engine *h, const char *what) {
-    return fail(h, "%s: this engine is poisoned -- an earlier pte_run_scans failed inside the one-launch scan loop, its replicas stopped at different scans; "
-                   "restore it with pte_set_state(state, chain, rng) or destroy it", what);
-}
-#define PTE_ALIVE(h, what) do { if ((h)->poisoned) return poisoned_error(h, what); } while (0)
-
-}  // namespace
-
-extern "C" {
-
-int pte_default_config(pte_config *c) {
-    if (!c) return 1;
-    std::memset(c, 0, sizeof *c);
-    c->struct_size = sizeof(pte_config);
-    c->abi_version = PTE_ABI_VERSION;
-    c->device = 0;
-    c->target = PTE_TARGET_MVN_SCALED_PRECISION;
-    c->explorer = PTE_EXPLORER_TOY;
-    c->record_flags = PTE_RECORD_ROUND_TRIP | PTE_RECORD_INDEX_PROCESS;
-    c->n_chains = 10; c->dim = 2; c->seed = 1;
-    c->max_scans_per_round = 1024;
-    c->target_params[0] = 1.0; c->target_params[1] = 10.0;
-    c->slice_w = 10.0; c->slice_p = 20; c->slice_n_passes = 3; c->slice_max_iter = 1024;
-    c->am_base_n_refresh = 3; c->am_exponent_n_refresh = 0.35; c->am_step_size = 1.0;
-    c->am_p0 = 1.0 / 3.0; c->am_p1 = 1.0 / 3.0; c->am_preconditioner = 2;
-    c->aaps_K = 5;                                   // AAPS.jl
-    c->rank = 0; c->world_size = 1;
-    return 0;
-}
-
-const char *pte_last_error(const pte_engine *h) { return h ? h->err.c_str() : g_create_error.c_str(); }
-
-int pte_create(const pte_config *cfg, pte_engine **out) {
-    if (!cfg || !out) return fail(nullptr, "pte_create: null argument");
-    *out = nullptr;
-    if (cfg->struct_size != sizeof(pte_config) || cfg->abi_version != PTE_ABI_VERSION)
-        return fail(nullptr, "pte_create: ABI mismatch (struct_size %u vs %zu, version %u vs %d)",
-                    cfg->struct_size, sizeof(pte_config), cfg->abi_version, PTE_ABI_VERSION);
-    if (cfg->n_chains < 1) return fail(nullptr, "pte_create: n_chains must be >= 1");
-    if (cfg->world_size < 1 || cfg->rank < 0 || cfg->rank >= cfg->world_size) return fail(nullptr, "pte_create: bad rank / world_size");
-    if (cfg->n_chains_variational < 0) return fail(nullptr, "pte_create: n_chains_variational must be >= 0");
-    if (cfg->n_chains_variational > 0 && cfg->world_size != 1) return fail(nullptr, "pte_create: two-leg tempering (n_chains_variational > 0) runs on a single engine");
-    if (cfg->n_chains % cfg->world_size != 0) return fail(nullptr, "pte_create: n_chains (%lld) must be a multiple of world_size (%d)", (long long)cfg->n_chains, cfg->world_size);
-    const bool swapper = cfg->target == PTE_TARGET_TEST_SWAPPER;
-    const bool funnel = cfg->target == PTE_TARGET_FUNNEL;
-    const bool ising = cfg->target == PTE_TARGET_ISING;
-    const bool mixture = cfg->target == PTE_TARGET_GAUSSIAN_MIXTURE;
-    const bool glm = cfg->target == PTE_TARGET_BAYESIAN_GLM;
-    if (cfg->explorer == PTE_EXPLORER_AAPS || cfg->explorer2 == PTE_EXPLORER_AAPS) {       // AAPS (pte_aaps.hpp): one wave per replica, one explorer
-        if (cfg->explorer2 != PTE_EXPLORER_NONE)
-            return fail(nullptr, "pte_create: AAPS is not available as half of a Compose on the device");
-        if (!funnel && cfg->target != PTE_TARGET_MVN_SCALED_PRECISION)
-            return fail(nullptr, "pte_create: AAPS is implemented on the scaled-precision MVN and funnel paths only (got target %d)", cfg->target);
-        if (cfg->dim < 1 || cfg->dim > 512)
-            return fail(nullptr, "pte_create: AAPS keeps the replica in the registers of one wave, dim must be in 1..512 (got %lld)", (long long)cfg->dim);
-        if (cfg->aaps_K < 0 || cfg->aaps_K > 64)
-            return fail(nullptr, "pte_create: AAPS needs aaps_K in 0..64 (got %d)", cfg->aaps_K);
-        if (!(cfg->am_step_size > 0) || !std::isfinite(cfg->am_step_size))
-            return fail(nullptr, "pte_create: AAPS needs a positive finite step size (got %g)", cfg->am_step_size);
-        if (cfg->debug_kernel != 0)
-            return fail(nullptr, "pte_create: AAPS has one kernel; debug_kernel must be 0 (got %d)", cfg->debug_kernel);
-    }
-    if (mixture) {          // Gaussian mixture (pte_mixture.hpp): one wave per replica, SliceSampler / AutoMALA / MALA
-        auto on_mix = [](int k) { return k == PTE_EXPLORER_SLICE || k == PTE_EXPLORER_AUTOMALA || k == PTE_EXPLORER_MALA; };
-        if (!on_mix(cfg->explorer) || (cfg->explorer2 != PTE_EXPLORER_NONE && !on_mix(cfg->explorer2)))
-            return fail(nullptr, "pte_create: the Gaussian-mixture path is implemented for SliceSampler / AutoMALA / MALA (and Compose of them) only (got explorers %d, %d)",
-                        cfg->explorer, cfg->explorer2);
-        if (cfg->dim < 1 || cfg->dim > 512)
-            return fail(nullptr, "pte_create: the Gaussian-mixture path keeps the replica in the registers of one wave, dim must be in 1..512 (got %lld)", (long long)cfg->dim);
-        if ((cfg->debug_kernel & ~(PTE_KERNEL_FLAG_BITS | PTE_KERNEL_TEST_BITS)) != 0)
-            return fail(nullptr, "pte_create: debug_kernel %d is not available on the Gaussian-mixture path (one register-resident kernel serves it)", cfg->debug_kernel);
-        if (cfg->n_chains_variational > 0)
-            return fail(nullptr, "pte_create: two-leg tempering (n_chains_variational > 0) is not available on the Gaussian-mixture path");
-    }
-    if (glm) {              // Bayesian GLM (pte_glm.hpp): one wave per replica, SliceSampler / AutoMALA / MALA (AAPS: refused above)
-        auto on_glm = [](int k) { return k == PTE_EXPLORER_SLICE || k == PTE_EXPLORER_AUTOMALA || k == PTE_EXPLORER_MALA; };
-        if (!on_glm(cfg->explorer) || (cfg->explorer2 != PTE_EXPLORER_NONE && !on_glm(cfg->explorer2)))
-            return fail(nullptr, "pte_create: the Bayesian-GLM path is implemented for SliceSampler / AutoMALA / MALA (and Compose of them) only (got explorers %d, %d)",
-                        cfg->explorer, cfg->explorer2);
-        if (cfg->dim < 1 || cfg->dim > 512)
-            return fail(nullptr, "pte_create: the Bayesian-GLM path keeps the replica in the registers of one wave, dim must be in 1..512 (got %lld)", (long long)cfg->dim);
-        if ((cfg->debug_kernel & ~(PTE_KERNEL_FLAG_BITS | PTE_KERNEL_TEST_BITS)) != 0)
-            return fail(nullptr, "pte_create: debug_kernel %d is not available on the Bayesian-GLM path (one kernel serves it)", cfg->debug_kernel);
-        if (cfg->n_chains_variational > 0)
-            return fail(nullptr, "pte_create: two-leg tempering (n_chains_variational > 0) is not available on the Bayesian-GLM path");
-    }
-    if (ising) {
-        const int64_t L = (int64_t)std::llround(std::sqrt((double)cfg->dim));
-        if (L < 2 || L * L != cfg->dim || cfg->dim > 65536) return fail(nullptr, "pte_create: Ising needs dim = base_length^2 <= 65536");
-        if (cfg->explorer == PTE_EXPLORER_SLICE || cfg->explorer2 == PTE_EXPLORER_SLICE)   // spins are Bool coordinates: SliceSampler.jl:65-86 (and :136-142, :189 for Integer ones)
-            return fail(nullptr, "pte_create: SliceSampler's Bool / Integer coordinate methods are not available on the device (its Float64 methods are); "
-                                 "the Ising path is explored by IsingMetropolis only -- use the reference CPU path for Bool / Integer states");
-        if (cfg->explorer != PTE_EXPLORER_ISING_METROPOLIS) return fail(nullptr, "pte_create: the Ising path is explored by IsingMetropolis only");
-    } else if (cfg->explorer == PTE_EXPLORER_ISING_METROPOLIS) return fail(nullptr, "pte_create: IsingMetropolis needs the Ising target");
-    if (!swapper && !funnel && !ising && !mixture && !glm && cfg->target != PTE_TARGET_MVN_SCALED_PRECISION)
-        return fail(nullptr, "pte_create: target %d has no device log-potential; use the reference CPU path", cfg->target);
+// device memory of a new engine (zeroed on its stream unless noted) and the EngineDev the kernels are given
+int alloc_engine(pte_engine *h) {
+    const pte_config *cfg = &h->cfg;
+    const int64_t N = h->N, K = h->K, d = h->d;
+    const bool funnel = cfg->target == PTE_TARGET_FUNNEL, ising = cfg->target == PTE_TARGET_ISING, aaps = cfg->explorer == PTE_EXPLORER_AAPS;
     auto grad_based = [](int k) { return k == PTE_EXPLORER_AUTOMALA || k == PTE_EXPLORER_MALA; };
     const bool uses_grad = grad_based(cfg->explorer) || grad_based(cfg->explorer2);
-    const bool aaps = cfg->explorer == PTE_EXPLORER_AAPS;
-    auto on_path = [&](int k) { return grad_based(k) || k == PTE_EXPLORER_SLICE; };
-    if (funnel && !aaps && !(on_path(cfg->explorer) && (cfg->explorer2 == PTE_EXPLORER_NONE || on_path(cfg->explorer2))))
-        return fail(nullptr, "pte_create: the funnel path is implemented for AutoMALA / MALA / SliceSampler (and Compose of them); use the reference CPU path");
-    if ((uses_grad || funnel) && (cfg->dim < 1 || cfg->dim > 1024))
-        return fail(nullptr, "pte_create: AutoMALA / MALA (and every explorer of the funnel path) keep the replica in registers, dim must be in 1..1024 (got %lld)", (long long)cfg->dim);
-    if (funnel && (cfg->debug_kernel & ~(PTE_KERNEL_FLAG_BITS | PTE_KERNEL_TEST_BITS)) != 0)
-        return fail(nullptr, "pte_create: debug_kernel %d is not available on the funnel path (one register-resident kernel serves it)", cfg->debug_kernel);
-    if (cfg->explorer2 != PTE_EXPLORER_NONE) {           // Compose(first, second)
-        auto composable = [&](int k) { return k == PTE_EXPLORER_SLICE || grad_based(k); };
-        if (!composable(cfg->explorer) || !composable(cfg->explorer2))
-            return fail(nullptr, "pte_create: Compose is available for SliceSampler / AutoMALA / MALA (got %d, %d)", cfg->explorer, cfg->explorer2);
-    }
-    if (!swapper && !ising && (cfg->dim < 1 || cfg->dim > 4096))
-        return fail(nullptr, "pte_create: dim must be in 1..4096 (got %lld)", (long long)cfg->dim);
-    if (swapper && cfg->explorer != PTE_EXPLORER_NONE)
-        return fail(nullptr, "pte_create: TestSwapper has no explorer");
-    if (!swapper && !ising && cfg->explorer != PTE_EXPLORER_TOY && cfg->explorer != PTE_EXPLORER_SLICE && !grad_based(cfg->explorer) && !aaps)
-        return fail(nullptr, "pte_create: explorer %d is not implemented on the device", cfg->explorer);
-    if ((cfg->record_flags & PTE_RECORD_TRACES_EXTENDED) && !(cfg->record_flags & PTE_RECORD_TRACES))
-        return fail(nullptr, "pte_create: PTE_RECORD_TRACES_EXTENDED needs PTE_RECORD_TRACES");
-    if (cfg->record_flags & PTE_RECORD_REFERENCE_REDUCTION) {
-        if (!(cfg->record_flags & PTE_RECORD_INDEX_PROCESS))
-            return fail(nullptr, "pte_create: PTE_RECORD_REFERENCE_REDUCTION needs PTE_RECORD_INDEX_PROCESS (the replay asks which replica held the lower chain of a pair)");
-        if ((double)cfg->max_scans_per_round * (double)(cfg->n_chains + cfg->n_chains_variational) * 16.0 > 64e9)
-            return fail(nullptr, "pte_create: the swap log (max_scans_per_round x chains x 2 doubles) would exceed 64 GB");
-    }
-#ifndef PTE_TEST_KERNELS
-    if (cfg->debug_kernel & PTE_KERNEL_TEST_BITS)
-        return fail(nullptr, "pte_create: debug_kernel 0x%x carries a fault-injection flag (PTE_KERNEL_TEST_*); those exist in the test build libpte_test.so only", cfg->debug_kernel);
-#endif
-    {   // debug_kernel: 0 = the default kernel of the explorer; anything else must exist in THIS build (no silent fall-through)
-        const int dk = cfg->debug_kernel & ~(PTE_KERNEL_FLAG_BITS | PTE_KERNEL_TEST_BITS);      // (the flag bit chooses the scan loop's form, not the kernel generation)
-        const bool slice = cfg->explorer == PTE_EXPLORER_SLICE || cfg->explorer2 == PTE_EXPLORER_SLICE;
-        bool ok = dk == 0 || (slice && dk == PTE_KERNEL_SLICE_SEQUENTIAL) || (ising && dk == PTE_KERNEL_ISING_BYTES);
-#ifdef PTE_TEST_KERNELS
-        ok = ok || (slice && (dk == 2 || dk == 5 || dk == 7 || dk == 8)) || (ising && dk == PTE_KERNEL_ISING_BITS);
-#endif
-        if (!ok) return fail(nullptr, "pte_create: debug_kernel %d is not available for this explorer in this build of libpte "
-                                      "(0 = default, %d = sequential SliceSampler kernel; the other generations live in the test build libpte_test.so)",
-                             dk, PTE_KERNEL_SLICE_SEQUENTIAL);
-    }
-    if ((cfg->record_flags & PTE_RECORD_TRACES) &&
-        (double)cfg->max_scans_per_round * (double)((cfg->record_flags & PTE_RECORD_TRACES_EXTENDED) ? cfg->n_chains / cfg->world_size : 1) * (double)(cfg->dim + 1) * 8.0 > 64e9)
-        return fail(nullptr, "pte_create: the traces buffer (max_scans_per_round x chains x (dim+1) doubles) would exceed 64 GB");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, "pte_create: no HIP device available (this library has no CPU fallback)");
-    if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, "pte_create: bad device ordinal %d", cfg->device);
-
-    pte_engine *h = new pte_engine();
-    h->cfg = *cfg;
-    const int64_t N = h->N = cfg->n_chains + cfg->n_chains_variational;      // Inputs.jl:128
-    const int64_t d = h->d = swapper ? 0 : cfg->dim;
-    h->world = cfg->world_size; h->rank = cfg->rank;
-    const int64_t K = h->K = N / cfg->world_size;
-    h->c0 = K * cfg->rank;
-    auto bail = [&](int) { g_create_error = h->err; pte_destroy(h); return 1; };
-    if (hipSetDevice(cfg->device) != hipSuccess) { h->err = "hipSetDevice failed"; return bail(1); }
-    if (hipStreamCreate(&h->stream) != hipSuccess) { h->err = "hipStreamCreate failed"; return bail(1); }
-    const int64_t B = (d + 63) / 64;
-    h->nlu = next_pow2_log(B > 0 ? B : 1);
-    // pte_config.debug_kernel (validated above): which kernel generation explores; never read from the environment
-    const int dk_kernel = cfg->debug_kernel & ~(PTE_KERNEL_FLAG_BITS | PTE_KERNEL_TEST_BITS);
-    h->fused_allowed = (cfg->debug_kernel & PTE_KERNEL_TWO_LAUNCHES) == 0;
-    h->fused_wg_allowed = (cfg->debug_kernel & PTE_KERNEL_SCAN_LOOP_ONE_CHAIN) == 0;
-    h->test_fault = (cfg->debug_kernel & PTE_KERNEL_TEST_DEAD_CHAIN) ? 1 : ((cfg->debug_kernel & PTE_KERNEL_TEST_LATE_WORKGROUP) ? 2 : 0);
-    if (cfg->explorer == PTE_EXPLORER_SLICE || cfg->explorer2 == PTE_EXPLORER_SLICE) h->slice_impl = dk_kernel == 0 ? 8 : dk_kernel;
-    if (cfg->explorer == PTE_EXPLORER_ISING_METROPOLIS) h->ising_impl = dk_kernel == PTE_KERNEL_ISING_BITS ? 1 : (dk_kernel == PTE_KERNEL_ISING_BYTES ? 2 : 0);
     EngineDev &e = h->dev;
     e.N = N; e.K = K; e.c0 = h->c0; e.d = d; e.ld = (d + 1) & ~(int64_t)1;
     e.sw = d;
@@ -923,9 +774,8 @@ int pte_create(const pte_config *cfg, pte_engine **out) {
         const int64_t lw = (d + 31) / 32;
         e.ld = (lw + 1) / 2; e.sw = e.ld;
     }
-    // (the swap and recorder kernels see the mixture as the funnel's interpolated path: suff = sum x^2 for the reference, suff2 = the target's log density)
-    // (and the Bayesian GLM too: suff2 = its target log density, prior included)
-    e.record_flags = cfg->record_flags; e.target = (mixture || glm) ? PTE_TARGET_FUNNEL : cfg->target; e.test_swapper_pr = cfg->target_params[0];
+    // (the swap and recorder kernels see every family on an interpolated path as the funnel's: suff = sum x^2 for the reference, suff2 = the target's log density)
+    e.record_flags = cfg->record_flags; e.target = on_interpolated_path(cfg->target) ? PTE_TARGET_FUNNEL : cfg->target; e.test_swapper_pr = cfg->target_params[0];
     const int64_t dd = d > 0 ? d : 1;
     int rc = 0;
     rc |= dev_alloc(h, &e.x, (size_t)(K * (e.ld > 0 ? e.ld : 1)));
@@ -977,21 +827,25 @@ int pte_create(const pte_config *cfg, pte_engine **out) {
     e.am_log = nullptr; e.am_log_cap = 0;
     if ((cfg->record_flags & PTE_RECORD_REFERENCE_REDUCTION) && (cfg->explorer == PTE_EXPLORER_AUTOMALA || cfg->explorer2 == PTE_EXPLORER_AUTOMALA)) {
         // AutoMALA searches a step size twice per refresh at most (forward, and backward for the reversibility check): am_factors' fits
-        const int nref = cfg->am_base_n_refresh * (int)std::ceil(std::pow((double)(d > 0 ? d : 1), cfg->am_exponent_n_refresh));
-        e.am_log_cap = 2 * nref;
+        e.am_log_cap = 2 * am_n_refresh(cfg, d);
         rc |= dev_alloc(h, &e.am_log, (size_t)(cfg->max_scans_per_round * K * e.am_log_cap), false);
     }
-    if (rc) return bail(1);
+    if (rc) return 1;
     e.nhp = h->d_nhp; e.sd = h->d_sd; e.nprec = h->d_nprec; e.beta = h->d_beta;
     e.ref_nhp = -0.5 * cfg->target_params[0];
     e.ising_beta = cfg->target_params[0];
     h->step_size = cfg->am_step_size;
-    // n_refresh = base_n_refresh * ceil(Int, dim^exponent_n_refresh)  (AutoMALA.jl:120)
-    h->am_n_refresh = cfg->am_base_n_refresh * (int)std::ceil(std::pow((double)(d > 0 ? d : 1), cfg->am_exponent_n_refresh));
+    h->am_n_refresh = am_n_refresh(cfg, d);
     if ((uses_grad || aaps) && cfg->am_preconditioner != 0) e.record_flags |= PTE_RECORD_ONLINE;   // _transformed_online (GradientBasedSampler.jl:19-25)
     e.slot_of_chain = h->slot_map[0]; e.slot_of_chain_alt = h->slot_map[1]; h->slot_cur = 0;
+    return 0;
+}
 
-    // equally_spaced_schedule (reference src/schedules/Schedule.jl:36-44)
+// equally_spaced_schedule (reference src/schedules/Schedule.jl:36-44)
+void default_schedule(pte_engine *h) {
+    const pte_config *cfg = &h->cfg;
+    EngineDev &e = h->dev;
+    const int64_t N = h->N;
     h->betas.resize(N);
     auto equally_spaced = [](int64_t n, int64_t i) { return n == 1 ? 1.0 : ((i == n - 1) ? 1.0 : (double)i / (double)(n - 1)); };
     if (cfg->n_chains_variational > 0) {       // StabilizedPT(inputs): both legs equally spaced, the fixed leg reversed
@@ -1003,8 +857,15 @@ int pte_create(const pte_config *cfg, pte_engine **out) {
         for (int64_t i = 0; i < N; ++i) h->betas[i] = equally_spaced(N, i);
         e.ref2 = -1; e.tgt_a = e.tgt_b = e.rt_tgt_a = e.rt_tgt_b = N - 1;
     }
-    if (upload_ladder(h)) return bail(1);
-    if (reset_recorders(h)) return bail(1);
+}
+
+// create_replicas: k_init draws every replica's state from the reference and seeds its streams (timed once: pte_timing_get(kernel = 2));
+// the Ising path has no k_init, its slots are numbered here
+int init_replicas(pte_engine *h) {
+    const pte_config *cfg = &h->cfg;
+    EngineDev &e = h->dev;
+    const int64_t K = h->K;
+    const bool swapper = cfg->target == PTE_TARGET_TEST_SWAPPER, ising = cfg->target == PTE_TARGET_ISING;
     const double init_sd = swapper ? 1.0 : std::sqrt(cfg->target_params[1]);   // toy_mvn_target.jl:10-11
     hipEvent_t init_a = nullptr, init_b = nullptr;       // k_init's duration: pte_timing_get(kernel = 2), one event pair per engine
     if (!ising) {
@@ -1025,46 +886,225 @@ int pte_create(const pte_config *cfg, pte_engine **out) {
         hipStreamSynchronize(h->stream);
     }
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) {
-        h->err = "k_init launch failed"; return bail(1);
+        h->err = "k_init launch failed"; return 1;
     }
     if (init_a) {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, init_a, init_b) == hipSuccess) h->init_ms = ms;
         hipEventDestroy(init_a); hipEventDestroy(init_b);
     }
-    if (funnel || ising || mixture || glm) {
-        // funnel, Gaussian mixture, Bayesian GLM: initialization(::LogDensity, rng, i) = zeros(dim); Ising: falses(L, L) (examples/ising.jl:85) (test/supporting/dimensional-analysis.jl:24): the streams
-        // stay untouched; suff2 = funnel(0) = d terms evaluated on the host exactly like the kernels' tree of equal terms
-        std::vector<uint64_t> rngs((size_t)(2 * K));
-        const uint64_t G = 0x9e3779b97f4a7c15ULL;
-        auto mix64h = [](uint64_t z) { z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL; z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL; return z ^ (z >> 31); };
-        auto mixg = [](uint64_t z) { z = (z ^ (z >> 33)) * 0xff51afd7ed558ccdULL; z = (z ^ (z >> 33)) * 0xc4ceb9fe1a85ec53ULL; z = (z ^ (z >> 33)) | 1ULL;
-                                     return (__builtin_popcountll(z ^ (z >> 1)) < 24) ? (z ^ 0xaaaaaaaaaaaaaaaaULL) : z; };
-        for (int64_t il = 0; il < K; ++il) {
-            const uint64_t i = (uint64_t)(h->c0 + il);
-            rngs[2 * il] = mix64h(cfg->seed + (2 * i + 1) * G); rngs[2 * il + 1] = mixg(cfg->seed + (2 * i + 2) * G);
-        }
-        hipMemcpyAsync(e.rng, rngs.data(), sizeof(uint64_t) * 2 * K, hipMemcpyHostToDevice, h->stream);
-        hipMemsetAsync(e.x, 0, sizeof(double) * K * e.ld, h->stream);
-        hipMemsetAsync(e.suff, 0, sizeof(double) * K, h->stream);
-        // funnel(0): terms[0] = -(log2pi)/2 - log 3 ; terms[i] = -(log2pi)/2 - log(exp(0)) ; summed with the fixed tree
-        std::vector<double> terms((size_t)d);
-        const double LOG2PI = 1.8378770664093453;
-        const double sigma = std::exp(0.0 / 2.0), ls = std::log(sigma);
-        for (int64_t i = 0; i < d; ++i) terms[i] = -(0.0 * 0.0 + LOG2PI) / 2.0 - (i == 0 ? std::log(3.0) : ls);
-        int64_t P = 1; while (P < d) P <<= 1;
-        std::vector<double> a((size_t)P, 0.0);
-        for (int64_t i = 0; i < d; ++i) a[i] = terms[i];
-        for (int64_t len = P; len > 1; len /= 2) for (int64_t i = 0; i < len / 2; ++i) a[i] = a[2 * i] + a[2 * i + 1];
-        std::vector<double> s2((size_t)K, a[0]);
-        hipMemcpyAsync(e.suff2, s2.data(), sizeof(double) * K, hipMemcpyHostToDevice, h->stream);
-        if (ising) {   // all spins -1: every site contributes (-1)(-4) = 4, halved: sum_pair_products = 2 L^2
-            std::vector<double> spp((size_t)K, 2.0 * (double)d);
-            hipMemcpyAsync(e.suff, spp.data(), sizeof(double) * K, hipMemcpyHostToDevice, h->stream);
-            if (hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "ising init failed"; return bail(1); }
-        }
-        if (hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "funnel init failed"; return bail(1); }
+    return 0;
+}
+
+// funnel(0): terms[0] = -(log2pi)/2 - log 3 ; terms[i] = -(log2pi)/2 - log(exp(0)) ; d terms evaluated on the host exactly like the kernels'
+// tree of equal terms and summed with the fixed tree
+double funnel_at_zero(int64_t d) {
+    std::vector<double> terms((size_t)d);
+    const double LOG2PI = 1.8378770664093453;
+    const double sigma = std::exp(0.0 / 2.0), ls = std::log(sigma);
+    for (int64_t i = 0; i < d; ++i) terms[i] = -(0.0 * 0.0 + LOG2PI) / 2.0 - (i == 0 ? std::log(3.0) : ls);
+    int64_t P = 1; while (P < d) P <<= 1;
+    std::vector<double> a((size_t)P, 0.0);
+    for (int64_t i = 0; i < d; ++i) a[i] = terms[i];
+    for (int64_t len = P; len > 1; len /= 2) for (int64_t i = 0; i < len / 2; ++i) a[i] = a[2 * i] + a[2 * i + 1];
+    return a[0];
+}
+// the interpolated paths: initialization(::LogDensity, rng, i) = zeros(dim) (test/supporting/dimensional-analysis.jl:24); Ising: falses(L, L)
+// (examples/ising.jl:85): the streams stay untouched; suff2 = funnel(0)
+int init_zero_state(pte_engine *h) {
+    const pte_config *cfg = &h->cfg;
+    EngineDev &e = h->dev;
+    const int64_t K = h->K, d = h->d;
+    const bool ising = cfg->target == PTE_TARGET_ISING;
+    std::vector<uint64_t> rngs((size_t)(2 * K));
+    const uint64_t G = 0x9e3779b97f4a7c15ULL;
+    auto mix64h = [](uint64_t z) { z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL; z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL; return z ^ (z >> 31); };
+    auto mixg = [](uint64_t z) { z = (z ^ (z >> 33)) * 0xff51afd7ed558ccdULL; z = (z ^ (z >> 33)) * 0xc4ceb9fe1a85ec53ULL; z = (z ^ (z >> 33)) | 1ULL;
+                                 return (__builtin_popcountll(z ^ (z >> 1)) < 24) ? (z ^ 0xaaaaaaaaaaaaaaaaULL) : z; };
+    for (int64_t il = 0; il < K; ++il) {
+        const uint64_t i = (uint64_t)(h->c0 + il);
+        rngs[2 * il] = mix64h(cfg->seed + (2 * i + 1) * G); rngs[2 * il + 1] = mixg(cfg->seed + (2 * i + 2) * G);
     }
+    hipMemcpyAsync(e.rng, rngs.data(), sizeof(uint64_t) * 2 * K, hipMemcpyHostToDevice, h->stream);
+    hipMemsetAsync(e.x, 0, sizeof(double) * K * e.ld, h->stream);
+    hipMemsetAsync(e.suff, 0, sizeof(double) * K, h->stream);
+    std::vector<double> s2((size_t)K, funnel_at_zero(d));
+    hipMemcpyAsync(e.suff2, s2.data(), sizeof(double) * K, hipMemcpyHostToDevice, h->stream);
+    if (ising) {   // all spins -1: every site contributes (-1)(-4) = 4, halved: sum_pair_products = 2 L^2
+        std::vector<double> spp((size_t)K, 2.0 * (double)d);
+        hipMemcpyAsync(e.suff, spp.data(), sizeof(double) * K, hipMemcpyHostToDevice, h->stream);
+        if (hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "ising init failed"; return 1; }
+    }
+    if (hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "funnel init failed"; return 1; }
+    return 0;
+}
+
+// Everything pte_create refuses before it touches a device, in the order that decides which message a doubly-wrong configuration gets.
+int validate_config(const pte_config *cfg) {
+    if (cfg->struct_size != sizeof(pte_config) || cfg->abi_version != PTE_ABI_VERSION)
+        return fail(nullptr, "pte_create: ABI mismatch (struct_size %u vs %zu, version %u vs %d)",
+                    cfg->struct_size, sizeof(pte_config), cfg->abi_version, PTE_ABI_VERSION);
+    if (cfg->n_chains < 1) return fail(nullptr, "pte_create: n_chains must be >= 1");
+    if (cfg->world_size < 1 || cfg->rank < 0 || cfg->rank >= cfg->world_size) return fail(nullptr, "pte_create: bad rank / world_size");
+    if (cfg->n_chains_variational < 0) return fail(nullptr, "pte_create: n_chains_variational must be >= 0");
+    if (cfg->n_chains_variational > 0 && cfg->world_size != 1) return fail(nullptr, "pte_create: two-leg tempering (n_chains_variational > 0) runs on a single engine");
+    if (cfg->n_chains % cfg->world_size != 0) return fail(nullptr, "pte_create: n_chains (%lld) must be a multiple of world_size (%d)", (long long)cfg->n_chains, cfg->world_size);
+    const bool swapper = cfg->target == PTE_TARGET_TEST_SWAPPER;
+    const bool funnel = cfg->target == PTE_TARGET_FUNNEL;
+    const bool ising = cfg->target == PTE_TARGET_ISING;
+    const PathFamily *family = path_family(cfg->target);
+    if (cfg->explorer == PTE_EXPLORER_AAPS || cfg->explorer2 == PTE_EXPLORER_AAPS) {       // AAPS (pte_aaps.hpp): one wave per replica, one explorer
+        if (cfg->explorer2 != PTE_EXPLORER_NONE)
+            return fail(nullptr, "pte_create: AAPS is not available as half of a Compose on the device");
+        if (!funnel && cfg->target != PTE_TARGET_MVN_SCALED_PRECISION)
+            return fail(nullptr, "pte_create: AAPS is implemented on the scaled-precision MVN and funnel paths only (got target %d)", cfg->target);
+        if (cfg->dim < 1 || cfg->dim > 512)
+            return fail(nullptr, "pte_create: AAPS keeps the replica in the registers of one wave, dim must be in 1..512 (got %lld)", (long long)cfg->dim);
+        if (cfg->aaps_K < 0 || cfg->aaps_K > 64)
+            return fail(nullptr, "pte_create: AAPS needs aaps_K in 0..64 (got %d)", cfg->aaps_K);
+        if (!(cfg->am_step_size > 0) || !std::isfinite(cfg->am_step_size))
+            return fail(nullptr, "pte_create: AAPS needs a positive finite step size (got %g)", cfg->am_step_size);
+        if (cfg->debug_kernel != 0)
+            return fail(nullptr, "pte_create: AAPS has one kernel; debug_kernel must be 0 (got %d)", cfg->debug_kernel);
+    }
+    if (family && !funnel) {    // the families with kernels of their own -- Gaussian mixture, Bayesian GLM: one wave per replica, SliceSampler / AutoMALA / MALA (AAPS: refused above)
+        auto on_family = [](int k) { return k == PTE_EXPLORER_SLICE || k == PTE_EXPLORER_AUTOMALA || k == PTE_EXPLORER_MALA; };
+        if (!on_family(cfg->explorer) || (cfg->explorer2 != PTE_EXPLORER_NONE && !on_family(cfg->explorer2)))
+            return fail(nullptr, "pte_create: the %s path is implemented for SliceSampler / AutoMALA / MALA (and Compose of them) only (got explorers %d, %d)",
+                        family->name, cfg->explorer, cfg->explorer2);
+        if (cfg->dim < 1 || cfg->dim > 512)
+            return fail(nullptr, "pte_create: the %s path keeps the replica in the registers of one wave, dim must be in 1..512 (got %lld)", family->name, (long long)cfg->dim);
+        if ((cfg->debug_kernel & ~(PTE_KERNEL_FLAG_BITS | PTE_KERNEL_TEST_BITS)) != 0)
+            return fail(nullptr, "pte_create: debug_kernel %d is not available on the %s path (%s)", cfg->debug_kernel, family->name, family->one_kernel);
+        if (cfg->n_chains_variational > 0)
+            return fail(nullptr, "pte_create: two-leg tempering (n_chains_variational > 0) is not available on the %s path", family->name);
+    }
+    if (ising) {
+        const int64_t L = (int64_t)std::llround(std::sqrt((double)cfg->dim));
+        if (L < 2 || L * L != cfg->dim || cfg->dim > 65536) return fail(nullptr, "pte_create: Ising needs dim = base_length^2 <= 65536");
+        if (cfg->explorer == PTE_EXPLORER_SLICE || cfg->explorer2 == PTE_EXPLORER_SLICE)   // spins are Bool coordinates: SliceSampler.jl:65-86 (and :136-142, :189 for Integer ones)
+            return fail(nullptr, "pte_create: SliceSampler's Bool / Integer coordinate methods are not available on the device (its Float64 methods are); "
+                                 "the Ising path is explored by IsingMetropolis only -- use the reference CPU path for Bool / Integer states");
+        if (cfg->explorer != PTE_EXPLORER_ISING_METROPOLIS) return fail(nullptr, "pte_create: the Ising path is explored by IsingMetropolis only");
+    } else if (cfg->explorer == PTE_EXPLORER_ISING_METROPOLIS) return fail(nullptr, "pte_create: IsingMetropolis needs the Ising target");
+    if (!swapper && !family && !ising && cfg->target != PTE_TARGET_MVN_SCALED_PRECISION)
+        return fail(nullptr, "pte_create: target %d has no device log-potential; use the reference CPU path", cfg->target);
+    auto grad_based = [](int k) { return k == PTE_EXPLORER_AUTOMALA || k == PTE_EXPLORER_MALA; };
+    const bool uses_grad = grad_based(cfg->explorer) || grad_based(cfg->explorer2);
+    const bool aaps = cfg->explorer == PTE_EXPLORER_AAPS;
+    auto on_path = [&](int k) { return grad_based(k) || k == PTE_EXPLORER_SLICE; };
+    if (funnel && !aaps && !(on_path(cfg->explorer) && (cfg->explorer2 == PTE_EXPLORER_NONE || on_path(cfg->explorer2))))
+        return fail(nullptr, "pte_create: the funnel path is implemented for AutoMALA / MALA / SliceSampler (and Compose of them); use the reference CPU path");
+    if ((uses_grad || funnel) && (cfg->dim < 1 || cfg->dim > 1024))
+        return fail(nullptr, "pte_create: AutoMALA / MALA (and every explorer of the funnel path) keep the replica in registers, dim must be in 1..1024 (got %lld)", (long long)cfg->dim);
+    if (funnel && (cfg->debug_kernel & ~(PTE_KERNEL_FLAG_BITS | PTE_KERNEL_TEST_BITS)) != 0)
+        return fail(nullptr, "pte_create: debug_kernel %d is not available on the %s path (%s)", cfg->debug_kernel, family->name, family->one_kernel);
+    if (cfg->explorer2 != PTE_EXPLORER_NONE) {           // Compose(first, second)
+        auto composable = [&](int k) { return k == PTE_EXPLORER_SLICE || grad_based(k); };
+        if (!composable(cfg->explorer) || !composable(cfg->explorer2))
+            return fail(nullptr, "pte_create: Compose is available for SliceSampler / AutoMALA / MALA (got %d, %d)", cfg->explorer, cfg->explorer2);
+    }
+    if (!swapper && !ising && (cfg->dim < 1 || cfg->dim > 4096))
+        return fail(nullptr, "pte_create: dim must be in 1..4096 (got %lld)", (long long)cfg->dim);
+    if (swapper && cfg->explorer != PTE_EXPLORER_NONE)
+        return fail(nullptr, "pte_create: TestSwapper has no explorer");
+    if (!swapper && !ising && cfg->explorer != PTE_EXPLORER_TOY && cfg->explorer != PTE_EXPLORER_SLICE && !grad_based(cfg->explorer) && !aaps)
+        return fail(nullptr, "pte_create: explorer %d is not implemented on the device", cfg->explorer);
+    if ((cfg->record_flags & PTE_RECORD_TRACES_EXTENDED) && !(cfg->record_flags & PTE_RECORD_TRACES))
+        return fail(nullptr, "pte_create: PTE_RECORD_TRACES_EXTENDED needs PTE_RECORD_TRACES");
+    if (cfg->record_flags & PTE_RECORD_REFERENCE_REDUCTION) {
+        if (!(cfg->record_flags & PTE_RECORD_INDEX_PROCESS))
+            return fail(nullptr, "pte_create: PTE_RECORD_REFERENCE_REDUCTION needs PTE_RECORD_INDEX_PROCESS (the replay asks which replica held the lower chain of a pair)");
+        if ((double)cfg->max_scans_per_round * (double)(cfg->n_chains + cfg->n_chains_variational) * 16.0 > 64e9)
+            return fail(nullptr, "pte_create: the swap log (max_scans_per_round x chains x 2 doubles) would exceed 64 GB");
+    }
+#ifndef PTE_TEST_KERNELS
+    if (cfg->debug_kernel & PTE_KERNEL_TEST_BITS)
+        return fail(nullptr, "pte_create: debug_kernel 0x%x carries a fault-injection flag (PTE_KERNEL_TEST_*); those exist in the test build libpte_test.so only", cfg->debug_kernel);
+#endif
+    {   // debug_kernel: 0 = the default kernel of the explorer; anything else must exist in THIS build (no silent fall-through)
+        const int dk = cfg->debug_kernel & ~(PTE_KERNEL_FLAG_BITS | PTE_KERNEL_TEST_BITS);      // (the flag bit chooses the scan loop's form, not the kernel generation)
+        const bool slice = cfg->explorer == PTE_EXPLORER_SLICE || cfg->explorer2 == PTE_EXPLORER_SLICE;
+        bool ok = dk == 0 || (slice && dk == PTE_KERNEL_SLICE_SEQUENTIAL) || (ising && dk == PTE_KERNEL_ISING_BYTES);
+#ifdef PTE_TEST_KERNELS
+        ok = ok || (slice && (dk == 2 || dk == 5 || dk == 7 || dk == 8)) || (ising && dk == PTE_KERNEL_ISING_BITS);
+#endif
+        if (!ok) return fail(nullptr, "pte_create: debug_kernel %d is not available for this explorer in this build of libpte "
+                                      "(0 = default, %d = sequential SliceSampler kernel; the other generations live in the test build libpte_test.so)",
+                             dk, PTE_KERNEL_SLICE_SEQUENTIAL);
+    }
+    if ((cfg->record_flags & PTE_RECORD_TRACES) &&
+        (double)cfg->max_scans_per_round * (double)((cfg->record_flags & PTE_RECORD_TRACES_EXTENDED) ? cfg->n_chains / cfg->world_size : 1) * (double)(cfg->dim + 1) * 8.0 > 64e9)
+        return fail(nullptr, "pte_create: the traces buffer (max_scans_per_round x chains x (dim+1) doubles) would exceed 64 GB");
+    return 0;
+}
+
+int poisoned_error(pte_engine *h, const char *what) {
+    return fail(h, "%s: this engine is poisoned -- an earlier pte_run_scans failed inside the one-launch scan loop, its replicas stopped at different scans; "
+                   "restore it with pte_set_state(state, chain, rng) or destroy it", what);
+}
+#define PTE_ALIVE(h, what) do { if ((h)->poisoned) return poisoned_error(h, what); } while (0)
+
+}  // namespace
+
+extern "C" {
+
+int pte_default_config(pte_config *c) {
+    if (!c) return 1;
+    std::memset(c, 0, sizeof *c);
+    c->struct_size = sizeof(pte_config);
+    c->abi_version = PTE_ABI_VERSION;
+    c->device = 0;
+    c->target = PTE_TARGET_MVN_SCALED_PRECISION;
+    c->explorer = PTE_EXPLORER_TOY;
+    c->record_flags = PTE_RECORD_ROUND_TRIP | PTE_RECORD_INDEX_PROCESS;
+    c->n_chains = 10; c->dim = 2; c->seed = 1;
+    c->max_scans_per_round = 1024;
+    c->target_params[0] = 1.0; c->target_params[1] = 10.0;
+    c->slice_w = 10.0; c->slice_p = 20; c->slice_n_passes = 3; c->slice_max_iter = 1024;
+    c->am_base_n_refresh = 3; c->am_exponent_n_refresh = 0.35; c->am_step_size = 1.0;
+    c->am_p0 = 1.0 / 3.0; c->am_p1 = 1.0 / 3.0; c->am_preconditioner = 2;
+    c->aaps_K = 5;                                   // AAPS.jl
+    c->rank = 0; c->world_size = 1;
+    return 0;
+}
+
+const char *pte_last_error(const pte_engine *h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+
+int pte_create(const pte_config *cfg, pte_engine **out) {
+    if (!cfg || !out) return fail(nullptr, "pte_create: null argument");
+    *out = nullptr;
+    if (validate_config(cfg)) return 1;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(nullptr, "pte_create: no HIP device available (this library has no CPU fallback)");
+    if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, "pte_create: bad device ordinal %d", cfg->device);
+
+    pte_engine *h = new pte_engine();
+    h->cfg = *cfg;
+    const int64_t N = h->N = cfg->n_chains + cfg->n_chains_variational;      // Inputs.jl:128
+    const int64_t d = h->d = cfg->target == PTE_TARGET_TEST_SWAPPER ? 0 : cfg->dim;
+    h->world = cfg->world_size; h->rank = cfg->rank;
+    const int64_t K = h->K = N / cfg->world_size;
+    h->c0 = K * cfg->rank;
+    auto bail = [&](int) { g_create_error = h->err; pte_destroy(h); return 1; };
+    if (hipSetDevice(cfg->device) != hipSuccess) { h->err = "hipSetDevice failed"; return bail(1); }
+    if (hipStreamCreate(&h->stream) != hipSuccess) { h->err = "hipStreamCreate failed"; return bail(1); }
+    const int64_t B = (d + 63) / 64;
+    h->nlu = next_pow2_log(B > 0 ? B : 1);
+    // pte_config.debug_kernel (validated above): which kernel generation explores; never read from the environment
+    const int dk_kernel = cfg->debug_kernel & ~(PTE_KERNEL_FLAG_BITS | PTE_KERNEL_TEST_BITS);
+    h->fused_allowed = (cfg->debug_kernel & PTE_KERNEL_TWO_LAUNCHES) == 0;
+    h->fused_wg_allowed = (cfg->debug_kernel & PTE_KERNEL_SCAN_LOOP_ONE_CHAIN) == 0;
+    h->test_fault = (cfg->debug_kernel & PTE_KERNEL_TEST_DEAD_CHAIN) ? 1 : ((cfg->debug_kernel & PTE_KERNEL_TEST_LATE_WORKGROUP) ? 2 : 0);
+    if (cfg->explorer == PTE_EXPLORER_SLICE || cfg->explorer2 == PTE_EXPLORER_SLICE) h->slice_impl = dk_kernel == 0 ? 8 : dk_kernel;
+    if (cfg->explorer == PTE_EXPLORER_ISING_METROPOLIS) h->ising_impl = dk_kernel == PTE_KERNEL_ISING_BITS ? 1 : (dk_kernel == PTE_KERNEL_ISING_BYTES ? 2 : 0);
+    if (alloc_engine(h)) return bail(1);
+    default_schedule(h);
+    if (upload_ladder(h)) return bail(1);
+    if (reset_recorders(h)) return bail(1);
+    if (init_replicas(h)) return bail(1);
+    if ((on_interpolated_path(cfg->target) || cfg->target == PTE_TARGET_ISING) && init_zero_state(h)) return bail(1);
     *out = h;
     return 0;
 }
@@ -1140,8 +1180,7 @@ int pte_explore(pte_engine *h, int64_t scan) {
 int pte_swap(pte_engine *h, int64_t scan) {
     if (!h) return 1;
     PTE_ALIVE(h, "pte_swap");
-    if (mixture_missing(h)) return mixture_missing_error(h, "pte_swap");
-    if (glm_missing(h)) return glm_missing_error(h, "pte_swap");
+    if (!family_ready(h)) return family_missing_error(h, "pte_swap");
     HIP_OK(h, hipSetDevice(h->cfg.device));
     if (launch_swap(h, scan)) return 1;
     return check_device_error(h);
@@ -1151,8 +1190,7 @@ int pte_run_scans(pte_engine *h, int64_t first_scan, int64_t n_scans) {
     if (!h) return 1;
     HIP_OK(h, hipSetDevice(h->cfg.device));
     PTE_ALIVE(h, "pte_run_scans");
-    if (mixture_missing(h)) return mixture_missing_error(h, "pte_run_scans");
-    if (glm_missing(h)) return glm_missing_error(h, "pte_run_scans");
+    if (!family_ready(h)) return family_missing_error(h, "pte_run_scans");
     if (h->world != 1) return run_scans_sharded(h, first_scan, n_scans);
     if (fused_scans_eligible(h, n_scans)) {
         if (h->fused_skip > 0) h->fused_skip -= 1;         // a recent launch found the device shared: not this call (run_scans_fused)
@@ -1844,9 +1882,7 @@ int pte_group_run_scans(pte_engine *const *hs, int32_t G, int64_t first_scan, in
     if (!hs || G < 1 || !hs[0]) return fail(nullptr, "pte_group_run_scans: null argument");
     pte_engine *h0 = hs[0];
     for (int32_t g = 0; g < G; ++g)
-        if (hs[g] && mixture_missing(hs[g])) return mixture_missing_error(h0, "pte_group_run_scans");
-    for (int32_t g = 0; g < G; ++g)
-        if (hs[g] && glm_missing(hs[g])) return glm_missing_error(h0, "pte_group_run_scans");
+        if (hs[g] && !family_ready(hs[g])) return family_missing_error(h0, "pte_group_run_scans", hs[g]);
     for (int g = 0; g < G; ++g) {
         pte_engine *h = hs[g];
         if (!h) return fail(h0, "pte_group_run_scans: engine %d is null", g);
@@ -1892,14 +1928,13 @@ int pte_group_run_scans(pte_engine *const *hs, int32_t G, int64_t first_scan, in
 
 const char *pte_kernel_name(const pte_engine *h) {
     if (!h) return "";
+    const PathFamily *f = path_family(h->cfg.target);
     switch (h->cfg.explorer) {
     case PTE_EXPLORER_TOY: return "k_explore_toy";
     case PTE_EXPLORER_SLICE:
         // SliceSampler on the interpolated path: the one-wave Langevin-family kernel in its slice mode (no momentum, gradient or trial copies:
         // its sixteen-block instantiation for d > 512 holds 255 VGPRs + 7 AGPRs and does not touch scratch)
-        if (h->cfg.target == PTE_TARGET_FUNNEL) return "k_explore_automala";
-        if (h->cfg.target == PTE_TARGET_GAUSSIAN_MIXTURE) return "k_explore_mixture";
-        if (h->cfg.target == PTE_TARGET_BAYESIAN_GLM) return "k_explore_glm";
+        if (f) return f->kernel;
         switch (h->slice_impl) {
         case 1: return "k_explore_slice"; case 2: return "k_explore_slice2"; case 5: return "k_explore_slice5";
         case 7: return "k_explore_slice7";
@@ -1910,8 +1945,7 @@ const char *pte_kernel_name(const pte_engine *h) {
     case PTE_EXPLORER_AUTOMALA: case PTE_EXPLORER_MALA:
         // d > 512: four waves per replica (pte_automala_mw.hpp, round 6); the one-wave kernel with sixteen blocks per lane -- 250-300 spilled VGPRs,
         // "unoptimised" in rounds 1-5 -- survives in the test build as its A/B reference
-        if (h->cfg.target == PTE_TARGET_GAUSSIAN_MIXTURE) return "k_explore_mixture";
-        if (h->cfg.target == PTE_TARGET_BAYESIAN_GLM) return "k_explore_glm";
+        if (f && h->d <= 512) return f->kernel;
         if (h->d > 512) return (h->cfg.debug_kernel & PTE_KERNEL_TEST_LANGEVIN_ONE_WAVE) ? "k_explore_automala [test build: one wave, sixteen blocks per lane]" : "k_explore_langevin_mw";
         return "k_explore_automala";
     case PTE_EXPLORER_AAPS: return "k_explore_aaps";
@@ -1955,33 +1989,6 @@ int pte_scan_loop_stats(const pte_engine *h, int64_t *fused_calls, int64_t *gate
     if (poisoned) *poisoned = h->poisoned ? 1 : 0;
     return 0;
 }
-
-namespace {
-int refresh_funnel_stats(pte_engine *h) {
-    const int E = h->d <= 64 ? 1 : h->d <= 128 ? 2 : h->d <= 256 ? 4 : h->d <= 512 ? 8 : 16;
-    const double log3 = std::log(3.0);
-    const unsigned N = (unsigned)h->K;
-    langevin_refresh_funnel_stats(E, N, h->stream, h->dev, log3);
-    HIP_OK(h, hipGetLastError());
-    HIP_OK(h, hipStreamSynchronize(h->stream));
-    return 0;
-}
-int refresh_mixture_stats(pte_engine *h) {
-    const int E = h->d <= 64 ? 1 : h->d <= 128 ? 2 : h->d <= 256 ? 4 : 8;
-    if (mixture_refresh_stats(E, (unsigned)h->K, h->stream, h->dev, mixture_params(h))) return fail(h, "this build holds no Gaussian-mixture kernel for dim %lld", (long long)h->d);
-    HIP_OK(h, hipGetLastError());
-    HIP_OK(h, hipStreamSynchronize(h->stream));
-    return 0;
-}
-int refresh_glm_stats(pte_engine *h) {
-    const int E = h->d <= 64 ? 1 : h->d <= 128 ? 2 : h->d <= 256 ? 4 : 8;
-    if (glm_refresh_stats(E, h->glm_lik, (unsigned)h->K, h->stream, h->dev, h->glm, h->cfg.target_params[0]))
-        return fail(h, "this build holds no Bayesian-GLM kernel for dim %lld", (long long)h->d);
-    HIP_OK(h, hipGetLastError());
-    HIP_OK(h, hipStreamSynchronize(h->stream));
-    return 0;
-}
-}  // namespace
 
 // The Gaussian-mixture target.  Host, once per call: lw_k = log w_k - logsumexp(log w), c_k = lw_k - sum_i log sigma_ki - (d/2) log 2 pi
 // (index order), inv_ki = 1 / sigma_ki; uploaded as [8][ld] means, [8][ld] inverses (zero-padded), [8] constants.
@@ -2027,7 +2034,7 @@ int pte_set_target_mixture(pte_engine *h, int64_t n_components, const double *we
     HIP_OK(h, hipMemcpyAsync(h->d_mix, buf.data(), sizeof(double) * buf.size(), hipMemcpyHostToDevice, h->stream));
     HIP_OK(h, hipStreamSynchronize(h->stream));
     h->mix_K = (int)K;
-    return refresh_mixture_stats(h);                               // suff / suff2 of the current states
+    return refresh_path_stats(h);                                  // suff / suff2 of the current states
 }
 
 // The Bayesian GLM.  Host, once per call: c_prior = -(d/2) log(2 pi / p), c_obs = 0 (logit) or -n (log sigma + log(2 pi) / 2)
@@ -2078,7 +2085,7 @@ int pte_set_target_glm(pte_engine *h, int32_t likelihood, int64_t n_obs, const d
     g.w1 = likelihood == PTE_GLM_NORMAL_IDENTITY ? 1.0 / (noise_sd * noise_sd) : 0.0;
     g.w2 = likelihood == PTE_GLM_NORMAL_IDENTITY ? 1.0 / (2.0 * (noise_sd * noise_sd)) : 0.0;
     h->glm_lik = likelihood;
-    return refresh_glm_stats(h);                                   // suff / suff2 of the current states
+    return refresh_path_stats(h);                                  // suff / suff2 of the current states
 }
 
 // update_reference! + update_path_variational (src/variational/variational.jl:28-41, GaussianReference.jl:24-31): from now on
@@ -2109,15 +2116,14 @@ int pte_set_variational_reference(pte_engine *h, const double *mean, const doubl
     HIP_OK(h, hipStreamSynchronize(h->stream));
     e.v_mean = h->d_vref; e.v_std = h->d_vref + d; e.v_c0 = h->d_vref + 2 * d; e.v_i2 = h->d_vref + 3 * d; e.v_gf = h->d_vref + 4 * d;
     e.v_use = h->d_vuse;
-    return refresh_funnel_stats(h);                                // suff3 of the current states
+    return refresh_path_stats(h);                                  // suff3 of the current states
 }
 
 int pte_get_state(const pte_engine *hc, double *state, int64_t *chain, uint64_t *rng) {
     pte_engine *h = const_cast<pte_engine *>(hc);
     if (!h) return 1;
     PTE_ALIVE(h, "pte_get_state");
-    if (mixture_missing(h)) return mixture_missing_error(h, "pte_get_state");
-    if (glm_missing(h)) return glm_missing_error(h, "pte_get_state");
+    if (!family_ready(h)) return family_missing_error(h, "pte_get_state");
     HIP_OK(h, hipSetDevice(h->cfg.device));
     const int64_t N = h->K, d = h->d;
     const bool ising = h->cfg.target == PTE_TARGET_ISING;
@@ -2204,9 +2210,7 @@ int pte_set_state(pte_engine *h, const double *state, const int64_t *chain, cons
         hipError_t e1 = hipStreamSynchronize(h->stream);
         hipFree(tmp);
         HIP_OK(h, e1);
-        if (h->cfg.target == PTE_TARGET_FUNNEL && refresh_funnel_stats(h)) return 1;   // + the target (and variational) log densities
-        if (h->cfg.target == PTE_TARGET_GAUSSIAN_MIXTURE && h->mix_K > 0 && refresh_mixture_stats(h)) return 1;   // + the mixture's log densities
-        if (h->cfg.target == PTE_TARGET_BAYESIAN_GLM && h->glm.n > 0 && refresh_glm_stats(h)) return 1;           // + the GLM's target log densities
+        if (family_ready(h) && refresh_path_stats(h)) return 1;   // + the target (and variational) log densities, once the family's data is there
     }
     return 0;
 }
@@ -2253,10 +2257,10 @@ int pte_set_rng_policy(int32_t device, uint32_t policy) {
     if (policy & ~PTE_RNG_POLICY_VALID_MASK) return fail(nullptr, "pte_set_rng_policy: invalid policy 0x%x", policy);
     if (hipSetDevice(device) != hipSuccess) return fail(nullptr, "pte_set_rng_policy: no HIP device %d", device);
     hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(g_rng_policy), &policy, sizeof policy);
-    if (e == hipSuccess) e = (hipError_t)langevin_set_rng_policy(policy);       // the second translation unit's copy of the word
-    if (e == hipSuccess) e = (hipError_t)aaps_set_rng_policy(policy);           // ... and the third's
-    if (e == hipSuccess) e = (hipError_t)mixture_set_rng_policy(policy);        // ... and the fourth's
-    if (e == hipSuccess) e = (hipError_t)glm_set_rng_policy(policy);            // ... and the fifth's
+#define PTE_RNG_POLICY_SETTER(unit) unit##_set_rng_policy,
+    int (*const others[])(unsigned) = {PTE_KERNEL_UNITS(PTE_RNG_POLICY_SETTER)};      // every other translation unit's copy of the word (all the same word when pte.hip is compiled alone)
+#undef PTE_RNG_POLICY_SETTER
+    for (auto set : others) if (e == hipSuccess) e = (hipError_t)set(policy);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     return e == hipSuccess ? 0 : fail(nullptr, "pte_set_rng_policy: %s", hipGetErrorString(e));
 }

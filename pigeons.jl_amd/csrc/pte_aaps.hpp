@@ -243,18 +243,12 @@ __global__ __launch_bounds__(64) void k_explore_aaps(EngineDev e, AapsParams ap)
     record_after_explore(e, cl, c, slot, lane, lp_before, S, l2, l3);
 }
 
-template <typename Kn>
-static inline void aaps_launch_one(Kn kernel, const AapsLaunch &L, const EngineDev &dev, const AapsParams &ap) {
-    if (L.ext) hipExtLaunchKernelGGL(kernel, dim3(L.N), dim3(64), 0, L.stream, L.ev_a, L.ev_b, 0, dev, ap);
-    else hipLaunchKernelGGL(kernel, dim3(L.N), dim3(64), 0, L.stream, dev, ap);
-}
-
 int aaps_launch(const AapsLaunch &L, const EngineDev &dev, const AapsParams &ap) {
 #define AAPS_ONE(EE)                                                                                                 \
-    if (L.target == TGT_FUNNEL && L.full) aaps_launch_one(k_explore_aaps<EE, TGT_FUNNEL, true>, L, dev, ap);         \
-    else if (L.target == TGT_FUNNEL) aaps_launch_one(k_explore_aaps<EE, TGT_FUNNEL, false>, L, dev, ap);             \
-    else if (L.full) aaps_launch_one(k_explore_aaps<EE, TGT_MVN, true>, L, dev, ap);                                 \
-    else aaps_launch_one(k_explore_aaps<EE, TGT_MVN, false>, L, dev, ap);
+    if (L.target == TGT_FUNNEL && L.full) launch_on(L.at, k_explore_aaps<EE, TGT_FUNNEL, true>, 64, 0, dev, ap);         \
+    else if (L.target == TGT_FUNNEL) launch_on(L.at, k_explore_aaps<EE, TGT_FUNNEL, false>, 64, 0, dev, ap);             \
+    else if (L.full) launch_on(L.at, k_explore_aaps<EE, TGT_MVN, true>, 64, 0, dev, ap);                                 \
+    else launch_on(L.at, k_explore_aaps<EE, TGT_MVN, false>, 64, 0, dev, ap);
     switch (L.E) {
     case 1: AAPS_ONE(1) break; case 2: AAPS_ONE(2) break; case 4: AAPS_ONE(4) break; case 8: AAPS_ONE(8) break;
     default: return 1;
@@ -263,6 +257,6 @@ int aaps_launch(const AapsLaunch &L, const EngineDev &dev, const AapsParams &ap)
     return 0;
 }
 
-int aaps_set_rng_policy(unsigned policy) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_rng_policy), &policy, sizeof policy); }
+PTE_DEFINE_RNG_POLICY_SETTER(aaps)
 
 }  // namespace pte

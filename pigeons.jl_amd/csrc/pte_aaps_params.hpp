@@ -1,7 +1,5 @@
 // pte_aaps_params.hpp -- what the launcher (pte.hip) and the AAPS kernels (pte_aaps.hpp) share: kernel parameters and the one entry point
-// through which the kernels are launched.  The kernels are the library's third translation unit (pte_aaps.hip, compiled with the flags of
-// pte_langevin.hip): a unit of their own leaves the generated code of the shipped kernels exactly as it was.  Tools and development builds
-// compile pte.hip alone (no -DPTE_SPLIT_LANGEVIN): it then includes the kernels and this entry point itself.
+// through which the kernels are launched.  The kernels are a translation unit of their own, pte_aaps.hip (pte_automala_params.hpp says why).
 #pragma once
 #include "pte_automala_params.hpp"
 
@@ -25,10 +23,8 @@ struct AapsParams {
     double log3;                // log(3.0) from the host libm
 };
 
-// one launch of k_explore_aaps<E, target, whole blocks>: N workgroups of one wave on `stream`; `ext`: the launch carries the start / stop
-// events (hipExtLaunchKernelGGL, as LangevinLaunch)
-struct AapsLaunch { int E; int target; bool full; unsigned N; hipStream_t stream; bool ext; hipEvent_t ev_a, ev_b; };
+// one launch of k_explore_aaps<E, target, whole blocks>, one workgroup of one wave per replica
+struct AapsLaunch { int E; int target; bool full; LaunchSite at; };
 int aaps_launch(const AapsLaunch &L, const EngineDev &dev, const AapsParams &ap);      // 0, or 1 if this build holds no such kernel
-int aaps_set_rng_policy(unsigned policy);                                               // the translation unit's own copy of g_rng_policy (hipError_t as int)
 
 }  // namespace pte

@@ -1,9 +1,18 @@
-// pte_automala_params.hpp -- what the launcher (pte.hip) and the Langevin-family kernels (pte_automala.hpp) share: kernel parameters and
-// the one entry point through which the kernels are launched.  The product library is built from TWO translation units -- pte.hip
-// (everything else, scheduled with -amdgpu-sched-strategy=max-ilp: the one-wave-per-SIMD slice kernels gain 1.3-2.3 %) and
-// pte_langevin.hip (these kernels with the default scheduler: max-ilp costs their d >= 512 instantiations up to 10 %).  Tools and
-// development builds compile pte.hip alone (no -DPTE_SPLIT_LANGEVIN): it then includes the kernels and this entry point itself.
+// pte_automala_params.hpp -- what the launcher (pte.hip) and the kernel families share: kernel parameters, where a launch goes (LaunchSite,
+// launch_on) and, per family, the one entry point through which its kernels are launched.
+//
+// The product library is built from FIVE translation units (UNITS in __graft_entry__.py):
+//   pte.hip           the C ABI, the launcher and every kernel not named below, scheduled with -O2 -amdgpu-sched-strategy=max-ilp: the
+//                     one-wave-per-SIMD slice kernels gain 1.3-2.3 %
+//   pte_langevin.hip  AutoMALA / MALA and SliceSampler on the funnel path (pte_langevin_launch.hpp) with the default scheduler: max-ilp
+//                     costs their d >= 512 instantiations up to 10 %
+//   pte_aaps.hip, pte_mixture.hip, pte_glm.hip
+//                     the AAPS, Gaussian-mixture and Bayesian-GLM kernels with pte_langevin.hip's flags.  A unit each: whatever is added
+//                     to an existing unit moves the generated code of the kernels already in it (tests/test_codegen_*.py freeze it)
+// Every unit includes pte_kernels.hpp and therefore holds its own copy of the `static __device__` word g_rng_policy: PTE_KERNEL_UNITS below.
+// Tools and development builds compile pte.hip alone (no -DPTE_SPLIT_LANGEVIN): it then includes the kernel headers and their entry points itself.
 #pragma once
+#include <hip/hip_ext.h>
 #include "pte_kernels.hpp"
 
 namespace pte {
@@ -34,16 +43,32 @@ struct AmParams {
     int pace;               // k_*_langevin_mw: 1 = steer the waves' priorities by the replicas' pace (several workgroups share a compute unit and all are resident)
 };
 
-// one launch of k_explore_automala<E, target, slice mode, whole blocks>: N workgroups of one wave on `stream`; `ext`: the launch carries
-// the start / stop events (hipExtLaunchKernelGGL: the kernel's own begin and end, see PTE_LAUNCH1 in pte.hip)
-struct LangevinLaunch { int E; int target; bool slice; bool full; unsigned N; hipStream_t stream; bool ext; hipEvent_t ev_a, ev_b;
+// Where one kernel launch goes: `grid` workgroups on `stream`.  ev_a != nullptr: the launch carries the start / stop events of the timing
+// bracket it stands in (hipExtLaunchKernelGGL: they take the kernel's own begin / end timestamps -- what rocprofv3's kernel trace reports --
+// instead of bracketing it with two event-record commands, which add the stream's hand-over time around a ~85 us kernel (~7 us)).
+struct LaunchSite { dim3 grid; hipStream_t stream; hipEvent_t ev_a = nullptr, ev_b = nullptr; };
+template <typename K, typename... Args>
+static inline void launch_on(const LaunchSite &at, K kernel, dim3 block, size_t lds_bytes, const Args &...args) {
+    if (at.ev_a) hipExtLaunchKernelGGL(kernel, at.grid, block, lds_bytes, at.stream, at.ev_a, at.ev_b, 0, args...);
+    else hipLaunchKernelGGL(kernel, at.grid, block, lds_bytes, at.stream, args...);
+}
+
+// one launch of k_explore_automala<E, target, slice mode, whole blocks>, one workgroup of one wave per replica
+struct LangevinLaunch { int E; int target; bool slice; bool full; LaunchSite at;
                         const ScanLoop *scans = nullptr;        // scans != nullptr: k_scans_automala, all the scans of a pte_run_scans call in one launch
-                        int scan_wg = 1;                         // ... > 1: k_scans_automala_wg, that many consecutive chains (waves) per workgroup (must equal langevin_scan_wg())
+                        int scan_wg = 1;                         // ... > 1: k_scans_automala_wg, that many consecutive chains (waves) per workgroup (must equal langevin_scan_wg(); at.grid counts those workgroups)
                         bool one_wave16 = false; };              // test build only (PTE_KERNEL_TEST_LANGEVIN_ONE_WAVE): 512 < d <= 1024 on the one-wave kernel with sixteen blocks per lane
 int langevin_launch(const LangevinLaunch &L, const EngineDev &dev, const AmParams &ap);     // 0, or 1 if this build holds no such kernel
 int langevin_scan_loop_blocks_per_cu(int E, int target, bool full, int scan_wg = 1);         // occupancy of k_scans_automala[_wg]<E, target, full> (0: not in this build)
 int langevin_scan_wg();                                                                      // PTE_SCAN_WG of the Langevin translation unit
 void langevin_refresh_funnel_stats(int E, unsigned N, hipStream_t stream, const EngineDev &dev, double log3);      // k_refresh_funnel_stats<E>
-int langevin_set_rng_policy(unsigned policy);                                                // the translation unit's own copy of g_rng_policy (hipError_t as int)
+
+// The translation units besides pte.hip.  Each defines <unit>_set_rng_policy -- its own copy of g_rng_policy (hipError_t as int) -- with
+// PTE_DEFINE_RNG_POLICY_SETTER(<unit>), and pte_set_rng_policy walks this list: a unit listed here without the setter does not link.
+#define PTE_KERNEL_UNITS(X) X(langevin) X(aaps) X(mixture) X(glm)
+#define PTE_DECLARE_RNG_POLICY_SETTER(unit) int unit##_set_rng_policy(unsigned policy);
+PTE_KERNEL_UNITS(PTE_DECLARE_RNG_POLICY_SETTER)
+#define PTE_DEFINE_RNG_POLICY_SETTER(unit)                                                                                        \
+    int unit##_set_rng_policy(unsigned policy) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_rng_policy), &policy, sizeof policy); }
 
 }  // namespace pte

@@ -36,18 +36,12 @@ __global__ __launch_bounds__(64) void k_refresh_glm_stats(EngineDev e, GlmParams
     if (lane == 0) { e.suff[slot] = S; e.suff2[slot] = l2; }
 }
 
-template <typename Kn>
-static inline void glm_launch_one(Kn kernel, const GlmLaunch &L, const EngineDev &dev, const AmParams &ap, const GlmParams &gp) {
-    const size_t lds = glm_lds_bytes(L.E, gp.n_pad);
-    if (L.ext) hipExtLaunchKernelGGL(kernel, dim3(L.N), dim3(64), lds, L.stream, L.ev_a, L.ev_b, 0, dev, ap, gp);
-    else hipLaunchKernelGGL(kernel, dim3(L.N), dim3(64), lds, L.stream, dev, ap, gp);
-}
-
 int glm_launch(const GlmLaunch &L, const EngineDev &dev, const AmParams &ap, const GlmParams &gp) {
+    const size_t lds = glm_lds_bytes(L.E, gp.n_pad);
 #define GLM_LIK(EE, LL)                                                                                         \
-    if (L.slice) glm_launch_one(k_explore_glm<EE, LL, true, false>, L, dev, ap, gp);                            \
-    else if (L.full) glm_launch_one(k_explore_glm<EE, LL, false, true>, L, dev, ap, gp);                        \
-    else glm_launch_one(k_explore_glm<EE, LL, false, false>, L, dev, ap, gp);
+    if (L.slice) launch_on(L.at, k_explore_glm<EE, LL, true, false>, 64, lds, dev, ap, gp);                            \
+    else if (L.full) launch_on(L.at, k_explore_glm<EE, LL, false, true>, 64, lds, dev, ap, gp);                        \
+    else launch_on(L.at, k_explore_glm<EE, LL, false, false>, 64, lds, dev, ap, gp);
 #define GLM_ONE(EE)                                                                                             \
     if (L.lik == GLM_NORMAL_IDENTITY) { GLM_LIK(EE, GLM_NORMAL_IDENTITY) } else { GLM_LIK(EE, GLM_BERNOULLI_LOGIT) }
     switch (L.E) {
@@ -72,6 +66,6 @@ int glm_refresh_stats(int E, int lik, unsigned N, hipStream_t stream, const Engi
     return 0;
 }
 
-int glm_set_rng_policy(unsigned policy) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_rng_policy), &policy, sizeof policy); }
+PTE_DEFINE_RNG_POLICY_SETTER(glm)
 
 }  // namespace pte

@@ -1,7 +1,6 @@
 // pte_glm_params.hpp -- what the launcher (pte.hip) and the Bayesian-GLM kernels (pte_glm.hpp) share: the data as the kernels read it and
-// the one entry point through which the kernels are launched.  The kernels are the library's fifth translation unit (pte_glm.hip, compiled
-// with the flags of pte_langevin.hip): a unit of their own leaves the generated code of the shipped kernels exactly as it was.  Tools and
-// development builds compile pte.hip alone (no -DPTE_SPLIT_LANGEVIN): it then includes the kernels and this entry point itself.
+// the one entry point through which the kernels are launched.  The kernels are a translation unit of their own, pte_glm.hip
+// (pte_automala_params.hpp says why).
 #pragma once
 #include "pte_automala_params.hpp"
 
@@ -23,11 +22,9 @@ struct GlmParams {
 // dynamic LDS of one workgroup (one wave): theta [64 E] then r [n_pad] doubles
 inline size_t glm_lds_bytes(int E, int n_pad) { return sizeof(double) * (size_t)(64 * E + n_pad); }
 
-// one launch of k_explore_glm<E, LIK, slice mode, whole blocks>: N workgroups of one wave on `stream`; `ext`: the launch carries the start /
-// stop events (hipExtLaunchKernelGGL, as LangevinLaunch)
-struct GlmLaunch { int E; int lik; bool slice; bool full; unsigned N; hipStream_t stream; bool ext; hipEvent_t ev_a, ev_b; };
+// one launch of k_explore_glm<E, LIK, slice mode, whole blocks>, one workgroup of one wave per replica
+struct GlmLaunch { int E; int lik; bool slice; bool full; LaunchSite at; };
 int glm_launch(const GlmLaunch &L, const EngineDev &dev, const AmParams &ap, const GlmParams &gp);               // 0, or 1 if this build holds no such kernel
 int glm_refresh_stats(int E, int lik, unsigned N, hipStream_t stream, const EngineDev &dev, const GlmParams &gp, double ref_prec);   // k_refresh_glm_stats<E, LIK>
-int glm_set_rng_policy(unsigned policy);                                                                         // the translation unit's own copy of g_rng_policy (hipError_t as int)
 
 }  // namespace pte

@@ -33,17 +33,11 @@ __global__ __launch_bounds__(64) void k_refresh_mixture_stats(EngineDev e, MixPa
     if (lane == 0) { e.suff[slot] = S; e.suff2[slot] = l2; }
 }
 
-template <typename Kn>
-static inline void mixture_launch_one(Kn kernel, const MixtureLaunch &L, const EngineDev &dev, const AmParams &ap, const MixParams &mp) {
-    if (L.ext) hipExtLaunchKernelGGL(kernel, dim3(L.N), dim3(64), 0, L.stream, L.ev_a, L.ev_b, 0, dev, ap, mp);
-    else hipLaunchKernelGGL(kernel, dim3(L.N), dim3(64), 0, L.stream, dev, ap, mp);
-}
-
 int mixture_launch(const MixtureLaunch &L, const EngineDev &dev, const AmParams &ap, const MixParams &mp) {
 #define MIX_KB(EE, KK)                                                                                          \
-    if (L.slice) mixture_launch_one(k_explore_mixture<EE, KK, true, false>, L, dev, ap, mp);                    \
-    else if (L.full) mixture_launch_one(k_explore_mixture<EE, KK, false, true>, L, dev, ap, mp);                \
-    else mixture_launch_one(k_explore_mixture<EE, KK, false, false>, L, dev, ap, mp);
+    if (L.slice) launch_on(L.at, k_explore_mixture<EE, KK, true, false>, 64, 0, dev, ap, mp);                    \
+    else if (L.full) launch_on(L.at, k_explore_mixture<EE, KK, false, true>, 64, 0, dev, ap, mp);                \
+    else launch_on(L.at, k_explore_mixture<EE, KK, false, false>, 64, 0, dev, ap, mp);
 #define MIX_ONE(EE)                                                                                             \
     switch (mixture_bucket(mp.K)) { case 2: MIX_KB(EE, 2) break; case 4: MIX_KB(EE, 4) break; default: MIX_KB(EE, 8) break; }
     switch (L.E) {
@@ -70,6 +64,6 @@ int mixture_refresh_stats(int E, unsigned N, hipStream_t stream, const EngineDev
     return 0;
 }
 
-int mixture_set_rng_policy(unsigned policy) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_rng_policy), &policy, sizeof policy); }
+PTE_DEFINE_RNG_POLICY_SETTER(mixture)
 
 }  // namespace pte

@@ -3,7 +3,7 @@
 Rounds 3-4 bought their last 15 % with things no correctness test sees: physical registers pinned in asm constraints, an occupancy hint the
 compiler cannot meet chosen for where the scheduler then settles, -amdgpu-sched-strategy=max-ilp, -align-all-nofallthru-blocks=6, -O2 over -O3.
 A ROCm point release -- or an innocent edit of a header -- that puts a spill, a scratch access or a few scalar branches back into a round loop
-costs 5-10 % and every parity test stays green.  This test compiles the product's two translation units to gfx950 assembly with the SHIPPED
+costs 5-10 % and every parity test stays green.  This test compiles the product's translation units to gfx950 assembly with the SHIPPED
 flags (__graft_entry__.FLAGS / UNITS; hipcc cross-compiles without a GPU: about 95 s the first time, cached under build/codegen/ by a hash of
 sources + flags + compiler version) and asserts on what tools/round_loop_lanes.py, tools/spills_by_loop.py and tools/kernel_resources.py print.
 

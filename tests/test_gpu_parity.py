@@ -532,8 +532,8 @@ def test_automala_mvn_parity(P, N, d, rounds, seed):
 
 
 def test_automala_follows_the_rng_policy(P):
-    """libpte is built from two translation units and each holds its own copy of the policy word (include/pte_rng_policy.h;
-    csrc/pte_automala_params.hpp): pte_set_rng_policy must reach the Langevin-family kernels too.  AutoMALA draws ~0.3 M momentum
+    """libpte is built from several translation units (csrc/pte_automala_params.hpp lists them) and each holds its own copy of the policy word (include/pte_rng_policy.h):
+    pte_set_rng_policy must reach the Langevin-family kernels too.  AutoMALA draws ~0.3 M momentum
     normals here, ~100 of them on the ziggurat's tail, whose formula the policy picks: engine == oracle under -log1p(-u), and the
     oracle under the default policy is somewhere else (the switch is live)."""
     from pigeons_amd.engine import set_rng_policy

@@ -4,7 +4,7 @@ tools/spills_by_loop.py and tools/kernel_resources.py print.
 The gains of rounds 3-4 live in places no correctness test sees -- physical registers pinned in asm constraints, an occupancy hint chosen for
 where the scheduler then settles, -amdgpu-sched-strategy=max-ilp, -align-all-nofallthru-blocks=6, -O2 over -O3 -- so a compiler point release (or
 an innocent edit of a header) that puts a spill or a scalar branch back into a round loop costs 5-10 % silently.  This module compiles the product's
-two translation units to gfx950 assembly WITH THE SHIPPED FLAGS (__graft_entry__.FLAGS / UNITS; hipcc cross-compiles without a GPU), caches the
+translation units to gfx950 assembly WITH THE SHIPPED FLAGS (__graft_entry__.FLAGS / UNITS; hipcc cross-compiles without a GPU), caches the
 result under build/codegen/ keyed by a hash of sources + flags + compiler version, and answers:
 
   resources()            per kernel: VGPRs, SGPR / VGPR spills, scratch bytes per lane, LDS, waves per SIMD (hipcc's kernel-resource-usage remarks)
