@@ -48,8 +48,11 @@ enum {
     PTE_TARGET_ISING                = 3, /* InterpolatingPath(Ising(0), Ising(beta)): examples/ising.jl        */
     PTE_TARGET_GAUSSIAN_MIXTURE     = 4, /* InterpolatingPath(normal ref, normalised mixture of K <= 8 diagonal Gaussians;
                                             pte_set_target_mixture): SliceSampler / AutoMALA / MALA / Compose of them, dim <= 512 */
-    PTE_TARGET_BAYESIAN_GLM         = 5  /* InterpolatingPath(normal ref = the prior, prior x GLM likelihood of data X, y;
+    PTE_TARGET_BAYESIAN_GLM         = 5, /* InterpolatingPath(normal ref = the prior, prior x GLM likelihood of data X, y;
                                             pte_set_target_glm): SliceSampler / AutoMALA / MALA / Compose of them, dim <= 512 */
+    PTE_TARGET_MIXTURE_MODEL        = 6  /* InterpolatingPath(normal ref = the prior, prior x likelihood of a K-component normal mixture model
+                                            of data y; pte_set_target_mixture_model): theta = [mu, s, alpha], dim = 3 K, K <= 8;
+                                            SliceSampler / AutoMALA / MALA / Compose of them */
 };
 /* PTE_TARGET_BAYESIAN_GLM: the likelihood of each observation */
 enum {
@@ -236,6 +239,12 @@ int pte_set_target_mixture(pte_engine *h, int64_t n_components, const double *we
  * pte_swap, pte_run_scans, pte_group_run_scans and pte_get_state fail.  stepping_stone estimates log p(y) - (d/2) log(2 pi / p).  DESIGN 4.9. */
 int pte_set_target_glm(pte_engine *h, int32_t likelihood, int64_t n_obs, const double *X /*[n_obs][d]*/, const double *y /*[n_obs]*/,
                        double noise_sd);
+/* PTE_TARGET_MIXTURE_MODEL: the observations of the target N(theta; 0, I / p) prod_i sum_k w_k N(y_i; mu_k, exp(s_k)^2) with
+ * theta = [mu_1..mu_K, s_1..s_K, alpha_1..alpha_K], w = softmax(alpha), K = dim / 3 (p = target_params[0], the reference's precision).
+ * Validates in this order (the engine's target; 1 <= n_obs <= 65536; y not NULL; every y[i] finite), uploads and refreshes the swap
+ * statistics of the current states; may be called again to replace the data.  Until the first call pte_explore, pte_swap, pte_run_scans,
+ * pte_group_run_scans and pte_get_state fail.  stepping_stone estimates log p(y) - (d/2) log(2 pi / p).  DESIGN 4.11. */
+int pte_set_target_mixture_model(pte_engine *h, int64_t n_obs, const double *y /*[n_obs]*/);
 int pte_get_state(const pte_engine *h, double *state, int64_t *chain, uint64_t *rng);
 int pte_set_state(pte_engine *h, const double *state, const int64_t *chain, const uint64_t *rng);
 

@@ -26,11 +26,13 @@
 #include "pte_aaps_params.hpp"
 #include "pte_mixture_params.hpp"
 #include "pte_glm_params.hpp"
+#include "pte_mixture_model_params.hpp"
 #else                              // tools / development builds: one translation unit
 #include "pte_langevin_launch.hpp"
 #include "pte_aaps.hpp"
 #include "pte_mixture.hpp"
 #include "pte_glm.hpp"
+#include "pte_mixture_model.hpp"
 #endif
 #include "pte_ising.hpp"
 #if defined(PTE_PROFILE_AM)               // debug builds only (tools/prof_automala.py): 12 words per wave, section times of k_explore_automala
@@ -95,6 +97,8 @@ struct pte_engine {
     double *d_glm = nullptr;        // PTE_TARGET_BAYESIAN_GLM: Xc [d][n_pad], Xr [n][ld] + 512 zeros, y [n_pad], sized for the largest n of this d
     GlmParams glm{};                // the uploaded data as the kernels read it; glm.n = 0 until pte_set_target_glm
     int glm_lik = 0;
+    double *d_mixmodel = nullptr;   // PTE_TARGET_MIXTURE_MODEL: y [65536], zero-padded
+    MixModelParams mixmodel{};      // the uploaded observations as the kernels read them; mixmodel.n = 0 until pte_set_target_mixture_model
     double step_size = 1.0;
     int am_n_refresh = 0;
     std::vector<double> fac_mean, rev_mean; std::vector<int64_t> fac_n, rev_n;
@@ -221,11 +225,13 @@ struct PathFamily {
 const PathFamily *path_family(int target) {
     static const PathFamily funnel{"funnel", nullptr, nullptr, "one register-resident kernel serves it", "k_explore_automala"},
                             mixture{"Gaussian-mixture", "components", "pte_set_target_mixture", "one register-resident kernel serves it", "k_explore_mixture"},
-                            glm{"Bayesian-GLM", "data", "pte_set_target_glm", "one kernel serves it", "k_explore_glm"};
+                            glm{"Bayesian-GLM", "data", "pte_set_target_glm", "one kernel serves it", "k_explore_glm"},
+                            mixmodel{"mixture-model", "data", "pte_set_target_mixture_model", "one kernel serves it", "k_explore_mixture_model"};
     switch (target) {
     case PTE_TARGET_FUNNEL: return &funnel;
     case PTE_TARGET_GAUSSIAN_MIXTURE: return &mixture;
     case PTE_TARGET_BAYESIAN_GLM: return &glm;
+    case PTE_TARGET_MIXTURE_MODEL: return &mixmodel;
     default: return nullptr;
     }
 }
@@ -235,6 +241,7 @@ bool family_ready(const pte_engine *h) {
     switch (h->cfg.target) {
     case PTE_TARGET_GAUSSIAN_MIXTURE: return h->mix_K > 0;
     case PTE_TARGET_BAYESIAN_GLM: return h->glm.n > 0;
+    case PTE_TARGET_MIXTURE_MODEL: return h->mixmodel.n > 0;
     default: return true;
     }
 }
@@ -256,12 +263,13 @@ MixParams mixture_params(const pte_engine *h) {
 }
 
 // One launch of the engine's AutoMALA / MALA / SliceSampler-on-the-path kernel over N replicas (one workgroup each): the family's own on the
-// mixture and GLM paths, the Langevin family's on the funnel and scaled-precision MVN paths.  The open timing bracket's events ride on it.
+// mixture, GLM and mixture-model paths, the Langevin family's on the funnel and scaled-precision MVN paths.  The open timing bracket's events ride on it.
 int launch_path_kernel(pte_engine *h, int E, bool slice, bool full, int64_t N, const AmParams &ap) {
     const LaunchSite at = launch_site(h, (unsigned)N);
     switch (h->cfg.target) {
     case PTE_TARGET_GAUSSIAN_MIXTURE: return mixture_launch(MixtureLaunch{E, slice, full, at}, h->dev, ap, mixture_params(h)) ? family_no_kernel_error(h) : 0;
     case PTE_TARGET_BAYESIAN_GLM: return glm_launch(GlmLaunch{E, h->glm_lik, slice, full, at}, h->dev, ap, h->glm) ? family_no_kernel_error(h) : 0;
+    case PTE_TARGET_MIXTURE_MODEL: return mixture_model_launch(MixModelLaunch{(int)(h->d / 3), slice, at}, h->dev, ap, h->mixmodel) ? family_no_kernel_error(h) : 0;
     default: break;
     }
     LangevinLaunch L{E, h->cfg.target == PTE_TARGET_FUNNEL ? TGT_FUNNEL : TGT_MVN, slice, full, at};
@@ -279,6 +287,7 @@ int refresh_path_stats(pte_engine *h) {
     case PTE_TARGET_FUNNEL: langevin_refresh_funnel_stats(E, N, h->stream, h->dev, std::log(3.0)); break;
     case PTE_TARGET_GAUSSIAN_MIXTURE: if (mixture_refresh_stats(E, N, h->stream, h->dev, mixture_params(h))) return family_no_kernel_error(h); break;
     case PTE_TARGET_BAYESIAN_GLM: if (glm_refresh_stats(E, h->glm_lik, N, h->stream, h->dev, h->glm, h->cfg.target_params[0])) return family_no_kernel_error(h); break;
+    case PTE_TARGET_MIXTURE_MODEL: if (mixture_model_refresh_stats((int)(h->d / 3), N, h->stream, h->dev, h->mixmodel, h->cfg.target_params[0])) return family_no_kernel_error(h); break;
     default: return 0;
     }
     HIP_OK(h, hipGetLastError());
@@ -967,11 +976,13 @@ int validate_config(const pte_config *cfg) {
         if (cfg->debug_kernel != 0)
             return fail(nullptr, "pte_create: AAPS has one kernel; debug_kernel must be 0 (got %d)", cfg->debug_kernel);
     }
-    if (family && !funnel) {    // the families with kernels of their own -- Gaussian mixture, Bayesian GLM: one wave per replica, SliceSampler / AutoMALA / MALA (AAPS: refused above)
+    if (family && !funnel) {    // the families with kernels of their own -- Gaussian mixture, Bayesian GLM, mixture model: one wave per replica, SliceSampler / AutoMALA / MALA (AAPS: refused above)
         auto on_family = [](int k) { return k == PTE_EXPLORER_SLICE || k == PTE_EXPLORER_AUTOMALA || k == PTE_EXPLORER_MALA; };
         if (!on_family(cfg->explorer) || (cfg->explorer2 != PTE_EXPLORER_NONE && !on_family(cfg->explorer2)))
             return fail(nullptr, "pte_create: the %s path is implemented for SliceSampler / AutoMALA / MALA (and Compose of them) only (got explorers %d, %d)",
                         family->name, cfg->explorer, cfg->explorer2);
+        if (cfg->target == PTE_TARGET_MIXTURE_MODEL && (cfg->dim < 3 || cfg->dim > 24 || cfg->dim % 3 != 0))
+            return fail(nullptr, "pte_create: the mixture-model path holds theta = [mu, s, alpha] of 1..8 components, dim must be in {3, 6, ..., 24} (got %lld)", (long long)cfg->dim);
         if (cfg->dim < 1 || cfg->dim > 512)
             return fail(nullptr, "pte_create: the %s path keeps the replica in the registers of one wave, dim must be in 1..512 (got %lld)", family->name, (long long)cfg->dim);
         if ((cfg->debug_kernel & ~(PTE_KERNEL_FLAG_BITS | PTE_KERNEL_TEST_BITS)) != 0)
@@ -2085,6 +2096,34 @@ int pte_set_target_glm(pte_engine *h, int32_t likelihood, int64_t n_obs, const d
     g.w1 = likelihood == PTE_GLM_NORMAL_IDENTITY ? 1.0 / (noise_sd * noise_sd) : 0.0;
     g.w2 = likelihood == PTE_GLM_NORMAL_IDENTITY ? 1.0 / (2.0 * (noise_sd * noise_sd)) : 0.0;
     h->glm_lik = likelihood;
+    return refresh_path_stats(h);                                  // suff / suff2 of the current states
+}
+
+// The posterior of a finite mixture model.  Host, once per call: c_prior = -(d/2) log(2 pi / p), c_obs = -(n/2) log(2 pi); y is
+// uploaded zero-padded into one allocation sized once for the largest n.
+int pte_set_target_mixture_model(pte_engine *h, int64_t n_obs, const double *y) {
+    if (!h) return 1;
+    PTE_ALIVE(h, "pte_set_target_mixture_model");
+    if (h->cfg.target != PTE_TARGET_MIXTURE_MODEL)
+        return fail(h, "pte_set_target_mixture_model: this engine's target is %d, not PTE_TARGET_MIXTURE_MODEL", h->cfg.target);
+    const int64_t n_max = 65536;
+    if (n_obs < 1 || n_obs > n_max)
+        return fail(h, "pte_set_target_mixture_model: the device holds 1..65536 observations (got %lld)", (long long)n_obs);
+    if (!y) return fail(h, "pte_set_target_mixture_model: null argument");
+    for (int64_t i = 0; i < n_obs; ++i)
+        if (!std::isfinite(y[i])) return fail(h, "pte_set_target_mixture_model: y[%lld] must be finite (got %g)", (long long)i, y[i]);
+    HIP_OK(h, hipSetDevice(h->cfg.device));
+    const int64_t n = n_obs, n_pad = (n + 63) & ~(int64_t)63, d = h->d;
+    std::vector<double> buf((size_t)n_max, 0.0);
+    for (int64_t i = 0; i < n; ++i) buf[(size_t)i] = y[i];
+    if (!h->d_mixmodel && dev_alloc(h, &h->d_mixmodel, buf.size(), false)) return 1;
+    HIP_OK(h, hipMemcpyAsync(h->d_mixmodel, buf.data(), sizeof(double) * buf.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    const double p = h->cfg.target_params[0];
+    MixModelParams &m = h->mixmodel;
+    m.y = h->d_mixmodel; m.n = (int)n; m.n_pad = (int)n_pad; m.nd = (double)n;
+    m.c_prior = -((double)d / 2.0) * std::log(2.0 * M_PI / p);
+    m.c_obs = -((double)n / 2.0) * std::log(2.0 * M_PI);
     return refresh_path_stats(h);                                  // suff / suff2 of the current states
 }
 

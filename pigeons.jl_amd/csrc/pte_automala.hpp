@@ -12,9 +12,12 @@
 //   TGT_MIXTURE the same path with a normalised mixture of KB (or fewer) diagonal Gaussians as the target (pte_mixture.hpp)
 //   TGT_GLM    the same path with prior x likelihood of a Bayesian GLM as the target, LIK = GLM_* (pte_glm.hpp): the one family
 //              that reads data -- through LDS, outside the register-only scheme above
+//   TGT_MIXMODEL the same path with prior x likelihood of a finite mixture model given data y as the target (DESIGN 4.11;
+//              pte_mixture_model.hpp): theta = [mu, s, alpha] in one block, lanes over observations, K <= KB components
 #pragma once
 #include "pte_automala_params.hpp"
 #include "pte_glm_params.hpp"
+#include "pte_mixture_model_params.hpp"
 
 namespace pte {
 
@@ -101,9 +104,12 @@ __device__ __forceinline__ double sqr_norm_regs(const double (&v)[E]) {
 // keeps its layout -- and their instantiations their generated code (a larger AmTarget moved k_explore_aaps<4, TGT_FUNNEL>'s)
 template <bool ON> struct AmGlmData {};
 template <> struct AmGlmData<true> { GlmParams gl; double *glds; };
+// TGT_MIXMODEL's data and its number of components (d / 3): the same arrangement
+template <bool ON> struct AmMixModelData {};
+template <> struct AmMixModelData<true> { MixModelParams mm; int mk; };
 
 template <int E, int TGT, bool FULL = false, int KB = 1, int LIK = 0>
-struct AmTarget : AmGlmData<TGT == TGT_GLM> {
+struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL> {
     int64_t d; int lane;
     double nhp, nprec;          // MVN: -0.5*prec, -prec of this chain
     double beta, omb, ref_nhp, ref_nprec, log3;   // funnel path
@@ -332,9 +338,108 @@ struct AmTarget : AmGlmData<TGT == TGT_GLM> {
         double S, Q, dummy[E];
         return glm_and_sqr_norm<false, false>(x, dummy, S, x, Q);
     }
+    // the mixture model's target log density: target = -(p/2) S + c_prior + sum_i l_i + c_obs, l_i = log sum_k exp(a_ik),
+    // a_ik = b_k - z_ik^2 / 2, z_ik = (y_i - mu_k) e_k.  The parameters of component k sit in lanes k, K + k, 2 K + k of the one block: they
+    // are read from there into scalar registers, and e_k = exp(-s_k), b_k = log w_k - s_k, w_k = softmax(alpha)_k are the same in every lane.
+    // One pass over y with lanes over observations: lane l sums l_i and, GRAD, r_ik, r_ik z_ik, r_ik (z_ik^2 - 1) (r_ik = the responsibilities)
+    // of its own observations in increasing i; the 64 lane sums go over the fixed tree in lockstep with S (and Q), and the totals go back to
+    // lane j for coordinate j.  Components k >= K of the bucket carry alpha = -inf: a_ik = -inf, u_ik = 0.
+    template <bool GRAD, bool WITH_Q>
+    __device__ __forceinline__ double mixmodel_and_sqr_norm(const double (&x)[E], double (&g)[E], double &S, const double (&q)[E], double &Q) const {
+        static_assert(E == 1 || TGT != TGT_MIXMODEL, "d = 3 K <= 24: one block per lane");
+        const MixModelParams &mm = this->mm;
+        const int K = this->mk;
+        double mu[KB], ek[KB], bk[KB], wk[KB], s[KB], al[KB];
+        double am = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < KB; ++k) {
+            const bool on = k < K;
+            const double m_ = readlane_f64(x[0], k), s_ = readlane_f64(x[0], K + k), a_ = readlane_f64(x[0], 2 * K + k);
+            mu[k] = on ? m_ : 0.0; s[k] = on ? s_ : 0.0; al[k] = on ? a_ : -INFINITY;
+            am = (k == 0 || al[k] > am) ? al[k] : am;
+        }
+        double se = 0.0;
+#pragma unroll
+        for (int k = 0; k < KB; ++k) se += exp(al[k] - am);
+        const double A = am + log(se);
+#pragma unroll
+        for (int k = 0; k < KB; ++k) {              // (uniform values: held in scalar registers through the loop over observations)
+            ek[k] = readlane_f64(exp(-s[k]), 0);
+            bk[k] = readlane_f64((al[k] - A) - s[k], 0);
+            wk[k] = exp(al[k] - A);
+        }
+        double ls = 0.0, R[KB], Z1[KB], Z2[KB];
+#pragma unroll
+        for (int k = 0; k < KB; ++k) { R[k] = 0.0; Z1[k] = 0.0; Z2[k] = 0.0; }
+        const double *yp = mm.y + lane;
+#pragma unroll(KB >= 8 ? 1 : 8 / KB)
+        for (int i0 = 0; i0 < mm.n_pad; i0 += 64) {
+            const double yi = yp[i0];
+            const bool ok = i0 + lane < mm.n;       // padded observations contribute exactly 0
+            double z[KB], a[KB], u[KB];
+            double mi = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < KB; ++k) {
+                z[k] = (yi - mu[k]) * ek[k];
+                const double t = bk[k] - (z[k] * z[k]) / 2.0;
+                a[k] = (t != t) ? -INFINITY : t;    // 0 x inf at y_i == mu_k with an overflowed e_k
+                mi = (k == 0 || a[k] > mi) ? a[k] : mi;
+            }
+            const bool dead = mi == -INFINITY;
+            double su = 0.0;
+#pragma unroll
+            for (int k = 0; k < KB; ++k) { u[k] = exp(a[k] - mi); su += u[k]; }
+            const double li = dead ? -INFINITY : mi + log(su);
+            ls = ok ? ls + li : ls;
+            if (GRAD) {
+#pragma unroll
+                for (int k = 0; k < KB; ++k) {
+                    const double r = dead ? 0.0 : u[k] / su;
+                    R[k] = ok ? R[k] + r : R[k];
+                    Z1[k] = ok ? Z1[k] + r * z[k] : Z1[k];
+                    Z2[k] = ok ? Z2[k] + r * (z[k] * z[k] - 1.0) : Z2[k];
+                }
+            }
+        }
+        constexpr int NQ = 2, NG = NQ + (WITH_Q ? 1 : 0), NS = NG + (GRAD ? 3 * KB : 0);
+        double v[NS];
+        v[0] = x[0] * x[0]; v[1] = ls;
+        if (WITH_Q) v[NQ % NS] = q[0] * q[0];
+        if (GRAD) {
+#pragma unroll
+            for (int k = 0; k < KB; ++k) { v[(NG + 3 * k) % NS] = R[k]; v[(NG + 3 * k + 1) % NS] = Z1[k]; v[(NG + 3 * k + 2) % NS] = Z2[k]; }
+        }
+        wave_sum_dpp_multi<NS>(v);
+        S = v[0];
+        if (WITH_Q) Q = v[NQ % NS];
+        const double lp = (((ref_nhp * S) + mm.c_prior) + v[1]) + mm.c_obs;
+        if (GRAD) {
+            double gl = 0.0;
+#pragma unroll
+            for (int k = 0; k < KB; ++k) {
+                if (k >= K) break;
+                gl = lane == k ? ek[k] * v[(NG + 3 * k + 1) % NS] : gl;
+                gl = lane == K + k ? v[(NG + 3 * k + 2) % NS] : gl;
+                gl = lane == 2 * K + k ? v[(NG + 3 * k) % NS] - mm.nd * wk[k] : gl;
+            }
+            g[0] = valid(0) ? (ref_nprec * x[0]) + gl : 0.0;
+        }
+        return lp;
+    }
+    __device__ __forceinline__ double mixmodel(const double (&x)[E]) const {
+        double S, Q, dummy[E];
+        return mixmodel_and_sqr_norm<false, false>(x, dummy, S, x, Q);
+    }
     // log_potentials[chain](x) as a plain callable: InterpolatedLogPotential(x) (src/paths/InterpolatedLogPotential.jl:9-16)
     // WITH its beta == 0 / beta == 1 short-circuits -- what SliceSampler evaluates (the AD form below has none)
     __device__ __forceinline__ double path_lp(const double (&x)[E]) const {
+        if constexpr (TGT == TGT_MIXMODEL) {
+            if (beta == 0.0) return ref_nhp * sqr_norm_regs<E>(x);
+            double S, Q, dummy[E];
+            const double l2 = mixmodel_and_sqr_norm<false, false>(x, dummy, S, x, Q);
+            if (beta == 1.0) return l2;
+            return omb * (ref_nhp * S) + beta * l2;
+        }
         if constexpr (TGT == TGT_GLM) {
             if (beta == 0.0) return ref_nhp * sqr_norm_regs<E>(x);
             double S, Q, dummy[E];
@@ -361,6 +466,10 @@ struct AmTarget : AmGlmData<TGT == TGT_GLM> {
     __device__ __forceinline__ double logdensity(const double (&x)[E]) const {
         if (TGT == TGT_MVN) return nhp * sqr_norm_regs<E>(x);
         double S, l2, dummy[E], dq;
+        if constexpr (TGT == TGT_MIXMODEL) {
+            l2 = mixmodel_and_sqr_norm<false, false>(x, dummy, S, x, dq);
+            return omb * (ref_nhp * S) + beta * l2;
+        }
         if constexpr (TGT == TGT_GLM) {
             l2 = glm_and_sqr_norm<false, false>(x, dummy, S, x, dq);
             return omb * (ref_nhp * S) + beta * l2;
@@ -393,6 +502,14 @@ struct AmTarget : AmGlmData<TGT == TGT_GLM> {
         double logdens = 0.0;
         double g2[E];
         double l2;
+        if constexpr (TGT == TGT_MIXMODEL) {
+            l2 = mixmodel_and_sqr_norm<true, WITH_Q>(x, g2, S, q, Q);
+            logdens += (ref_nhp * S) * omb;
+            logdens += l2 * beta;
+#pragma unroll
+            for (int j = 0; j < E; ++j) g[j] = (ref_nprec * x[j]) * omb + g2[j] * beta;
+            return logdens;
+        }
         if constexpr (TGT == TGT_GLM) {
             l2 = glm_and_sqr_norm<true, WITH_Q>(x, g2, S, q, Q);
             logdens += (ref_nhp * S) * omb;
@@ -446,10 +563,10 @@ __device__ __forceinline__ int64_t am_chain_of_workgroup(int64_t K, int64_t wg) 
 // DIRECT (the scan loop with several chains per workgroup, k_scans_automala_wg): `wg` IS the local chain, and the table staging ends in a
 // wave-level wait instead of a workgroup barrier -- every wave writes all the (identical) entries itself, so it only has to see its own stores
 // KB, mp: TGT_MIXTURE only -- the components' bucket (K <= KB) and parameters.  LIK, gp: TGT_GLM only -- the likelihood and the data
-// (the workgroup's dynamic LDS holds theta and r: pte_glm.hpp)
+// (the workgroup's dynamic LDS holds theta and r: pte_glm.hpp).  mm: TGT_MIXMODEL only -- the observations (pte_mixture_model.hpp)
 template <int E, int TGT, bool SLICE = false, bool FULL = false, bool DIRECT = false, int KB = 1, int LIK = 0>
 __device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const int64_t wg, const MixParams &mp = MixParams{},
-                                              const GlmParams &gp = GlmParams{}) {      // wg: blockIdx.x
+                                              const GlmParams &gp = GlmParams{}, const MixModelParams &mm = MixModelParams{}) {      // wg: blockIdx.x
     constexpr int NLU = (E == 1 ? 0 : E == 2 ? 1 : E == 4 ? 2 : E == 8 ? 3 : 4);
     const int lane = lane_id();
     // the ziggurat tables of the momentum draws, staged once: a global gather per block of draws costs a memory round trip each time
@@ -474,6 +591,7 @@ __device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const in
         extern __shared__ __attribute__((aligned(16))) double glm_lds[];      // after s_wi / s_ki / s_fi (6 KiB: the base stays 16-B aligned)
         T.gl = gp; T.glds = glm_lds;
     }
+    if constexpr (TGT == TGT_MIXMODEL) { T.mm = mm; T.mk = (int)(d / 3); }
     T.nhp = e.nhp[c]; T.nprec = e.nprec[c];
     T.beta = e.beta[c]; T.omb = 1.0 - T.beta;
     T.ref_nhp = -0.5 * ap.ref_prec; T.ref_nprec = -ap.ref_prec; T.log3 = ap.log3;
@@ -518,6 +636,10 @@ __device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const in
         }
         if constexpr (TGT == TGT_GLM) {
             l20 = T.glm(x);
+            if (lane == 0) e.suff2[slot] = l20;
+        }
+        if constexpr (TGT == TGT_MIXMODEL) {
+            l20 = T.mixmodel(x);
             if (lane == 0) e.suff2[slot] = l20;
         }
         record_after_explore_impl(e, cl, c, slot, lane, lp0, S0, l20, l30);
@@ -838,10 +960,11 @@ __device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const in
     if (TGT == TGT_FUNNEL) l2 = T.funnel(x, nullptr);
     if (TGT == TGT_MIXTURE) l2 = T.mixture(x);
     if constexpr (TGT == TGT_GLM) l2 = T.glm(x);
+    if constexpr (TGT == TGT_MIXMODEL) l2 = T.mixmodel(x);
     if (v_on) l3 = T.variational_lp(x);
     if (lane == 0) {
         e.suff[slot] = S;
-        if (TGT == TGT_FUNNEL || TGT == TGT_MIXTURE || TGT == TGT_GLM) e.suff2[slot] = l2;
+        if (TGT == TGT_FUNNEL || TGT == TGT_MIXTURE || TGT == TGT_GLM || TGT == TGT_MIXMODEL) e.suff2[slot] = l2;
         if (v_on) e.suff3[slot] = l3;
         e.rng[2 * slot] = r.seed;
         e.expl_steps_sum[cl] += (double)steps_sum; e.expl_steps_n[cl] += steps_n;

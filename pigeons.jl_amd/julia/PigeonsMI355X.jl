@@ -36,6 +36,7 @@ const libpte = "libpte.so"
 # ---- include/pte.h mirrored ------------------------------------------------------------------------------------------------
 const TARGET_MVN, TARGET_TEST_SWAPPER, TARGET_FUNNEL, TARGET_ISING, TARGET_GAUSSIAN_MIXTURE = Int32(0), Int32(1), Int32(2), Int32(3), Int32(4)
 const TARGET_BAYESIAN_GLM = Int32(5)
+const TARGET_MIXTURE_MODEL = Int32(6)
 const GLM_BERNOULLI_LOGIT, GLM_NORMAL_IDENTITY = Int32(0), Int32(1)
 const EXPLORER_NONE, EXPLORER_TOY, EXPLORER_SLICE, EXPLORER_AUTOMALA, EXPLORER_ISING, EXPLORER_MALA, EXPLORER_AAPS = Int32.((0, 1, 2, 3, 4, 5, 6))
 const RECORD_ROUND_TRIP, RECORD_INDEX_PROCESS, RECORD_ONLINE, RECORD_TRACES, RECORD_ENERGY_AC1, RECORD_TRACES_EXTENDED =
@@ -112,6 +113,12 @@ regression with known `noise_sd`).  X is n x dim.  Used as `Inputs(target = on_m
 reference = ScaledPrecisionNormalLogPotential(p, dim))` -- the reference is the prior.  stepping_stone(pt) + (dim/2) log(2 pi / p) is the
 log evidence."""
 struct DeviceBayesianGLM; X::Matrix{Float64}; y::Vector{Float64}; likelihood::Symbol; noise_sd::Float64; end
+"""The posterior of a finite mixture model given data, the device family PTE_TARGET_MIXTURE_MODEL (DESIGN 4.11): `y` holds n real
+observations of a mixture of `n_components` normals (K <= 8); the state is [mu; s; alpha] (dim = 3 K) with standard deviations exp.(s)
+and weights softmax(alpha), and the prior N(0, I / p).  Used as `Inputs(target = on_mi355x(DeviceMixtureModelPosterior(y, 2)),
+reference = ScaledPrecisionNormalLogPotential(p, 6))` -- the reference is the prior.  stepping_stone(pt) + (dim/2) log(2 pi / p) is the
+log evidence."""
+struct DeviceMixtureModelPosterior; y::Vector{Float64}; n_components::Int; end
 
 # (target code, dim, target_params, reference precision check) of a wrapped target
 device_family(t::ScaledPrecisionNormalPath, inputs) = (TARGET_MVN, t.dim, (t.precision0, t.precision1, 0.0, 0.0))
@@ -139,6 +146,15 @@ function device_family(t::DeviceBayesianGLM, inputs)
     ref isa ScaledPrecisionNormalLogPotential && ref.dim == dim ||
         error("the device Bayesian-GLM path needs reference = ScaledPrecisionNormalLogPotential(precision, $dim) (the prior); keep the CPU path otherwise")
     return (TARGET_BAYESIAN_GLM, dim, (ref.precision, 0.0, 0.0, 0.0))
+end
+function device_family(t::DeviceMixtureModelPosterior, inputs)
+    1 <= t.n_components <= 8 || error("DeviceMixtureModelPosterior: the device holds 1..8 components")
+    1 <= length(t.y) <= 65536 || error("DeviceMixtureModelPosterior: the device holds 1..65536 observations")
+    dim = 3 * t.n_components
+    ref = inputs.reference
+    ref isa ScaledPrecisionNormalLogPotential && ref.dim == dim ||
+        error("the device mixture-model path needs reference = ScaledPrecisionNormalLogPotential(precision, $dim) (the prior); keep the CPU path otherwise")
+    return (TARGET_MIXTURE_MODEL, dim, (ref.precision, 0.0, 0.0, 0.0))
 end
 device_family(t, inputs) = error("target $(typeof(t)) has no device log-potential family (closed set: include/pte.h PTE_TARGET_*); keep the CPU path")
 
@@ -257,6 +273,9 @@ function Pigeons.create_replicas(inputs::Inputs{<:OnDevice}, shared::Shared, sou
         lik = g.likelihood === :normal_identity ? GLM_NORMAL_IDENTITY : GLM_BERNOULLI_LOGIT
         check(r, ccall((:pte_set_target_glm, libpte), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Float64),
                        r.handle, lik, length(g.y), collect(vec(permutedims(g.X))), g.y, g.noise_sd))
+    end
+    if t.target isa DeviceMixtureModelPosterior     # the observations as pte_set_target_mixture_model reads them
+        check(r, ccall((:pte_set_target_mixture_model, libpte), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}), r.handle, length(t.target.y), t.target.y))
     end
     source === nothing || restore!(r, source)          # FromCheckpoint: pte_set_state from the deserialised Replica structs
     return r

@@ -101,6 +101,11 @@ class Engine:
             raise ValueError("set_target_glm: X must be n x %d with n = len(y) = %d (got shape %s)" % (self.d, ya.size, Xa.shape))
         self._chk(self.L.pte_set_target_glm(self.h, int(likelihood), ya.size, _dp(Xa), _dp(ya), float(noise_sd)))
 
+    def set_target_mixture_model(self, y):
+        """pte_set_target_mixture_model: the observations y [n]"""
+        ya = np.ascontiguousarray(y, dtype=np.float64).ravel()
+        self._chk(self.L.pte_set_target_mixture_model(self.h, ya.size, _dp(ya)))
+
     # --- hot path
     def explore(self, scan):
         self._chk(self.L.pte_explore(self.h, scan))

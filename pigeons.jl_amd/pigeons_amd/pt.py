@@ -162,6 +162,42 @@ class BayesianGLM:
         return "BayesianGLM(%s, n=%d, dim=%d)" % (self.likelihood, self.n_obs, self.dim)
 
 
+class MixtureModelPosterior:
+    """The posterior of a finite mixture model given data, the device's label-switching target: n real observations y_i from
+    a mixture of K = n_components normals (1 <= K <= 8, 1 <= n <= 65536), with the state
+        theta = [mu_1..mu_K, s_1..s_K, alpha_1..alpha_K]        (d = 3 K)
+    component k having mean mu_k, standard deviation exp(s_k) and weight softmax(alpha)_k, and the prior N(0, I / p) on theta (standardise
+    y).  Every relabelling of the components has the same posterior density: K! symmetric modes.  Tempered through the default
+    InterpolatingPath(reference, target) (src/targets/target.jl:72-75) from reference=ScaledPrecisionNormalLogPotential(p, d) -- the prior,
+    unnormalised -- to prior x likelihood with the prior normalised; initialization = zeros(d); default explorer SliceSampler (target.jl:20).
+
+    Evidence: stepping_stone(pt) estimates log Z1 / Z0 = log p(y) - (d/2) log(2 pi / p), so the log evidence (marginal likelihood) is
+    stepping_stone(pt) + (d/2) log(2 pi / p)."""
+
+    def __init__(self, y, n_components):
+        y = np.array(y, dtype=np.float64)
+        if isinstance(n_components, bool) or int(n_components) != n_components or not 1 <= int(n_components) <= 8:
+            raise ValueError("MixtureModelPosterior: the device holds 1..8 components (got %r)" % (n_components,))
+        if y.ndim != 1:
+            raise ValueError("MixtureModelPosterior: y must be a vector of real observations")
+        if y.size < 1 or y.size > 65536:
+            raise ValueError("MixtureModelPosterior: the device holds 1..65536 observations (got %d)" % y.size)
+        if not np.all(np.isfinite(y)):
+            raise ValueError("MixtureModelPosterior: y[%d] must be finite" % int(np.flatnonzero(~np.isfinite(y))[0]))
+        self.y, self.n_components = y, int(n_components)
+
+    @property
+    def n_obs(self):
+        return self.y.size
+
+    @property
+    def dim(self):
+        return 3 * self.n_components
+
+    def __repr__(self):
+        return "MixtureModelPosterior(n=%d, K=%d)" % (self.n_obs, self.n_components)
+
+
 @dataclass
 class GaussianReference:
     """src/variational/GaussianReference.jl:4-17: mean-field Gaussian variational reference, refitted every round from
@@ -476,6 +512,11 @@ class PT:
             if not isinstance(ref, ScaledPrecisionNormalLogPotential) or ref.dim != target.dim:
                 raise NotImplementedError("the device Bayesian-GLM path needs reference=ScaledPrecisionNormalLogPotential(prec, dim) -- the prior")
             kw.update(target=_lib.TARGET_BAYESIAN_GLM, dim=target.dim, target_params=[ref.precision])
+        elif isinstance(target, MixtureModelPosterior):
+            ref = inputs.reference
+            if not isinstance(ref, ScaledPrecisionNormalLogPotential) or ref.dim != target.dim:
+                raise NotImplementedError("the device mixture-model path needs reference=ScaledPrecisionNormalLogPotential(prec, dim) -- the prior")
+            kw.update(target=_lib.TARGET_MIXTURE_MODEL, dim=target.dim, target_params=[ref.precision])
         else:
             raise NotImplementedError(
                 "target %r has no device log-potential; use the reference CPU path (Pigeons.jl)" % (target,))
@@ -540,6 +581,9 @@ class PT:
         if isinstance(target, BayesianGLM):              # every engine (rank) holds the data
             for eng in (self.shards.engines if hasattr(self.shards, "engines") else [self.replicas]):
                 eng.set_target_glm(target.likelihood_code, target.X, target.y, target.noise_sd)
+        if isinstance(target, MixtureModelPosterior):    # every engine (rank) holds the observations
+            for eng in (self.shards.engines if hasattr(self.shards, "engines") else [self.replicas]):
+                eng.set_target_mixture_model(target.y)
 
 
 def next_round(pt):
