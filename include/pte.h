@@ -50,9 +50,12 @@ enum {
                                             pte_set_target_mixture): SliceSampler / AutoMALA / MALA / Compose of them, dim <= 512 */
     PTE_TARGET_BAYESIAN_GLM         = 5, /* InterpolatingPath(normal ref = the prior, prior x GLM likelihood of data X, y;
                                             pte_set_target_glm): SliceSampler / AutoMALA / MALA / Compose of them, dim <= 512 */
-    PTE_TARGET_MIXTURE_MODEL        = 6  /* InterpolatingPath(normal ref = the prior, prior x likelihood of a K-component normal mixture model
+    PTE_TARGET_MIXTURE_MODEL        = 6, /* InterpolatingPath(normal ref = the prior, prior x likelihood of a K-component normal mixture model
                                             of data y; pte_set_target_mixture_model): theta = [mu, s, alpha], dim = 3 K, K <= 8;
                                             SliceSampler / AutoMALA / MALA / Compose of them */
+    PTE_TARGET_VARIABLE_SELECTION = 7    /* spike-and-slab regression on data X, y (pte_set_target_varsel): the state is [theta, gamma],
+                                            d Float64 coefficients then d Bool indicators stored as 0.0 / 1.0, dim = 2 d, d <= 256;
+                                            SliceSampler only (its Float64 and Bool coordinate methods) */
 };
 /* PTE_TARGET_BAYESIAN_GLM: the likelihood of each observation */
 enum {
@@ -245,6 +248,15 @@ int pte_set_target_glm(pte_engine *h, int32_t likelihood, int64_t n_obs, const d
  * statistics of the current states; may be called again to replace the data.  Until the first call pte_explore, pte_swap, pte_run_scans,
  * pte_group_run_scans and pte_get_state fail.  stepping_stone estimates log p(y) - (d/2) log(2 pi / p).  DESIGN 4.11. */
 int pte_set_target_mixture_model(pte_engine *h, int64_t n_obs, const double *y /*[n_obs]*/);
+/* PTE_TARGET_VARIABLE_SELECTION: the data of the target N(theta; 0, I / p) prod_j pi^gamma_j (1 - pi)^(1 - gamma_j)
+ * prod_i p(y_i | eta_i = sum_j X[i][j] gamma_j theta_j) (p = target_params[0], the reference's precision; pi = inclusion_prob; X row-major
+ * [n_obs][d] with d = dim / 2; likelihood PTE_GLM_*, noise_sd read by PTE_GLM_NORMAL_IDENTITY only).  Validates as pte_set_target_glm does
+ * (the likelihood; d == dim / 2; 1 <= n_obs <= 4096 and n_obs * d <= 131072; X and y finite; y in {0, 1} for the logit; noise_sd positive
+ * and finite for the normal), then inclusion_prob in (0, 1); uploads and refreshes the swap statistics of the current states; may be called
+ * again to replace the data.  Until the first call pte_explore, pte_swap, pte_run_scans, pte_group_run_scans and pte_get_state fail.
+ * stepping_stone estimates log p(y) - (d/2) log(2 pi / p) - d log 2 (the reference is uniform on the 2^d indicator vectors).  DESIGN 4.12. */
+int pte_set_target_varsel(pte_engine *h, const double *X /*[n_obs][d]*/, const double *y /*[n_obs]*/, int64_t n_obs, int64_t d,
+                          int32_t likelihood, double noise_sd, double inclusion_prob);
 int pte_get_state(const pte_engine *h, double *state, int64_t *chain, uint64_t *rng);
 int pte_set_state(pte_engine *h, const double *state, const int64_t *chain, const uint64_t *rng);
 

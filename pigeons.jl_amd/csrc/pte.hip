@@ -27,12 +27,14 @@
 #include "pte_mixture_params.hpp"
 #include "pte_glm_params.hpp"
 #include "pte_mixture_model_params.hpp"
+#include "pte_varsel_params.hpp"
 #else                              // tools / development builds: one translation unit
 #include "pte_langevin_launch.hpp"
 #include "pte_aaps.hpp"
 #include "pte_mixture.hpp"
 #include "pte_glm.hpp"
 #include "pte_mixture_model.hpp"
+#include "pte_varsel.hpp"
 #endif
 #include "pte_ising.hpp"
 #if defined(PTE_PROFILE_AM)               // debug builds only (tools/prof_automala.py): 12 words per wave, section times of k_explore_automala
@@ -99,6 +101,9 @@ struct pte_engine {
     int glm_lik = 0;
     double *d_mixmodel = nullptr;   // PTE_TARGET_MIXTURE_MODEL: y [65536], zero-padded
     MixModelParams mixmodel{};      // the uploaded observations as the kernels read them; mixmodel.n = 0 until pte_set_target_mixture_model
+    double *d_varsel = nullptr;     // PTE_TARGET_VARIABLE_SELECTION: Xc [d][n_pad], y [n_pad], sized for the largest n of this d
+    VarselParams varsel{};          // the uploaded data as the kernels read it; varsel.n = 0 until pte_set_target_varsel
+    int varsel_lik = 0;
     double step_size = 1.0;
     int am_n_refresh = 0;
     std::vector<double> fac_mean, rev_mean; std::vector<int64_t> fac_n, rev_n;
@@ -226,12 +231,14 @@ const PathFamily *path_family(int target) {
     static const PathFamily funnel{"funnel", nullptr, nullptr, "one register-resident kernel serves it", "k_explore_automala"},
                             mixture{"Gaussian-mixture", "components", "pte_set_target_mixture", "one register-resident kernel serves it", "k_explore_mixture"},
                             glm{"Bayesian-GLM", "data", "pte_set_target_glm", "one kernel serves it", "k_explore_glm"},
-                            mixmodel{"mixture-model", "data", "pte_set_target_mixture_model", "one kernel serves it", "k_explore_mixture_model"};
+                            mixmodel{"mixture-model", "data", "pte_set_target_mixture_model", "one kernel serves it", "k_explore_mixture_model"},
+                            varsel{"variable-selection", "data", "pte_set_target_varsel", "one kernel serves it", "k_explore_varsel"};
     switch (target) {
     case PTE_TARGET_FUNNEL: return &funnel;
     case PTE_TARGET_GAUSSIAN_MIXTURE: return &mixture;
     case PTE_TARGET_BAYESIAN_GLM: return &glm;
     case PTE_TARGET_MIXTURE_MODEL: return &mixmodel;
+    case PTE_TARGET_VARIABLE_SELECTION: return &varsel;
     default: return nullptr;
     }
 }
@@ -242,6 +249,7 @@ bool family_ready(const pte_engine *h) {
     case PTE_TARGET_GAUSSIAN_MIXTURE: return h->mix_K > 0;
     case PTE_TARGET_BAYESIAN_GLM: return h->glm.n > 0;
     case PTE_TARGET_MIXTURE_MODEL: return h->mixmodel.n > 0;
+    case PTE_TARGET_VARIABLE_SELECTION: return h->varsel.n > 0;
     default: return true;
     }
 }
@@ -270,6 +278,8 @@ int launch_path_kernel(pte_engine *h, int E, bool slice, bool full, int64_t N, c
     case PTE_TARGET_GAUSSIAN_MIXTURE: return mixture_launch(MixtureLaunch{E, slice, full, at}, h->dev, ap, mixture_params(h)) ? family_no_kernel_error(h) : 0;
     case PTE_TARGET_BAYESIAN_GLM: return glm_launch(GlmLaunch{E, h->glm_lik, slice, full, at}, h->dev, ap, h->glm) ? family_no_kernel_error(h) : 0;
     case PTE_TARGET_MIXTURE_MODEL: return mixture_model_launch(MixModelLaunch{(int)(h->d / 3), slice, at}, h->dev, ap, h->mixmodel) ? family_no_kernel_error(h) : 0;
+    case PTE_TARGET_VARIABLE_SELECTION:      // SliceSampler alone (validate_config); whole blocks: 2 d == 64 E
+        return varsel_launch(VarselLaunch{E, h->varsel_lik, h->d == 64 * (int64_t)E, at}, h->dev, ap, h->varsel) ? family_no_kernel_error(h) : 0;
     default: break;
     }
     LangevinLaunch L{E, h->cfg.target == PTE_TARGET_FUNNEL ? TGT_FUNNEL : TGT_MVN, slice, full, at};
@@ -288,6 +298,7 @@ int refresh_path_stats(pte_engine *h) {
     case PTE_TARGET_GAUSSIAN_MIXTURE: if (mixture_refresh_stats(E, N, h->stream, h->dev, mixture_params(h))) return family_no_kernel_error(h); break;
     case PTE_TARGET_BAYESIAN_GLM: if (glm_refresh_stats(E, h->glm_lik, N, h->stream, h->dev, h->glm, h->cfg.target_params[0])) return family_no_kernel_error(h); break;
     case PTE_TARGET_MIXTURE_MODEL: if (mixture_model_refresh_stats((int)(h->d / 3), N, h->stream, h->dev, h->mixmodel, h->cfg.target_params[0])) return family_no_kernel_error(h); break;
+    case PTE_TARGET_VARIABLE_SELECTION: if (varsel_refresh_stats(E, h->varsel_lik, N, h->stream, h->dev, h->varsel, h->cfg.target_params[0])) return family_no_kernel_error(h); break;
     default: return 0;
     }
     HIP_OK(h, hipGetLastError());
@@ -975,6 +986,15 @@ int validate_config(const pte_config *cfg) {
             return fail(nullptr, "pte_create: AAPS needs a positive finite step size (got %g)", cfg->am_step_size);
         if (cfg->debug_kernel != 0)
             return fail(nullptr, "pte_create: AAPS has one kernel; debug_kernel must be 0 (got %d)", cfg->debug_kernel);
+    }
+    if (cfg->target == PTE_TARGET_VARIABLE_SELECTION) {      // Float64 and Bool coordinates, SliceSampler's two methods and nothing else
+        if (cfg->explorer != PTE_EXPLORER_SLICE || cfg->explorer2 != PTE_EXPLORER_NONE)
+            return fail(nullptr, "pte_create: the variable-selection path is explored by SliceSampler only -- its Bool coordinates have no gradient, "
+                                 "and no Compose (got explorers %d, %d)", cfg->explorer, cfg->explorer2);
+        if (cfg->dim % 2 != 0)
+            return fail(nullptr, "pte_create: the variable-selection path holds [theta, gamma] of d columns, dim = 2 d must be even (got %lld)", (long long)cfg->dim);
+        if (cfg->dim < 2 || cfg->dim > 512)
+            return fail(nullptr, "pte_create: the variable-selection path keeps the replica in the registers of one wave, d = dim / 2 must be in 1..256 (got dim %lld)", (long long)cfg->dim);
     }
     if (family && !funnel) {    // the families with kernels of their own -- Gaussian mixture, Bayesian GLM, mixture model: one wave per replica, SliceSampler / AutoMALA / MALA (AAPS: refused above)
         auto on_family = [](int k) { return k == PTE_EXPLORER_SLICE || k == PTE_EXPLORER_AUTOMALA || k == PTE_EXPLORER_MALA; };
@@ -2124,6 +2144,61 @@ int pte_set_target_mixture_model(pte_engine *h, int64_t n_obs, const double *y) 
     m.y = h->d_mixmodel; m.n = (int)n; m.n_pad = (int)n_pad; m.nd = (double)n;
     m.c_prior = -((double)d / 2.0) * std::log(2.0 * M_PI / p);
     m.c_obs = -((double)n / 2.0) * std::log(2.0 * M_PI);
+    return refresh_path_stats(h);                                  // suff / suff2 of the current states
+}
+
+// Variable selection.  Host, once per call: the GLM's constants with d = dim / 2 columns -- c_prior = -(d/2) log(2 pi / p),
+// c_obs = 0 (logit) or -n (log sigma + log(2 pi) / 2) (normal), 1 / (2 sigma^2) -- and log pi, log(1 - pi); uploaded as Xc [d][n_pad]
+// (column-major) and y [n_pad], zero-padded, into one allocation sized once for the largest n this d admits.
+int pte_set_target_varsel(pte_engine *h, const double *X, const double *y, int64_t n_obs, int64_t d, int32_t likelihood, double noise_sd,
+                          double inclusion_prob) {
+    if (!h) return 1;
+    PTE_ALIVE(h, "pte_set_target_varsel");
+    if (h->cfg.target != PTE_TARGET_VARIABLE_SELECTION)
+        return fail(h, "pte_set_target_varsel: this engine's target is %d, not PTE_TARGET_VARIABLE_SELECTION", h->cfg.target);
+    if (likelihood != PTE_GLM_BERNOULLI_LOGIT && likelihood != PTE_GLM_NORMAL_IDENTITY)
+        return fail(h, "pte_set_target_varsel: likelihood must be PTE_GLM_BERNOULLI_LOGIT (0) or PTE_GLM_NORMAL_IDENTITY (1) (got %d)", likelihood);
+    if (2 * d != h->d)
+        return fail(h, "pte_set_target_varsel: this engine holds dim / 2 = %lld columns (got %lld)", (long long)(h->d / 2), (long long)d);
+    if (n_obs < 1 || n_obs > 4096)
+        return fail(h, "pte_set_target_varsel: the device holds 1..4096 observations (got %lld)", (long long)n_obs);
+    if (n_obs * d > 131072)
+        return fail(h, "pte_set_target_varsel: n_obs * d must be <= 131072 (got %lld * %lld)", (long long)n_obs, (long long)d);
+    if (!X || !y) return fail(h, "pte_set_target_varsel: null argument");
+    for (int64_t i = 0; i < n_obs; ++i) {
+        for (int64_t j = 0; j < d; ++j)
+            if (!std::isfinite(X[i * d + j]))
+                return fail(h, "pte_set_target_varsel: X[%lld][%lld] must be finite (got %g)", (long long)i, (long long)j, X[i * d + j]);
+        if (!std::isfinite(y[i])) return fail(h, "pte_set_target_varsel: y[%lld] must be finite (got %g)", (long long)i, y[i]);
+        if (likelihood == PTE_GLM_BERNOULLI_LOGIT && y[i] != 0.0 && y[i] != 1.0)
+            return fail(h, "pte_set_target_varsel: the Bernoulli-logit likelihood needs y in {0, 1} (y[%lld] = %g)", (long long)i, y[i]);
+    }
+    if (likelihood == PTE_GLM_NORMAL_IDENTITY && (!(noise_sd > 0) || !std::isfinite(noise_sd)))
+        return fail(h, "pte_set_target_varsel: the normal-identity likelihood needs noise_sd positive and finite (got %g)", noise_sd);
+    if (!(inclusion_prob > 0.0 && inclusion_prob < 1.0))
+        return fail(h, "pte_set_target_varsel: inclusion_prob must be in (0, 1) (got %g)", inclusion_prob);
+    HIP_OK(h, hipSetDevice(h->cfg.device));
+    const int64_t n = n_obs, n_pad = (n + 63) & ~(int64_t)63;
+    const int64_t n_max = std::min<int64_t>(4096, 131072 / d), n_pad_max = (n_max + 63) & ~(int64_t)63;
+    const int64_t xc_len = d * n_pad_max;
+    std::vector<double> buf((size_t)(xc_len + n_pad_max), 0.0);
+    double *xc = buf.data(), *yy = xc + xc_len;
+    for (int64_t i = 0; i < n; ++i) {
+        for (int64_t j = 0; j < d; ++j) xc[j * n_pad + i] = X[i * d + j];
+        yy[i] = y[i];
+    }
+    const double p = h->cfg.target_params[0], LOG2PI = 1.8378770664093453;
+    if (!h->d_varsel && dev_alloc(h, &h->d_varsel, buf.size(), false)) return 1;
+    HIP_OK(h, hipMemcpyAsync(h->d_varsel, buf.data(), sizeof(double) * buf.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    VarselParams &v = h->varsel;
+    v.xc = h->d_varsel; v.y = h->d_varsel + xc_len;
+    v.n = (int)n; v.n_pad = (int)n_pad; v.d = (int)d;
+    v.c_prior = -((double)d / 2.0) * std::log(2.0 * M_PI / p);
+    v.c_obs = likelihood == PTE_GLM_NORMAL_IDENTITY ? -(double)n * (std::log(noise_sd) + 0.5 * LOG2PI) : 0.0;
+    v.w2 = likelihood == PTE_GLM_NORMAL_IDENTITY ? 1.0 / (2.0 * (noise_sd * noise_sd)) : 0.0;
+    v.log_pi = std::log(inclusion_prob); v.log_1mpi = std::log(1.0 - inclusion_prob);
+    h->varsel_lik = likelihood;
     return refresh_path_stats(h);                                  // suff / suff2 of the current states
 }
 

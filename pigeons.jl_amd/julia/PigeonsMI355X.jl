@@ -37,6 +37,7 @@ const libpte = "libpte.so"
 const TARGET_MVN, TARGET_TEST_SWAPPER, TARGET_FUNNEL, TARGET_ISING, TARGET_GAUSSIAN_MIXTURE = Int32(0), Int32(1), Int32(2), Int32(3), Int32(4)
 const TARGET_BAYESIAN_GLM = Int32(5)
 const TARGET_MIXTURE_MODEL = Int32(6)
+const TARGET_VARIABLE_SELECTION = Int32(7)
 const GLM_BERNOULLI_LOGIT, GLM_NORMAL_IDENTITY = Int32(0), Int32(1)
 const EXPLORER_NONE, EXPLORER_TOY, EXPLORER_SLICE, EXPLORER_AUTOMALA, EXPLORER_ISING, EXPLORER_MALA, EXPLORER_AAPS = Int32.((0, 1, 2, 3, 4, 5, 6))
 const RECORD_ROUND_TRIP, RECORD_INDEX_PROCESS, RECORD_ONLINE, RECORD_TRACES, RECORD_ENERGY_AC1, RECORD_TRACES_EXTENDED =
@@ -119,6 +120,13 @@ and weights softmax(alpha), and the prior N(0, I / p).  Used as `Inputs(target =
 reference = ScaledPrecisionNormalLogPotential(p, 6))` -- the reference is the prior.  stepping_stone(pt) + (dim/2) log(2 pi / p) is the
 log evidence."""
 struct DeviceMixtureModelPosterior; y::Vector{Float64}; n_components::Int; end
+"""Bayesian variable selection, a spike-and-slab regression: the device family PTE_TARGET_VARIABLE_SELECTION (DESIGN 4.12).  The data and
+likelihoods of DeviceBayesianGLM (X is n x d) with an inclusion indicator per column: the state is [theta; gamma] (dim = 2 d, gamma stored as
+0.0 / 1.0), eta = X * (gamma .* theta), prior N(0, I / p) on theta and Bernoulli(`inclusion_prob`) on every gamma_j.  Used as
+`Inputs(target = on_mi355x(DeviceSpikeSlabRegression(X, y, :normal_identity, 1.0, 0.5)), reference = ScaledPrecisionNormalLogPotential(p, d),
+explorer = SliceSampler())` -- SliceSampler is the one explorer of this family.  stepping_stone(pt) + (d/2) log(2 pi / p) + d log 2 is the
+log evidence."""
+struct DeviceSpikeSlabRegression; X::Matrix{Float64}; y::Vector{Float64}; likelihood::Symbol; noise_sd::Float64; inclusion_prob::Float64; end
 
 # (target code, dim, target_params, reference precision check) of a wrapped target
 device_family(t::ScaledPrecisionNormalPath, inputs) = (TARGET_MVN, t.dim, (t.precision0, t.precision1, 0.0, 0.0))
@@ -155,6 +163,17 @@ function device_family(t::DeviceMixtureModelPosterior, inputs)
     ref isa ScaledPrecisionNormalLogPotential && ref.dim == dim ||
         error("the device mixture-model path needs reference = ScaledPrecisionNormalLogPotential(precision, $dim) (the prior); keep the CPU path otherwise")
     return (TARGET_MIXTURE_MODEL, dim, (ref.precision, 0.0, 0.0, 0.0))
+end
+function device_family(t::DeviceSpikeSlabRegression, inputs)
+    n, d = size(t.X)
+    length(t.y) == n || error("DeviceSpikeSlabRegression: X is n x d, y has the n observations")
+    t.likelihood in (:bernoulli_logit, :normal_identity) || error("DeviceSpikeSlabRegression: likelihood :bernoulli_logit or :normal_identity")
+    1 <= d <= 256 || error("DeviceSpikeSlabRegression: the device holds 1..256 columns")
+    0 < t.inclusion_prob < 1 || error("DeviceSpikeSlabRegression: inclusion_prob must be in (0, 1)")
+    ref = inputs.reference
+    ref isa ScaledPrecisionNormalLogPotential && ref.dim == d ||
+        error("the device variable-selection path needs reference = ScaledPrecisionNormalLogPotential(precision, $d) (the prior of the coefficients); keep the CPU path otherwise")
+    return (TARGET_VARIABLE_SELECTION, 2 * d, (ref.precision, 0.0, 0.0, 0.0))
 end
 device_family(t, inputs) = error("target $(typeof(t)) has no device log-potential family (closed set: include/pte.h PTE_TARGET_*); keep the CPU path")
 
@@ -276,6 +295,12 @@ function Pigeons.create_replicas(inputs::Inputs{<:OnDevice}, shared::Shared, sou
     end
     if t.target isa DeviceMixtureModelPosterior     # the observations as pte_set_target_mixture_model reads them
         check(r, ccall((:pte_set_target_mixture_model, libpte), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}), r.handle, length(t.target.y), t.target.y))
+    end
+    if t.target isa DeviceSpikeSlabRegression       # the data, X row-major [n][d] as pte_set_target_varsel reads it
+        g = t.target
+        lik = g.likelihood === :normal_identity ? GLM_NORMAL_IDENTITY : GLM_BERNOULLI_LOGIT
+        check(r, ccall((:pte_set_target_varsel, libpte), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int32, Float64, Float64),
+                       r.handle, collect(vec(permutedims(g.X))), g.y, length(g.y), size(g.X, 2), lik, g.noise_sd, g.inclusion_prob))
     end
     source === nothing || restore!(r, source)          # FromCheckpoint: pte_set_state from the deserialised Replica structs
     return r

@@ -106,6 +106,15 @@ class Engine:
         ya = np.ascontiguousarray(y, dtype=np.float64).ravel()
         self._chk(self.L.pte_set_target_mixture_model(self.h, ya.size, _dp(ya)))
 
+    def set_target_varsel(self, likelihood, X, y, noise_sd=1.0, inclusion_prob=0.5):
+        """pte_set_target_varsel: likelihood GLM_*, X [n][d] (row-major, d = dim / 2), y [n]"""
+        Xa = np.ascontiguousarray(X, dtype=np.float64)
+        ya = np.ascontiguousarray(y, dtype=np.float64).ravel()
+        if Xa.ndim != 2 or Xa.shape[0] != ya.size:
+            raise ValueError("set_target_varsel: X must be n x d with n = len(y) = %d (got shape %s)" % (ya.size, Xa.shape))
+        self._chk(self.L.pte_set_target_varsel(self.h, _dp(Xa), _dp(ya), ya.size, Xa.shape[1], int(likelihood), float(noise_sd),
+                                               float(inclusion_prob)))
+
     # --- hot path
     def explore(self, scan):
         self._chk(self.L.pte_explore(self.h, scan))

@@ -198,6 +198,56 @@ class MixtureModelPosterior:
         return "MixtureModelPosterior(n=%d, K=%d)" % (self.n_obs, self.n_components)
 
 
+class SpikeSlabRegression:
+    """Bayesian variable selection, a spike-and-slab regression: the data of BayesianGLM (X: n x d, y: n, the same two
+    likelihoods) with an inclusion indicator per column.  The state is
+        [theta_0..theta_{d-1}, gamma_0..gamma_{d-1}]            (dim = 2 d; theta Float64, gamma Bool stored as 0.0 / 1.0)
+    the linear predictor eta_i = sum_j X[i][j] gamma_j theta_j, the prior N(0, I / p) on theta and Bernoulli(inclusion_prob) on every gamma_j
+    (1 <= d <= 256, 1 <= n <= 4096, n d <= 131072).  Tempered from reference=ScaledPrecisionNormalLogPotential(p, d) on theta -- the
+    prior, unnormalised -- times the uniform distribution on gamma, to prior x likelihood; initialization = zeros(2 d).  The explorer is
+    SliceSampler (target.jl:20) and nothing else: its Float64 method on the thetas, its Bool method on the gammas.
+
+    Evidence: stepping_stone(pt) estimates log p(y) - (d/2) log(2 pi / p) - d log 2 (the reference has mass (2 pi / p)^(d/2) 2^d), so the
+    log evidence is stepping_stone(pt) - evidence_offset(p): see evidence_offset."""
+
+    LIKELIHOODS = BayesianGLM.LIKELIHOODS
+
+    def __init__(self, X, y, likelihood="bernoulli_logit", noise_sd=1.0, inclusion_prob=0.5):
+        glm = BayesianGLM(X, y, likelihood=likelihood, noise_sd=noise_sd)          # the GLM family's validation of the data
+        n, d = glm.X.shape
+        if d > 256:
+            raise ValueError("SpikeSlabRegression: the device keeps [theta, gamma] in one wave's registers, d must be in 1..256 (got %d)" % d)
+        inclusion_prob = float(inclusion_prob)
+        if not 0.0 < inclusion_prob < 1.0:
+            raise ValueError("SpikeSlabRegression: inclusion_prob must be in (0, 1) (got %r)" % (inclusion_prob,))
+        self.X, self.y, self.likelihood, self.noise_sd, self.inclusion_prob = glm.X, glm.y, likelihood, glm.noise_sd, inclusion_prob
+
+    @property
+    def n_obs(self):
+        return self.X.shape[0]
+
+    @property
+    def n_columns(self):
+        return self.X.shape[1]
+
+    @property
+    def dim(self):
+        return 2 * self.X.shape[1]
+
+    @property
+    def likelihood_code(self):
+        return self.LIKELIHOODS[self.likelihood]
+
+    def evidence_offset(self, precision):
+        """what stepping_stone(pt) is off the log evidence by: stepping_stone(pt) = log p(y) + evidence_offset(p), with
+        evidence_offset(p) = -(d/2) log(2 pi / p) - d log 2 and p the reference's precision"""
+        d = self.n_columns
+        return -(d / 2.0) * math.log(2.0 * math.pi / float(precision)) - d * math.log(2.0)
+
+    def __repr__(self):
+        return "SpikeSlabRegression(%s, n=%d, d=%d, inclusion_prob=%g)" % (self.likelihood, self.n_obs, self.n_columns, self.inclusion_prob)
+
+
 @dataclass
 class GaussianReference:
     """src/variational/GaussianReference.jl:4-17: mean-field Gaussian variational reference, refitted every round from
@@ -517,6 +567,14 @@ class PT:
             if not isinstance(ref, ScaledPrecisionNormalLogPotential) or ref.dim != target.dim:
                 raise NotImplementedError("the device mixture-model path needs reference=ScaledPrecisionNormalLogPotential(prec, dim) -- the prior")
             kw.update(target=_lib.TARGET_MIXTURE_MODEL, dim=target.dim, target_params=[ref.precision])
+        elif isinstance(target, SpikeSlabRegression):
+            ref = inputs.reference
+            if not isinstance(ref, ScaledPrecisionNormalLogPotential) or ref.dim != target.n_columns:
+                raise NotImplementedError("the device variable-selection path needs reference=ScaledPrecisionNormalLogPotential(prec, d) "
+                                          "-- the prior of the d coefficients")
+            if not isinstance(explorer, SliceSampler):
+                raise NotImplementedError("the device variable-selection path is explored by SliceSampler only (got %r)" % (explorer,))
+            kw.update(target=_lib.TARGET_VARIABLE_SELECTION, dim=target.dim, target_params=[ref.precision])
         else:
             raise NotImplementedError(
                 "target %r has no device log-potential; use the reference CPU path (Pigeons.jl)" % (target,))
@@ -584,6 +642,9 @@ class PT:
         if isinstance(target, MixtureModelPosterior):    # every engine (rank) holds the observations
             for eng in (self.shards.engines if hasattr(self.shards, "engines") else [self.replicas]):
                 eng.set_target_mixture_model(target.y)
+        if isinstance(target, SpikeSlabRegression):      # every engine (rank) holds the data
+            for eng in (self.shards.engines if hasattr(self.shards, "engines") else [self.replicas]):
+                eng.set_target_varsel(target.likelihood_code, target.X, target.y, target.noise_sd, target.inclusion_prob)
 
 
 def next_round(pt):
