@@ -51,7 +51,7 @@ constexpr int S8_BD = PTE_S8_BD;                 // doubling budget of a specula
 // None of the spills of either kernel is executed per round: the round loop of k_explore_slice8<4, 9> holds no v_writelane and no
 // spill reload (profiles/r04_slice8_round_loop.txt lists every lane instruction of the loop: the five of the chase) -- the 134 spilled
 // SGPRs of the resource table live in the prologue, the window refill and the exact sequential procedure.
-template <int NLU, int S8_BS, int WINDOW, int DBL_MODE>      // DBL_MODE: form of the budgeted doubling steps (0 selects, 1 EXEC masks, 2 v_cmpx + selects)
+template <int NLU, int S8_BS, int WINDOW, int DBL_MODE>      // DBL_MODE: form of the budgeted doubling steps (0 arithmetic under selected 0 / 1 factors, 1 EXEC masks, 2 v_cmpx + the same arithmetic)
 __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const int64_t cl) {      // cl: the local chain this workgroup explores (blockIdx.x in the per-scan kernels)
     using namespace s7;
     constexpr int WIN = WINDOW, REFILL_AT = WINDOW - PTE_S7_MARGIN;
@@ -158,6 +158,11 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
     };
     fill_window();
 
+    // constants of the round's doubling block (DBL_MODE 2), made opaque here so that they stay in registers for the whole kernel instead of
+    // being re-created every round: the zero low dwords of the register pairs (sL, sR) and the high dword of 1.0
+    int dbl_z0 = 0, dbl_z1 = 0, dbl_one_hi = 0x3ff00000;
+    if constexpr (DBL_MODE == 2) asm volatile("" : "+v"(dbl_z0), "+v"(dbl_z1), "+v"(dbl_one_hi));
+
     // recorder sums of the coordinates done by the exact sequential procedure; those of the speculative rounds are
     // derived at the end from the draws consumed (every coordinate draws E and u0, every further draw is one step)
     long long steps_sum = 0, fb_draws = 0, ex_total = 0;     // ex_total: extra draws of slow-path exponentials taken inside rounds
@@ -215,11 +220,23 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                         for (int it = 0; it < S8_BD; ++it) Vd[it] = s_u[idx0 + 2 + it];
                     }
                 }
-                const double Q = xold * xold - E * inv_nhp;
+                // Round 7: every slice test of the round is ONE fused operation, d = fma(v, v, -Q) = RN(v^2 - Q), where it used to be
+                // RN(RN(v^2) - Q) in two (the build uses -ffp-contract=off: the fusion is spelled out).  Only the sign of d is used, and only
+                // if |d| clears the margin 2e-12 Bq at the end of the round -- and then the two-operation value g the exact sequential
+                // procedure tests has the same sign and clears ITS margin, 1e-12 Bq: |d - g| <= 2^-53 v^2 + 2^-53 |g| + 2^-53 |d|, so for
+                // v^2 <= 2 |Q| the two differ by less than 2^-50 Bq = 9e-16 Bq, and for v^2 > 2 |Q| both are within 2^-50 of v^2 - Q >= v^2 / 2
+                // in relative terms.  Q itself is taken with one rounding too (it shares the product E / nhp with dmin's initial value): that
+                // moves it by at most 2^-53 x_old^2 <= 2^-53 Bq, which the factor of two between the margins absorbs in the same way.  So a
+                // hypothesis that is valid here takes the decisions of the exact procedure; one whose validity flips at the threshold is only
+                // retired by the other of the two procedures, which write the same state, draws and recorders.  The values that go INTO the
+                // state or are the reference's own arithmetic -- LL = x - w u0, RR = LL + w, R - L, the proposal L + u (R - L) -- keep their
+                // two roundings, and the exact sequential procedure below is untouched.
+                const double Enh = E * inv_nhp;
+                const double Q = __builtin_fma(xold, xold, -Enh);
                 const double Bq = Sest + fabs(Q);
-                double dmin = fabs(E * inv_nhp);             // |x_old^2 - Q|: the old position is inside the slice by the margin too (see the acceptance check)
+                double dmin = fabs(Enh);                     // |x_old^2 - Q|: the old position is inside the slice by the margin too (see the acceptance check)
                 auto test = [&](double v) __attribute__((always_inline)) -> double {
-                    const double d = v * v - Q;
+                    const double d = __builtin_fma(v, v, -Q);
                     dmin = fmin(dmin, fabs(d));
                     return d;                                // inside the slice <=> d < 0
                 };
@@ -233,36 +250,41 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                 if constexpr (DBL_MODE == 2) {           // (the launcher picks this instantiation only for sp.p >= S8_BD: no second body in the loop)
                     // Round 4, the one-wave-per-SIMD kernel: a hypothesis that needs no (further) doubling drops out of EXEC by v_cmpx --
                     // written by the VECTOR side, no trip to the scalar side (what made the EXEC-mask form below 2 % slower for a lone
-                    // wave) -- which freezes its interval, end values, step count and dmin without a select; only the side (left / right,
-                    // per lane) is selected: 20 VALU instructions per step, none scalar, where the pure select form needs 28.  "Needs
-                    // doubling" is monotone (a lane that stops never resumes: its values do not change), so EXEC only narrows and is
-                    // restored once.  Same operations in the same order per lane: L - (R - L) or R + (R - L) (SliceSampler.jl:123-131),
-                    // d = v * v - Q, |d| folded into dmin.  (>= 4 instructions between a VALU write of VCC and its use as a lane mask.)
-                    // Fixed registers because the 64-bit selects address register halves; LL / RR / dmin / Q sit where the shrinkage block
-                    // below wants Lbar / Rbar / dmin / Q.
-                    double t_, wd_, cl_, cr_, cd_, dc_;
-                    uint64_t sv_;
+                    // wave) -- which freezes its interval, end values, step count and dmin without a select.  "Needs doubling" is monotone
+                    // (a lane that stops never resumes: its values do not change), so EXEC only narrows and is restored once.
+                    // Round 7: the side (left / right, per lane) is not selected either -- round 4 computed both candidates and picked five
+                    // 64-bit values by ten v_cndmask halves, 20 VALU per step; now the extension itself is arithmetic, 13 per step and no
+                    // candidate registers.  sL = left ? 1.0 : 0.0 and sR = left ? 0.0 : 1.0 are ONE v_cndmask each, on the high dword of a
+                    // register pair whose low dword is a zero kept for the whole kernel; then
+                    //     LL = fma(-sL, wd, LL)   RR = fma(sR, wd, RR)   dL = fma(LL, LL, -Q)   dR = fma(RR, RR, -Q)
+                    // with wd = RR - LL taken first.  Bit for bit the reference's L - (R - L) or R + (R - L) (SliceSampler.jl:123-131) on
+                    // the side that moves: a product by 1.0 is exact, so the fma rounds once, as the addition did.  The side that stays is
+                    // reproduced exactly: wd is FINITE (w 2^k with k <= 20 doublings; anything else is a NaN hypothesis, invalid anyway), so
+                    // -0.0 * wd = -0.0 and +0.0 * wd = +0.0; x + (-0.0) = x for every x, and x + (+0.0) = x unless x is -0.0, which RR never
+                    // is (RR = RN(LL + w) or RN(RR + wd), a sum with a positive term: an exact zero of it is +0.0).  Its end value is
+                    // recomputed from the unchanged end by the operation that produced it (the head's test is the same fma), i.e. unchanged,
+                    // and folding its |d| into dmin a second time changes nothing.  Both |d| go into dmin.
+                    // `left` is decided FIRST, into VCC, and the narrowing v_cmpx writes its mask to a scalar pair instead: four instructions
+                    // stand between the VALU write of VCC and its use as a lane mask (a v_cmp under the EXEC of the step before: a lane
+                    // that dropped out does not read it).  Fixed registers because the selects address register halves; LL / RR / dmin / Q
+                    // sit where the shrinkage block below wants Lbar / Rbar / dmin / Q.
+                    double t_, wd_;
+                    int sLh_, sRh_;
+                    uint64_t sv_, sx_;
 #define PTE_S8_CSTEP(V) \
-                    "v_min_f64 v[102:103], v[114:115], v[116:117]\n" \
-                    "v_cmpx_gt_f64 vcc, 0, v[102:103]\n" \
                     "v_cmp_ge_f64 vcc, 0.5, " V "\n" \
+                    "v_min_f64 v[102:103], v[114:115], v[116:117]\n" \
+                    "v_cmpx_gt_f64_e64 %[sx], 0, v[102:103]\n" \
                     "v_add_f64 v[112:113], v[98:99], -v[96:97]\n" \
                     "v_add_u32 %[kd], 1, %[kd]\n" \
-                    "v_add_f64 v[118:119], v[96:97], -v[112:113]\n" \
-                    "v_add_f64 v[120:121], v[98:99], v[112:113]\n" \
-                    "v_cndmask_b32 v100, v120, v118, vcc\n" \
-                    "v_cndmask_b32 v101, v121, v119, vcc\n" \
-                    "v_cndmask_b32 v96, v96, v118, vcc\n" \
-                    "v_cndmask_b32 v97, v97, v119, vcc\n" \
-                    "v_mul_f64 v[102:103], v[100:101], v[100:101]\n" \
-                    "v_cndmask_b32 v98, v120, v98, vcc\n" \
-                    "v_cndmask_b32 v99, v121, v99, vcc\n" \
-                    "v_add_f64 v[122:123], v[102:103], -v[110:111]\n" \
-                    "v_cndmask_b32 v114, v114, v122, vcc\n" \
-                    "v_cndmask_b32 v115, v115, v123, vcc\n" \
-                    "v_cndmask_b32 v116, v122, v116, vcc\n" \
-                    "v_cndmask_b32 v117, v123, v117, vcc\n" \
-                    "v_min_f64 v[104:105], v[104:105], |v[122:123]|\n"
+                    "v_cndmask_b32 v119, 0, %[one], vcc\n" \
+                    "v_cndmask_b32 v121, %[one], v118, vcc\n" \
+                    "v_fma_f64 v[96:97], -v[118:119], v[112:113], v[96:97]\n" \
+                    "v_fma_f64 v[98:99], v[120:121], v[112:113], v[98:99]\n" \
+                    "v_fma_f64 v[114:115], v[96:97], v[96:97], -v[110:111]\n" \
+                    "v_fma_f64 v[116:117], v[98:99], v[98:99], -v[110:111]\n" \
+                    "v_min_f64 v[104:105], v[104:105], |v[114:115]|\n" \
+                    "v_min_f64 v[104:105], v[104:105], |v[116:117]|\n"
                     asm volatile("s_mov_b64 %[sv], exec\n"
                                  PTE_S8_CSTEP("%[V0]")
 #if PTE_S8_BD >= 2
@@ -277,18 +299,18 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                                  "s_mov_b64 exec, %[sv]\n"
                                  "v_min_f64 v[102:103], v[114:115], v[116:117]\n"      // (all lanes: what "still needs doubling" is decided on below)
                                  : "+{v[96:97]}"(LL), "+{v[98:99]}"(RR), "+{v[114:115]}"(dL), "+{v[116:117]}"(dR), "+{v[104:105]}"(dmin), [kd] "+v"(kd),
-                                   "=&{v[102:103]}"(t_), "=&{v[112:113]}"(wd_), "=&{v[118:119]}"(cl_), "=&{v[120:121]}"(cr_), "=&{v[100:101]}"(cd_),
-                                   "=&{v[122:123]}"(dc_), [sv] "=&s"(sv_)
-                                 : "{v[110:111]}"(Q), [V0] "v"(Vd[0]), [V1] "v"(Vd[S8_BD > 1 ? 1 : 0]), [V2] "v"(Vd[S8_BD > 2 ? 2 : 0]), [V3] "v"(Vd[S8_BD > 3 ? 3 : 0])
+                                   "=&{v[102:103]}"(t_), "=&{v[112:113]}"(wd_), "=&{v119}"(sLh_), "=&{v121}"(sRh_), [sv] "=&s"(sv_), [sx] "=&s"(sx_)
+                                 : "{v[110:111]}"(Q), "{v118}"(dbl_z0), "{v120}"(dbl_z1), [one] "v"(dbl_one_hi),
+                                   [V0] "v"(Vd[0]), [V1] "v"(Vd[S8_BD > 1 ? 1 : 0]), [V2] "v"(Vd[S8_BD > 2 ? 2 : 0]), [V3] "v"(Vd[S8_BD > 3 ? 3 : 0])
                                  : "vcc", "scc");
 #undef PTE_S8_CSTEP
                     dmin_lr = t_;
                 } else
                 if (DBL_MODE == 1 && sp.p >= S8_BD) {    // (uniform; compile-time per kernel)
                     // Hand-written: a step runs under EXEC = "this hypothesis still needs doubling", the left / right extension under
-                    // EXEC = need & left / need & ~left -- 13 VALU instructions per step where the select form below needs 28 (sixteen of
-                    // them v_cndmask halves).  Same operations in the same order per lane: L - (R - L) or R + (R - L)
-                    // (SliceSampler.jl:123-131), d = v * v - Q, |d| folded into dmin.  Which form is faster depends on what else the SIMD
+                    // EXEC = need & left / need & ~left -- 11 VALU instructions per step (13 before round 7 fused the slice test) where the
+                    // pure select form of rounds 3-6 needed 28 (sixteen of them v_cndmask halves; these measurements are of that form).  Same operations in the same order per lane: L - (R - L)
+                    // or R + (R - L) (SliceSampler.jl:123-131), d = fma(v, v, -Q), |d| folded into dmin.  Which form is faster depends on what else the SIMD
                     // has to do: each step of this form crosses twice from the vector to the scalar side (v_cmp -> s_and_saveexec), ~40
                     // cycles each for a wave ALONE on its SIMD, nothing when other waves fill the gap -- measured at N = 1024 / 2048 /
                     // 4096 / 8192 replicas per GPU: 0.868 / 1.141 / 1.853 / 3.395 ms per scan in this form against 0.851 / 1.167 / 1.950 /
@@ -305,13 +327,11 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                     "v_cmp_ge_f64 vcc, 0.5, " V "\n" \
                     "s_and_saveexec_b64 %[sv2], vcc\n" \
                     "v_add_f64 %[LL], %[LL], -%[wd]\n" \
-                    "v_mul_f64 %[t], %[LL], %[LL]\n" \
-                    "v_add_f64 %[dL], %[t], -%[Q]\n" \
+                    "v_fma_f64 %[dL], %[LL], %[LL], -%[Q]\n" \
                     "v_min_f64 %[dmin], %[dmin], |%[dL]|\n" \
                     "s_andn2_b64 exec, %[sv2], exec\n" \
                     "v_add_f64 %[RR], %[RR], %[wd]\n" \
-                    "v_mul_f64 %[t], %[RR], %[RR]\n" \
-                    "v_add_f64 %[dR], %[t], -%[Q]\n" \
+                    "v_fma_f64 %[dR], %[RR], %[RR], -%[Q]\n" \
                     "v_min_f64 %[dmin], %[dmin], |%[dR]|\n" \
                     "s_mov_b64 exec, %[sv]\n"
                     asm volatile(PTE_S8_DSTEP("%[V0]")
@@ -338,14 +358,27 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                     kd += need ? 1 : 0;
                     const bool left = V <= 0.5;
                     const double wd = RR - LL;
-                    const double cand = left ? (LL - wd) : (RR + wd);
-                    const double dc = cand * cand - Q;
-                    dmin = need ? fmin(dmin, fabs(dc)) : dmin;
-                    const bool nl_ = need && left, nr_ = need && !left;
-                    LL = nl_ ? cand : LL;
-                    RR = nr_ ? cand : RR;
-                    dL = nl_ ? dc : dL;
-                    dR = nr_ ? dc : dR;
+                    if constexpr (DBL_MODE == 0) {
+                        // the arithmetic form of the hand-written block above (the side that stays -- both, without `need` -- is reproduced
+                        // exactly): 325 -> 287 instructions per round in k_scans_slice8_generic
+                        const double sL = (need && left) ? 1.0 : 0.0, sR = (need && !left) ? 1.0 : 0.0;
+                        LL = __builtin_fma(-sL, wd, LL);
+                        RR = __builtin_fma(sR, wd, RR);
+                        dL = __builtin_fma(LL, LL, -Q);
+                        dR = __builtin_fma(RR, RR, -Q);
+                        dmin = fmin(dmin, fmin(fabs(dL), fabs(dR)));
+                    } else {
+                        // (the many-replica twin keeps the select form for its p < S8_BD body: the two factors cost the kernel, capped at 128
+                        // VGPRs, six more spilled registers -- 36-44 B of scratch per lane instead of 12-20)
+                        const double cand = left ? (LL - wd) : (RR + wd);
+                        const double dc = __builtin_fma(cand, cand, -Q);
+                        dmin = need ? fmin(dmin, fabs(dc)) : dmin;
+                        const bool nl_ = need && left, nr_ = need && !left;
+                        LL = nl_ ? cand : LL;
+                        RR = nr_ ? cand : RR;
+                        dL = nl_ ? dc : dL;
+                        dR = nr_ ? dc : dR;
+                    }
                 }
 #if !(PTE_S8_BD >= 1 && PTE_S8_BD <= 4) || defined(PTE_S8_DOUBLING_SELECTS)
                 // the hand-written block is compiled out in this variant build: DBL_MODE 2 would run the select loop above and leave dmin_lr at 0.0
@@ -413,9 +446,8 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                     "v_mul_f64 v[102:103], " U ", v[112:113]\n" \
                     "v_add_f64 v[100:101], v[96:97], v[102:103]\n" \
                     "v_cmp_lt_f64 vcc, v[100:101], v[108:109]\n" \
-                    "v_mul_f64 v[102:103], v[100:101], v[100:101]\n" \
+                    "v_fma_f64 v[102:103], v[100:101], v[100:101], -v[110:111]\n" \
                     "v_add_u32 v106, 1, v106\n" \
-                    "v_add_f64 v[102:103], v[102:103], -v[110:111]\n" \
                     "v_cndmask_b32 v96, v96, v100, vcc\n" \
                     "v_cndmask_b32 v97, v97, v101, vcc\n" \
                     "v_cndmask_b32 v98, v100, v98, vcc\n" \
@@ -455,7 +487,7 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                     for (int k = 0; k < S8_BS; ++k) {
                         W = Rbar - Lbar;
                         const double v = Lbar + u[k] * W;
-                        const double dv = v * v - Q;
+                        const double dv = __builtin_fma(v, v, -Q);
                         dmin = fmin(dmin, fabs(dv));              // (after `fin` too: only ever makes the filter more conservative)
                         xf = fin ? xf : v;
                         n += fin ? 0 : 1;
@@ -567,7 +599,10 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                 //      { v : v^2 < Q' } for the reference's own floating-point predicate too (the fixed-tree sum is monotone in
                 //      |v|: every rounding step is), an interval -- and both positions are inside it with the filter's margin to
                 //      spare (the new one by its own test, the old one because |x_old^2 - Q| = E / |nhp| was folded into dmin
-                //      above), so that end is inside and the test cannot fire.  Measured before the removal: 0 rejections in every
+                //      above), so that end is inside and the test cannot fire.  (Round 7: the round's tests are fused, d = fma(v, v, -Q), and
+                //      Q is taken with one rounding; |d| > 2e-12 Bq still leaves the two-operation value RN(RN(v^2) - Q) of the reference's
+                //      arithmetic beyond 1e-12 Bq on the same side -- the bound is at the head of the round -- which is the margin this
+                //      argument needs.)  Measured before the removal: 0 rejections in every
                 //      profile (profiles/r03_slice8_sections_by_chain.txt), while the region cost the hot chains (precision near 1,
                 //      where most intervals are doubled) ~8 % of their time -- they were the launch's slowest waves
                 //      (profiles/r03_slice8_per_wave.txt).  The exact sequential procedure below still runs the reference's test.
