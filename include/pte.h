@@ -53,9 +53,12 @@ enum {
     PTE_TARGET_MIXTURE_MODEL        = 6, /* InterpolatingPath(normal ref = the prior, prior x likelihood of a K-component normal mixture model
                                             of data y; pte_set_target_mixture_model): theta = [mu, s, alpha], dim = 3 K, K <= 8;
                                             SliceSampler / AutoMALA / MALA / Compose of them */
-    PTE_TARGET_VARIABLE_SELECTION = 7    /* spike-and-slab regression on data X, y (pte_set_target_varsel): the state is [theta, gamma],
+    PTE_TARGET_VARIABLE_SELECTION = 7,   /* spike-and-slab regression on data X, y (pte_set_target_varsel): the state is [theta, gamma],
                                             d Float64 coefficients then d Bool indicators stored as 0.0 / 1.0, dim = 2 d, d <= 256;
                                             SliceSampler only (its Float64 and Bool coordinate methods) */
+    PTE_TARGET_CHANGE_POINT = 8          /* K Poisson change points on n counts (pte_set_target_changepoint): the state is [r, tau],
+                                            K + 1 Float64 log rates then K Integer change points stored as integral doubles in 0..n,
+                                            dim = 2 K + 1, K <= 63; SliceSampler only (its Float64 and Integer coordinate methods) */
 };
 /* PTE_TARGET_BAYESIAN_GLM: the likelihood of each observation */
 enum {
@@ -257,6 +260,17 @@ int pte_set_target_mixture_model(pte_engine *h, int64_t n_obs, const double *y /
  * stepping_stone estimates log p(y) - (d/2) log(2 pi / p) - d log 2 (the reference is uniform on the 2^d indicator vectors).  DESIGN 4.12. */
 int pte_set_target_varsel(pte_engine *h, const double *X /*[n_obs][d]*/, const double *y /*[n_obs]*/, int64_t n_obs, int64_t d,
                           int32_t likelihood, double noise_sd, double inclusion_prob);
+/* PTE_TARGET_CHANGE_POINT: the data of the target N(r; 0, I / p) (n + 1)^-K prod_j prod_{s_j <= i < s_{j+1}} Poisson(y_i; exp(r_j)), where
+ * s_1 <= ... <= s_K are the sorted change points tau (unordered in the state), s_0 = 0, s_{K+1} = n, K = (dim - 1) / 2 and p =
+ * target_params[0], the reference's precision.  Validates (1 <= n_obs <= 65536; every y_i finite, integral and in 0..2^20), uploads the
+ * prefix sums of y and refreshes the swap statistics of the current states; may be called again to replace the data.  Until the first call
+ * pte_explore, pte_swap, pte_run_scans, pte_group_run_scans and pte_get_state fail.  stepping_stone estimates
+ * log p(y) - ((K+1)/2) log(2 pi / p) - K log(n + 1) (the reference is uniform on the (n + 1)^K placements).  DESIGN 4.13. */
+int pte_set_target_changepoint(pte_engine *h, const double *y /*[n_obs]*/, int64_t n_obs);
+/* PTE_TARGET_CHANGE_POINT: the form in which k_explore_changepoint evaluates a proposal -- in full, or from the sorted bounds kept for the
+ * committed state.  Both compute the same bits; AUTO is the faster one.  For measurements and tests. */
+enum { PTE_CHANGEPOINT_FORM_AUTO = 0, PTE_CHANGEPOINT_FORM_FULL = 1, PTE_CHANGEPOINT_FORM_CACHED = 2 };
+int pte_set_changepoint_form(pte_engine *h, int32_t form);
 int pte_get_state(const pte_engine *h, double *state, int64_t *chain, uint64_t *rng);
 int pte_set_state(pte_engine *h, const double *state, const int64_t *chain, const uint64_t *rng);
 

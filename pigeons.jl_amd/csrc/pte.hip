@@ -28,6 +28,7 @@
 #include "pte_glm_params.hpp"
 #include "pte_mixture_model_params.hpp"
 #include "pte_varsel_params.hpp"
+#include "pte_changepoint_params.hpp"
 #else                              // tools / development builds: one translation unit
 #include "pte_langevin_launch.hpp"
 #include "pte_aaps.hpp"
@@ -35,6 +36,7 @@
 #include "pte_glm.hpp"
 #include "pte_mixture_model.hpp"
 #include "pte_varsel.hpp"
+#include "pte_changepoint.hpp"
 #endif
 #include "pte_ising.hpp"
 #if defined(PTE_PROFILE_AM)               // debug builds only (tools/prof_automala.py): 12 words per wave, section times of k_explore_automala
@@ -104,6 +106,9 @@ struct pte_engine {
     double *d_varsel = nullptr;     // PTE_TARGET_VARIABLE_SELECTION: Xc [d][n_pad], y [n_pad], sized for the largest n of this d
     VarselParams varsel{};          // the uploaded data as the kernels read it; varsel.n = 0 until pte_set_target_varsel
     int varsel_lik = 0;
+    double *d_changepoint = nullptr;    // PTE_TARGET_CHANGE_POINT: the prefix table C [65537], sized once for the largest n
+    ChangepointParams changepoint{};    // the uploaded table as the kernels read it; changepoint.n = 0 until pte_set_target_changepoint
+    int changepoint_form = CHANGEPOINT_FORM_AUTO;      // pte_set_changepoint_form
     double step_size = 1.0;
     int am_n_refresh = 0;
     std::vector<double> fac_mean, rev_mean; std::vector<int64_t> fac_n, rev_n;
@@ -232,13 +237,15 @@ const PathFamily *path_family(int target) {
                             mixture{"Gaussian-mixture", "components", "pte_set_target_mixture", "one register-resident kernel serves it", "k_explore_mixture"},
                             glm{"Bayesian-GLM", "data", "pte_set_target_glm", "one kernel serves it", "k_explore_glm"},
                             mixmodel{"mixture-model", "data", "pte_set_target_mixture_model", "one kernel serves it", "k_explore_mixture_model"},
-                            varsel{"variable-selection", "data", "pte_set_target_varsel", "one kernel serves it", "k_explore_varsel"};
+                            varsel{"variable-selection", "data", "pte_set_target_varsel", "one kernel serves it", "k_explore_varsel"},
+                            changepoint{"change-point", "data", "pte_set_target_changepoint", "one kernel serves it", "k_explore_changepoint"};
     switch (target) {
     case PTE_TARGET_FUNNEL: return &funnel;
     case PTE_TARGET_GAUSSIAN_MIXTURE: return &mixture;
     case PTE_TARGET_BAYESIAN_GLM: return &glm;
     case PTE_TARGET_MIXTURE_MODEL: return &mixmodel;
     case PTE_TARGET_VARIABLE_SELECTION: return &varsel;
+    case PTE_TARGET_CHANGE_POINT: return &changepoint;
     default: return nullptr;
     }
 }
@@ -250,6 +257,7 @@ bool family_ready(const pte_engine *h) {
     case PTE_TARGET_BAYESIAN_GLM: return h->glm.n > 0;
     case PTE_TARGET_MIXTURE_MODEL: return h->mixmodel.n > 0;
     case PTE_TARGET_VARIABLE_SELECTION: return h->varsel.n > 0;
+    case PTE_TARGET_CHANGE_POINT: return h->changepoint.n > 0;
     default: return true;
     }
 }
@@ -270,6 +278,10 @@ MixParams mixture_params(const pte_engine *h) {
     return mp;
 }
 
+// the evaluation form of k_explore_changepoint (the same bits either way): the one asked for (pte_set_changepoint_form), or
+// the cached form, which was the faster one at every shape measured
+bool changepoint_cached(const pte_engine *h) { return h->changepoint_form != CHANGEPOINT_FORM_FULL; }
+
 // One launch of the engine's AutoMALA / MALA / SliceSampler-on-the-path kernel over N replicas (one workgroup each): the family's own on the
 // mixture, GLM and mixture-model paths, the Langevin family's on the funnel and scaled-precision MVN paths.  The open timing bracket's events ride on it.
 int launch_path_kernel(pte_engine *h, int E, bool slice, bool full, int64_t N, const AmParams &ap) {
@@ -280,6 +292,8 @@ int launch_path_kernel(pte_engine *h, int E, bool slice, bool full, int64_t N, c
     case PTE_TARGET_MIXTURE_MODEL: return mixture_model_launch(MixModelLaunch{(int)(h->d / 3), slice, at}, h->dev, ap, h->mixmodel) ? family_no_kernel_error(h) : 0;
     case PTE_TARGET_VARIABLE_SELECTION:      // SliceSampler alone (validate_config); whole blocks: 2 d == 64 E
         return varsel_launch(VarselLaunch{E, h->varsel_lik, h->d == 64 * (int64_t)E, at}, h->dev, ap, h->varsel) ? family_no_kernel_error(h) : 0;
+    case PTE_TARGET_CHANGE_POINT:            // SliceSampler alone (validate_config); two registers per lane whatever the dim: no E
+        return changepoint_launch(ChangepointLaunch{changepoint_cached(h), at}, h->dev, ap, h->changepoint) ? family_no_kernel_error(h) : 0;
     default: break;
     }
     LangevinLaunch L{E, h->cfg.target == PTE_TARGET_FUNNEL ? TGT_FUNNEL : TGT_MVN, slice, full, at};
@@ -299,6 +313,7 @@ int refresh_path_stats(pte_engine *h) {
     case PTE_TARGET_BAYESIAN_GLM: if (glm_refresh_stats(E, h->glm_lik, N, h->stream, h->dev, h->glm, h->cfg.target_params[0])) return family_no_kernel_error(h); break;
     case PTE_TARGET_MIXTURE_MODEL: if (mixture_model_refresh_stats((int)(h->d / 3), N, h->stream, h->dev, h->mixmodel, h->cfg.target_params[0])) return family_no_kernel_error(h); break;
     case PTE_TARGET_VARIABLE_SELECTION: if (varsel_refresh_stats(E, h->varsel_lik, N, h->stream, h->dev, h->varsel, h->cfg.target_params[0])) return family_no_kernel_error(h); break;
+    case PTE_TARGET_CHANGE_POINT: if (changepoint_refresh_stats(N, h->stream, h->dev, h->changepoint, h->cfg.target_params[0])) return family_no_kernel_error(h); break;
     default: return 0;
     }
     HIP_OK(h, hipGetLastError());
@@ -995,6 +1010,17 @@ int validate_config(const pte_config *cfg) {
             return fail(nullptr, "pte_create: the variable-selection path holds [theta, gamma] of d columns, dim = 2 d must be even (got %lld)", (long long)cfg->dim);
         if (cfg->dim < 2 || cfg->dim > 512)
             return fail(nullptr, "pte_create: the variable-selection path keeps the replica in the registers of one wave, d = dim / 2 must be in 1..256 (got dim %lld)", (long long)cfg->dim);
+    }
+    if (cfg->target == PTE_TARGET_CHANGE_POINT) {            // Float64 and Integer coordinates, SliceSampler's two methods and nothing else
+        if (cfg->explorer != PTE_EXPLORER_SLICE || cfg->explorer2 != PTE_EXPLORER_NONE)
+            return fail(nullptr, "pte_create: the change-point path is explored by SliceSampler only -- its Integer coordinates have no gradient, "
+                                 "and no Compose (got explorers %d, %d)", cfg->explorer, cfg->explorer2);
+        if (cfg->dim % 2 != 1)
+            return fail(nullptr, "pte_create: the change-point path holds K + 1 log rates and K change points, dim = 2 K + 1 must be odd (got %lld)", (long long)cfg->dim);
+        if (cfg->dim < 3 || cfg->dim > 127)
+            return fail(nullptr, "pte_create: the change-point path gives every segment a lane of one wave, K = (dim - 1) / 2 must be in 1..63 (got dim %lld)", (long long)cfg->dim);
+        if (cfg->slice_w != std::floor(cfg->slice_w) || !std::isfinite(cfg->slice_w))      // SliceSampler.jl:137 (@assert), the oracle's text
+            return fail(nullptr, "pte_create: for integer variables, the width should be an integer. Got: %g", cfg->slice_w);
     }
     if (family && !funnel) {    // the families with kernels of their own -- Gaussian mixture, Bayesian GLM, mixture model: one wave per replica, SliceSampler / AutoMALA / MALA (AAPS: refused above)
         auto on_family = [](int k) { return k == PTE_EXPLORER_SLICE || k == PTE_EXPLORER_AUTOMALA || k == PTE_EXPLORER_MALA; };
@@ -2200,6 +2226,49 @@ int pte_set_target_varsel(pte_engine *h, const double *X, const double *y, int64
     v.log_pi = std::log(inclusion_prob); v.log_1mpi = std::log(1.0 - inclusion_prob);
     h->varsel_lik = likelihood;
     return refresh_path_stats(h);                                  // suff / suff2 of the current states
+}
+
+// Poisson change points.  Host, once per call: the prefix table C[t] = sum_{i < t} y_i (exact: below 2^36), c_prior =
+// -((K+1)/2) log(2 pi / p), c_tau = -K log(n + 1) and c_obs = -sum_i lgamma(y_i + 1), sequential in i; the table goes into one allocation
+// sized once for the largest n.
+int pte_set_target_changepoint(pte_engine *h, const double *y, int64_t n_obs) {
+    if (!h) return 1;
+    PTE_ALIVE(h, "pte_set_target_changepoint");
+    if (h->cfg.target != PTE_TARGET_CHANGE_POINT)
+        return fail(h, "pte_set_target_changepoint: this engine's target is %d, not PTE_TARGET_CHANGE_POINT", h->cfg.target);
+    if (n_obs < 1 || n_obs > 65536)
+        return fail(h, "pte_set_target_changepoint: the device holds 1..65536 observations (got %lld)", (long long)n_obs);
+    if (!y) return fail(h, "pte_set_target_changepoint: null argument");
+    for (int64_t i = 0; i < n_obs; ++i)
+        if (!std::isfinite(y[i]) || y[i] != std::floor(y[i]) || y[i] < 0.0 || y[i] > 1048576.0)
+            return fail(h, "pte_set_target_changepoint: y[%lld] must be an integer count in 0..2^20 (got %g)", (long long)i, y[i]);
+    HIP_OK(h, hipSetDevice(h->cfg.device));
+    const int64_t n = n_obs, K = (h->d - 1) / 2;
+    std::vector<double> C((size_t)65537, 0.0);
+    double c_obs = 0.0;
+    for (int64_t i = 0; i < n; ++i) { C[i + 1] = C[i] + y[i]; c_obs = c_obs - std::lgamma(y[i] + 1.0); }
+    if (!h->d_changepoint && dev_alloc(h, &h->d_changepoint, C.size(), false)) return 1;
+    HIP_OK(h, hipMemcpyAsync(h->d_changepoint, C.data(), sizeof(double) * C.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    const double p = h->cfg.target_params[0];
+    ChangepointParams &v = h->changepoint;
+    v.C = h->d_changepoint; v.n = (int)n; v.K = (int)K;
+    v.c_prior = -((double)(K + 1) / 2.0) * std::log(2.0 * M_PI / p);
+    v.c_tau = -(double)K * std::log((double)(n + 1));
+    v.c_obs = c_obs;
+    return refresh_path_stats(h);                                  // suff / suff2 of the current states
+}
+
+// Which evaluation form k_explore_changepoint takes from now on (PTE_CHANGEPOINT_FORM_*); both give the same bits.
+int pte_set_changepoint_form(pte_engine *h, int32_t form) {
+    if (!h) return 1;
+    PTE_ALIVE(h, "pte_set_changepoint_form");
+    if (h->cfg.target != PTE_TARGET_CHANGE_POINT)
+        return fail(h, "pte_set_changepoint_form: this engine's target is %d, not PTE_TARGET_CHANGE_POINT", h->cfg.target);
+    if (form != CHANGEPOINT_FORM_AUTO && form != CHANGEPOINT_FORM_FULL && form != CHANGEPOINT_FORM_CACHED)
+        return fail(h, "pte_set_changepoint_form: form must be PTE_CHANGEPOINT_FORM_AUTO (0), _FULL (1) or _CACHED (2) (got %d)", form);
+    h->changepoint_form = form;
+    return 0;
 }
 
 // update_reference! + update_path_variational (src/variational/variational.jl:28-41, GaussianReference.jl:24-31): from now on

@@ -1,13 +1,13 @@
 // pte_automala_params.hpp -- what the launcher (pte.hip) and the kernel families share: kernel parameters, where a launch goes (LaunchSite,
 // launch_on) and, per family, the one entry point through which its kernels are launched.
 //
-// The product library is built from SEVEN translation units (UNITS in __graft_entry__.py):
+// The product library is built from EIGHT translation units (UNITS in __graft_entry__.py):
 //   pte.hip           the C ABI, the launcher and every kernel not named below, scheduled with -O2 -amdgpu-sched-strategy=max-ilp: the
 //                     one-wave-per-SIMD slice kernels gain 1.3-2.3 %
 //   pte_langevin.hip  AutoMALA / MALA and SliceSampler on the funnel path (pte_langevin_launch.hpp) with the default scheduler: max-ilp
 //                     costs their d >= 512 instantiations up to 10 %
-//   pte_aaps.hip, pte_mixture.hip, pte_glm.hip, pte_mixture_model.hip, pte_varsel.hip
-//                     the AAPS, Gaussian-mixture, Bayesian-GLM, mixture-model-posterior and variable-selection kernels with pte_langevin.hip's flags.  A unit each: whatever is added
+//   pte_aaps.hip, pte_mixture.hip, pte_glm.hip, pte_mixture_model.hip, pte_varsel.hip, pte_changepoint.hip
+//                     the AAPS, Gaussian-mixture, Bayesian-GLM, mixture-model-posterior, variable-selection and change-point kernels with pte_langevin.hip's flags.  A unit each: whatever is added
 //                     to an existing unit moves the generated code of the kernels already in it (tests/test_codegen_*.py freeze it)
 // Every unit includes pte_kernels.hpp and therefore holds its own copy of the `static __device__` word g_rng_policy: PTE_KERNEL_UNITS below.
 // Tools and development builds compile pte.hip alone (no -DPTE_SPLIT_LANGEVIN): it then includes the kernel headers and their entry points itself.
@@ -65,7 +65,7 @@ void langevin_refresh_funnel_stats(int E, unsigned N, hipStream_t stream, const 
 
 // The translation units besides pte.hip.  Each defines <unit>_set_rng_policy -- its own copy of g_rng_policy (hipError_t as int) -- with
 // PTE_DEFINE_RNG_POLICY_SETTER(<unit>), and pte_set_rng_policy walks this list: a unit listed here without the setter does not link.
-#define PTE_KERNEL_UNITS(X) X(langevin) X(aaps) X(mixture) X(glm) X(mixture_model) X(varsel)
+#define PTE_KERNEL_UNITS(X) X(langevin) X(aaps) X(mixture) X(glm) X(mixture_model) X(varsel) X(changepoint)
 #define PTE_DECLARE_RNG_POLICY_SETTER(unit) int unit##_set_rng_policy(unsigned policy);
 PTE_KERNEL_UNITS(PTE_DECLARE_RNG_POLICY_SETTER)
 #define PTE_DEFINE_RNG_POLICY_SETTER(unit)                                                                                        \

@@ -38,6 +38,7 @@ const TARGET_MVN, TARGET_TEST_SWAPPER, TARGET_FUNNEL, TARGET_ISING, TARGET_GAUSS
 const TARGET_BAYESIAN_GLM = Int32(5)
 const TARGET_MIXTURE_MODEL = Int32(6)
 const TARGET_VARIABLE_SELECTION = Int32(7)
+const TARGET_CHANGE_POINT = Int32(8)
 const GLM_BERNOULLI_LOGIT, GLM_NORMAL_IDENTITY = Int32(0), Int32(1)
 const EXPLORER_NONE, EXPLORER_TOY, EXPLORER_SLICE, EXPLORER_AUTOMALA, EXPLORER_ISING, EXPLORER_MALA, EXPLORER_AAPS = Int32.((0, 1, 2, 3, 4, 5, 6))
 const RECORD_ROUND_TRIP, RECORD_INDEX_PROCESS, RECORD_ONLINE, RECORD_TRACES, RECORD_ENERGY_AC1, RECORD_TRACES_EXTENDED =
@@ -127,6 +128,13 @@ likelihoods of DeviceBayesianGLM (X is n x d) with an inclusion indicator per co
 explorer = SliceSampler())` -- SliceSampler is the one explorer of this family.  stepping_stone(pt) + (d/2) log(2 pi / p) + d log 2 is the
 log evidence."""
 struct DeviceSpikeSlabRegression; X::Matrix{Float64}; y::Vector{Float64}; likelihood::Symbol; noise_sd::Float64; inclusion_prob::Float64; end
+"""Multiple change-point detection on count data: the device family PTE_TARGET_CHANGE_POINT (DESIGN 4.13).  n counts y, K = n_changepoints
+change points; the state is [r; tau] (dim = 2 K + 1): K + 1 log rates, then K Integer change points in 0:n stored as integral Float64,
+unordered -- segment j lies between the j-th and (j+1)-th smallest -- with prior N(0, I / p) on r and uniform on every tau.  Used as
+`Inputs(target = on_mi355x(DevicePoissonChangePoint(y, K)), reference = ScaledPrecisionNormalLogPotential(p, K + 1), explorer =
+SliceSampler())` -- SliceSampler is the one explorer of this family, and its width must be integral.
+stepping_stone(pt) + ((K+1)/2) log(2 pi / p) + K log(n + 1) is the log evidence."""
+struct DevicePoissonChangePoint; y::Vector{Float64}; n_changepoints::Int; end
 
 # (target code, dim, target_params, reference precision check) of a wrapped target
 device_family(t::ScaledPrecisionNormalPath, inputs) = (TARGET_MVN, t.dim, (t.precision0, t.precision1, 0.0, 0.0))
@@ -174,6 +182,16 @@ function device_family(t::DeviceSpikeSlabRegression, inputs)
     ref isa ScaledPrecisionNormalLogPotential && ref.dim == d ||
         error("the device variable-selection path needs reference = ScaledPrecisionNormalLogPotential(precision, $d) (the prior of the coefficients); keep the CPU path otherwise")
     return (TARGET_VARIABLE_SELECTION, 2 * d, (ref.precision, 0.0, 0.0, 0.0))
+end
+function device_family(t::DevicePoissonChangePoint, inputs)
+    K = t.n_changepoints
+    1 <= K <= 63 || error("DevicePoissonChangePoint: the device holds 1..63 change points")
+    1 <= length(t.y) <= 65536 || error("DevicePoissonChangePoint: the device holds 1..65536 observations")
+    all(v -> isinteger(v) && 0 <= v <= 2^20, t.y) || error("DevicePoissonChangePoint: every y must be an integer count in 0..2^20")
+    ref = inputs.reference
+    ref isa ScaledPrecisionNormalLogPotential && ref.dim == K + 1 ||
+        error("the device change-point path needs reference = ScaledPrecisionNormalLogPotential(precision, $(K + 1)) (the prior of the log rates); keep the CPU path otherwise")
+    return (TARGET_CHANGE_POINT, 2 * K + 1, (ref.precision, 0.0, 0.0, 0.0))
 end
 device_family(t, inputs) = error("target $(typeof(t)) has no device log-potential family (closed set: include/pte.h PTE_TARGET_*); keep the CPU path")
 
@@ -301,6 +319,9 @@ function Pigeons.create_replicas(inputs::Inputs{<:OnDevice}, shared::Shared, sou
         lik = g.likelihood === :normal_identity ? GLM_NORMAL_IDENTITY : GLM_BERNOULLI_LOGIT
         check(r, ccall((:pte_set_target_varsel, libpte), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int32, Float64, Float64),
                        r.handle, collect(vec(permutedims(g.X))), g.y, length(g.y), size(g.X, 2), lik, g.noise_sd, g.inclusion_prob))
+    end
+    if t.target isa DevicePoissonChangePoint        # the counts as pte_set_target_changepoint reads them
+        check(r, ccall((:pte_set_target_changepoint, libpte), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), r.handle, t.target.y, length(t.target.y)))
     end
     source === nothing || restore!(r, source)          # FromCheckpoint: pte_set_state from the deserialised Replica structs
     return r

@@ -115,6 +115,15 @@ class Engine:
         self._chk(self.L.pte_set_target_varsel(self.h, _dp(Xa), _dp(ya), ya.size, Xa.shape[1], int(likelihood), float(noise_sd),
                                                float(inclusion_prob)))
 
+    def set_target_changepoint(self, y):
+        """pte_set_target_changepoint: y [n], integer counts"""
+        ya = np.ascontiguousarray(y, dtype=np.float64).ravel()
+        self._chk(self.L.pte_set_target_changepoint(self.h, _dp(ya), ya.size))
+
+    def set_changepoint_form(self, form):
+        """pte_set_changepoint_form: CHANGEPOINT_FORM_AUTO / _FULL / _CACHED, the same bits either way"""
+        self._chk(self.L.pte_set_changepoint_form(self.h, int(form)))
+
     # --- hot path
     def explore(self, scan):
         self._chk(self.L.pte_explore(self.h, scan))

@@ -248,6 +248,54 @@ class SpikeSlabRegression:
         return "SpikeSlabRegression(%s, n=%d, d=%d, inclusion_prob=%g)" % (self.likelihood, self.n_obs, self.n_columns, self.inclusion_prob)
 
 
+class PoissonChangePoint:
+    """Multiple change-point detection on count data: n counts y_i, K = n_changepoints change points, K + 1 segments with a
+    Poisson rate each.  The state is
+        [r_0..r_K, tau_1..tau_K]            (dim = 2 K + 1; the log rates Float64, the change points Integer stored as integral doubles)
+    every tau_k in 0..n and the taus unordered: with s_1 <= ... <= s_K the sorted taus, s_0 = 0 and s_{K+1} = n, segment j covers observations
+    [s_j, s_{j+1}) with y_i ~ Poisson(exp(r_j)); the prior is N(0, I / p) on r and uniform on the (n + 1)^K placements
+    (1 <= K <= 63, 1 <= n <= 65536, every y_i an integer in 0..2^20).  Tempered from reference=ScaledPrecisionNormalLogPotential(p, K + 1)
+    on r -- the prior, unnormalised -- times the uniform distribution on tau, to prior x likelihood; initialization = zeros(2 K + 1).  The
+    explorer is SliceSampler (target.jl:20) and nothing else: its Float64 method on the rates, its Integer method on the change points, so
+    its width w must be integral.
+
+    Evidence: stepping_stone(pt) estimates log p(y) - ((K+1)/2) log(2 pi / p) - K log(n + 1) (the reference has mass
+    (2 pi / p)^((K+1)/2) (n + 1)^K), so the log evidence is stepping_stone(pt) - evidence_offset(p): see evidence_offset."""
+
+    def __init__(self, y, n_changepoints):
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if y.ndim != 1 or not 1 <= y.size <= 65536:
+            raise ValueError("PoissonChangePoint: y must be a vector of 1..65536 observations (got shape %s)" % (y.shape,))
+        if not np.all(np.isfinite(y)) or np.any(y != np.floor(y)) or np.any(y < 0) or np.any(y > 2 ** 20):
+            raise ValueError("PoissonChangePoint: every y must be an integer count in 0..2^20")
+        K = int(n_changepoints)
+        if K != n_changepoints or not 1 <= K <= 63:
+            raise ValueError("PoissonChangePoint: the device gives every segment a lane of one wave, n_changepoints must be in 1..63 (got %r)"
+                             % (n_changepoints,))
+        self.y, self.n_changepoints = y, K
+
+    @property
+    def n_obs(self):
+        return self.y.size
+
+    @property
+    def n_rates(self):
+        return self.n_changepoints + 1
+
+    @property
+    def dim(self):
+        return 2 * self.n_changepoints + 1
+
+    def evidence_offset(self, precision):
+        """what stepping_stone(pt) is off the log evidence by: stepping_stone(pt) = log p(y) + evidence_offset(p), with
+        evidence_offset(p) = -((K+1)/2) log(2 pi / p) - K log(n + 1) and p the reference's precision"""
+        K = self.n_changepoints
+        return -((K + 1) / 2.0) * math.log(2.0 * math.pi / float(precision)) - K * math.log(self.n_obs + 1.0)
+
+    def __repr__(self):
+        return "PoissonChangePoint(n=%d, K=%d)" % (self.n_obs, self.n_changepoints)
+
+
 @dataclass
 class GaussianReference:
     """src/variational/GaussianReference.jl:4-17: mean-field Gaussian variational reference, refitted every round from
@@ -575,6 +623,14 @@ class PT:
             if not isinstance(explorer, SliceSampler):
                 raise NotImplementedError("the device variable-selection path is explored by SliceSampler only (got %r)" % (explorer,))
             kw.update(target=_lib.TARGET_VARIABLE_SELECTION, dim=target.dim, target_params=[ref.precision])
+        elif isinstance(target, PoissonChangePoint):
+            ref = inputs.reference
+            if not isinstance(ref, ScaledPrecisionNormalLogPotential) or ref.dim != target.n_rates:
+                raise NotImplementedError("the device change-point path needs reference=ScaledPrecisionNormalLogPotential(prec, K + 1) "
+                                          "-- the prior of the K + 1 log rates")
+            if not isinstance(explorer, SliceSampler):
+                raise NotImplementedError("the device change-point path is explored by SliceSampler only (got %r)" % (explorer,))
+            kw.update(target=_lib.TARGET_CHANGE_POINT, dim=target.dim, target_params=[ref.precision])
         else:
             raise NotImplementedError(
                 "target %r has no device log-potential; use the reference CPU path (Pigeons.jl)" % (target,))
@@ -645,6 +701,9 @@ class PT:
         if isinstance(target, SpikeSlabRegression):      # every engine (rank) holds the data
             for eng in (self.shards.engines if hasattr(self.shards, "engines") else [self.replicas]):
                 eng.set_target_varsel(target.likelihood_code, target.X, target.y, target.noise_sd, target.inclusion_prob)
+        if isinstance(target, PoissonChangePoint):       # every engine (rank) holds the data
+            for eng in (self.shards.engines if hasattr(self.shards, "engines") else [self.replicas]):
+                eng.set_target_changepoint(target.y)
 
 
 def next_round(pt):
