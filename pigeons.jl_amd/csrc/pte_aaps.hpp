@@ -22,16 +22,8 @@
 
 namespace pte {
 
-// rand(rng, 0:n-1) on Int64 (Random.SamplerRangeNDL, the oracle's po_rand_range): Lemire's nearly division-less sampler over rand(rng, UInt64)
-__device__ __forceinline__ int64_t rand_range0(SeqRng &r, uint64_t n) {
-    uint64_t x = r.next();
-    uint64_t low = x * n, hi = __umul64hi(x, n);
-    if (low < n) {
-        const uint64_t t = (0ULL - n) % n;
-        while (low < t) { x = r.next(); low = x * n; hi = __umul64hi(x, n); }
-    }
-    return (int64_t)hi;
-}
+// rand(rng, 0:n-1) on Int64 from the replica's sequential stream
+__device__ __forceinline__ int64_t rand_range0(SeqRng &r, uint64_t n) { return rand_range0_from([&]() { return r.next(); }, n); }
 
 template <int E, int TGT, bool FULL = false>
 __global__ __launch_bounds__(64) void k_explore_aaps(EngineDev e, AapsParams ap) {

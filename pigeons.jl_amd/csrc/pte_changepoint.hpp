@@ -22,18 +22,6 @@
 
 namespace pte {
 
-// rand(rng, 0:n-1) on Int64 (Random.SamplerRangeNDL, the oracle's po_rand_range; rand_range0 of pte_aaps.hpp) over any source of raw draws
-template <class Next>
-__device__ __forceinline__ int64_t rand_range0_from(Next next, uint64_t n) {
-    uint64_t x = next();
-    uint64_t low = x * n, hi = __umul64hi(x, n);
-    if (low < n) {
-        const uint64_t t = (0ULL - n) % n;
-        while (low < t) { x = next(); low = x * n; hi = __umul64hi(x, n); }
-    }
-    return (int64_t)hi;
-}
-
 // What one wave knows about its replica: the committed state and what the evaluation of it left.
 template <bool CACHED>
 struct ChangepointChain {
@@ -154,11 +142,9 @@ struct ChangepointChain {
     }
 };
 
-// One sweep of SliceSampler over the 2 K + 1 coordinates in state order, n_passes times (slice_sample! :43-62): the Float64 method
-// (slice_sample_coord! :89-95, slice_double, slice_shrink!, slice_accept) on the rates -- k_explore_varsel's statements -- and the Integer
-// method on the taus: initialize_slice_endpoints(::Integer) :136-142, the doubling on the lattice, draw_new_position = rand(rng, Lbar:Rbar)
-// :189 and Lbar == Rbar, statement for statement the oracle's mixed_coord_integer.  All control flow is uniform: every value it branches
-// on comes out of a wave reduction or a uniform draw.
+// One sweep of SliceSampler over the 2 K + 1 coordinates in state order, n_passes times (slice_sample! :43-62): the Float64 method on the
+// rates and the Integer method on the taus (slice_coord<double>, slice_coord<int64_t>: pte_slice_coord.hpp).  All control flow is uniform:
+// every value it branches on comes out of a wave reduction or a uniform draw.
 template <bool CACHED>
 __global__ __launch_bounds__(64) void k_explore_changepoint(EngineDev e, AmParams ap, ChangepointParams cp) {
     const int lane = lane_id();
@@ -196,115 +182,38 @@ __global__ __launch_bounds__(64) void k_explore_changepoint(EngineDev e, AmParam
 
     WaveDraws dr;
     dr.init(e.rng[2 * slot], e.rng[2 * slot + 1], lane);
-    long long steps_sum = 0; int steps_n = 0;
-    double acc_sum = 0.0; int acc_n = 0;
+    SliceTally tally;
     double lp = inside ? T.path_lp(T.com.S, T.com.ls) : -INFINITY;       // cached_log_potential (:32-41)
     if (lp == -INFINITY) { if (lane == 0) set_error(e, ERR_SLICE_SUPPORT, (int)c, -1); return; }
-    const double w = ap.slice_w, w11 = 1.1 * ap.slice_w;
-    const int64_t width = (int64_t)ceil(w);
+    const SliceKnobs kn{ap.slice_w, 1.1 * ap.slice_w, ap.slice_p, ap.slice_max_iter};
+    // coordinate idx for slice_coord (pte_slice_coord.hpp): rate idx, or the tau of lane ti
+    struct Coord {
+        Chain &T;
+        int idx, ti, rho;
+        bool is_rate;
+        typename Chain::TauMove mv;
+        typename Chain::Eval ev, cand;                           // of the last evaluation, of the proposal
+        __device__ __forceinline__ double eval(double v) { return is_rate ? T.eval_rate(idx, v, ev) : T.eval_tau(ti, rho, mv, v, ev); }
+        __device__ __forceinline__ void hold() { cand = ev; }
+        __device__ __forceinline__ void commit(double v) {
+            if (is_rate) T.r = T.lane == idx ? v : T.r; else T.tau = T.lane == ti ? (int)v : T.tau;
+            T.com = cand;
+        }
+    };
+    const int64_t width = (int64_t)ceil(kn.w);
     for (int pass = 0; pass < ap.slice_n_passes; ++pass) {
         for (int idx = 0; idx < 2 * K + 1; ++idx) {
             const bool is_rate = idx <= K;
             const int ti = idx - K - 1;                          // the tau's lane
             const double xold = is_rate ? readlane_f64(T.r, idx) : (double)__builtin_amdgcn_readlane(T.tau, max(ti, 0));
-            int rho = 0;
-            typename Chain::TauMove mv{};
+            Coord coord{T, idx, ti, 0, is_rate};
             if (CACHED && !is_rate) {
-                rho = (int)__builtin_ctzll(ballot64(lane < K && T.com.hi == (int)xold));
-                mv = T.tau_move(rho);
+                coord.rho = (int)__builtin_ctzll(ballot64(lane < K && T.com.hi == (int)xold));
+                coord.mv = T.tau_move(coord.rho);
             }
-            typename Chain::Eval ev;                             // of the last evaluation
-            auto eval = [&](double v) -> double { return is_rate ? T.eval_rate(idx, v, ev) : T.eval_tau(ti, rho, mv, v, ev); };
-            // slice_accept (:192-237), one body for both methods: on a tau every midpoint is integral (R - L = w 2^k, w integral)
-            auto accept = [&](double newpos, double z, double L, double R, double aL, double aR) -> bool {
-                double Lhat = L, Rhat = R;
-                bool Rstale = false, Lstale = false, D = false, take = true;
-                while (Rhat - Lhat > w11) {
-                    const double Mid = (Lhat + Rhat) / 2.0;
-                    if ((xold < Mid && newpos >= Mid) || (xold >= Mid && newpos < Mid)) D = true;
-                    if (newpos < Mid) { Rhat = Mid; Rstale = true; } else { Lhat = Mid; Lstale = true; }
-                    if (D) {
-                        if (Lstale) { aL = eval(Lhat); Lstale = false; }
-                        if (Rstale) { aR = eval(Rhat); Rstale = false; }
-                        if (z >= aL && z >= aR) { take = false; break; }
-                    }
-                }
-                acc_sum += take ? 1.0 : 0.0; acc_n += 1;
-                return take;
-            };
-            // coordinate idx ends at v, evaluated as cand
-            auto commit = [&](double v, const typename Chain::Eval &cand) {
-                if (is_rate) T.r = lane == idx ? v : T.r; else T.tau = lane == ti ? (int)v : T.tau;
-                T.com = cand;
-            };
-            double Ex;
-            {
-                const uint64_t raw = dr.next_raw(lane);
-                const uint64_t ri = raw & MASK52;
-                const int zi = (int)(ri & 0xFF);
-                Ex = (double)ri * ZIG_WE[zi];
-                if (!(ri < ZIG_KE[zi])) { SeqRng sq = dr.to_seq(); Ex = randexp_from_raw(sq, raw); dr.from_seq(sq, lane); }
-            }
-            const double z = lp - Ex;
-            bool done = false;
-            if (is_rate) {
-                double L = xold - w * dr.rand(lane);
-                double R = L + w;
-                int Kd = ap.slice_p;
-                double lp_L = eval(L), lp_R = eval(R);
-                while (Kd > 0 && (z < lp_L || z < lp_R)) {
-                    const double V = dr.rand(lane);
-                    if (V <= 0.5) { L = L - (R - L); lp_L = eval(L); }
-                    else { R = R + (R - L); lp_R = eval(R); }
-                    Kd -= 1;
-                }
-                steps_sum += ap.slice_p - Kd; steps_n += 1;
-                double Lbar = L, Rbar = R;
-                for (int it = 1; it <= ap.slice_max_iter; ++it) {
-                    const double newpos = Lbar + dr.rand(lane) * (Rbar - Lbar);
-                    const double newlp = eval(newpos);
-                    const typename Chain::Eval cand = ev;
-                    if (z < newlp && accept(newpos, z, L, R, lp_L, lp_R)) {
-                        commit(newpos, cand); lp = newlp;
-                        steps_sum += it; steps_n += 1; done = true; break;
-                    }
-                    if (newpos < xold) Lbar = newpos; else Rbar = newpos;
-                    if (jl_isapprox(Lbar, Rbar)) {
-                        lp = eval(xold);
-                        steps_sum += it; steps_n += 1; done = true; break;
-                    }
-                }
-            } else {
-                const int64_t old = (int64_t)xold;
-                int64_t L = old - rand_range0_from([&]() { return dr.next_raw(lane); }, (uint64_t)width + 1ull);
-                int64_t R = L + width;
-                int Kd = ap.slice_p;
-                double lp_L = eval((double)L), lp_R = eval((double)R);
-                while (Kd > 0 && (z < lp_L || z < lp_R)) {
-                    const double V = dr.rand(lane);
-                    if (V <= 0.5) { L = L - (R - L); lp_L = eval((double)L); }
-                    else { R = R + (R - L); lp_R = eval((double)R); }
-                    Kd -= 1;
-                }
-                steps_sum += ap.slice_p - Kd; steps_n += 1;
-                int64_t Lbar = L, Rbar = R;
-                for (int it = 1; it <= ap.slice_max_iter; ++it) {
-                    const int64_t newpos = Lbar + rand_range0_from([&]() { return dr.next_raw(lane); }, (uint64_t)(Rbar - Lbar) + 1ull);
-                    const double newlp = eval((double)newpos);
-                    const typename Chain::Eval cand = ev;
-                    if (z < newlp && accept((double)newpos, z, (double)L, (double)R, lp_L, lp_R)) {
-                        commit((double)newpos, cand); lp = newlp;
-                        steps_sum += it; steps_n += 1; done = true; break;
-                    }
-                    if (newpos < old) Lbar = newpos; else Rbar = newpos;
-                    if (Lbar == Rbar) {
-                        lp = eval(xold);
-                        steps_sum += it; steps_n += 1; done = true; break;
-                    }
-                }
-            }
-            if (!done) { if (lane == 0) set_error(e, ERR_SLICE_MAX_ITER, (int)c, idx); return; }
-            if (!isfinite(lp)) { if (lane == 0) set_error(e, ERR_SLICE_INVALID_LP, (int)c, idx); return; }
+            const int err = is_rate ? slice_coord<double>(coord, dr, lane, kn, tally, xold, kn.w, lp)
+                                    : slice_coord<int64_t>(coord, dr, lane, kn, tally, (int64_t)xold, width, lp);
+            if (err) { if (lane == 0) set_error(e, err, (int)c, idx); return; }
         }
     }
     if (lane <= K) xrow[lane] = T.r;
@@ -315,8 +224,8 @@ __global__ __launch_bounds__(64) void k_explore_changepoint(EngineDev e, AmParam
     if (lane == 0) {
         e.suff[slot] = fin.S; e.suff2[slot] = l2;
         e.rng[2 * slot] = dr.final_seed();
-        e.expl_steps_sum[cl] += (double)steps_sum; e.expl_steps_n[cl] += steps_n;
-        e.expl_acc_sum[cl] += acc_sum;             e.expl_acc_n[cl] += acc_n;
+        e.expl_steps_sum[cl] += (double)tally.steps_sum; e.expl_steps_n[cl] += tally.steps_n;
+        e.expl_acc_sum[cl] += tally.acc_sum;             e.expl_acc_n[cl] += tally.acc_n;
     }
     record_after_explore(e, cl, c, slot, lane, lp_before, fin.S, l2);
 }

@@ -123,8 +123,8 @@ struct VarselChain {
     }
 };
 
-// One sweep of SliceSampler over the 2 d coordinates in state order, n_passes times (slice_sample! :43-62): the Float64 method
-// (slice_sample_coord! :89-95, slice_double, slice_shrink!, slice_accept) on the thetas, the Bool method (:65-86) on the gammas.  The log
+// One sweep of SliceSampler over the 2 d coordinates in state order, n_passes times (slice_sample! :43-62): the Float64 method on the
+// thetas, the Bool method on the gammas (slice_coord<double>, slice_coord_bool: pte_slice_coord.hpp).  The log
 // potential of a proposal v for coordinate idx is evaluated from the cached predictor: with column c = idx mod d and b_old, b_new the
 // effective coefficient of c before and at the proposal, eta' = fma(X_c, b_new, fma(X_c, -b_old, eta)) -- or eta itself when b_new == b_old
 // (a theta whose indicator is off never touches the likelihood) -- and S, m follow the proposal.  When a coordinate is done its final value
@@ -174,108 +174,48 @@ __global__ __launch_bounds__(64) void k_explore_varsel(EngineDev e, AmParams ap,
 
     WaveDraws dr;
     dr.init(e.rng[2 * slot], e.rng[2 * slot + 1], lane);
-    long long steps_sum = 0; int steps_n = 0;
-    double acc_sum = 0.0; int acc_n = 0;
+    SliceTally tally;
     double lp = T.path_lp(T.S, T.m, T.ls);                     // cached_log_potential (:32-41)
     if (lp == -INFINITY) { if (lane == 0) set_error(e, ERR_SLICE_SUPPORT, (int)c, -1); return; }
-    const double w = ap.slice_w, w11 = 1.1 * ap.slice_w;
-    const bool tempered = T.beta != 0.0;                       // beta == 0: the path is the reference alone, eta is never read
+    const SliceKnobs kn{ap.slice_w, 1.1 * ap.slice_w, ap.slice_p, ap.slice_max_iter};
+    // coordinate idx (column col, committed at xold) for slice_coord / slice_coord_bool (pte_slice_coord.hpp)
+    struct Coord {
+        VarselChain<E, LIK, FULL> &T;
+        int idx, col;
+        bool is_theta, tempered;                               // beta == 0: the path is the reference alone, eta is never read
+        double xold, other, b_old;                             // other: the indicator of a theta, the theta of an indicator
+        double S_v, m_v, ls_v;                                 // the sums of the state with the coordinate at the last evaluated v
+        double S_h, m_h, ls_h;                                 // those of the proposal
+        __device__ __forceinline__ double eval(double v) {
+            double xv[E];
+#pragma unroll
+            for (int j = 0; j < E; ++j) xv[j] = (idx >> 6) == j && T.lane == (idx & 63) ? v : T.x[j];
+            const double b_new = is_theta ? other * v : v * other;
+            m_v = is_theta ? T.m : (T.m - xold) + v;
+            double lsum = 0.0;
+            const bool moved = tempered && b_new != b_old;
+            if (moved) lsum = T.column_pass(col, b_old, b_new);
+            T.sums(xv, lsum, S_v, ls_v);
+            if (!moved) ls_v = T.ls;
+            return T.path_lp(S_v, m_v, ls_v);
+        }
+        __device__ __forceinline__ void hold() { S_h = S_v; m_h = m_v; ls_h = ls_v; }
+        __device__ __forceinline__ void commit(double v) {
+            const double b_new = is_theta ? other * v : v * other;
+            if (tempered && b_new != b_old) T.column_commit(col, b_old, b_new);
+#pragma unroll
+            for (int j = 0; j < E; ++j) T.x[j] = (idx >> 6) == j && T.lane == (idx & 63) ? v : T.x[j];
+            T.S = S_h; T.m = m_h; T.ls = ls_h;
+        }
+    };
     for (int pass = 0; pass < ap.slice_n_passes; ++pass) {
         for (int idx = 0; idx < 2 * d; ++idx) {
             const bool is_theta = idx < d;
-            const int col = is_theta ? idx : idx - d;
             const double xold = T.get(T.x, idx);
-            const double other = T.get(T.x, is_theta ? idx + d : idx - d);      // the indicator of a theta, the theta of an indicator
-            const double b_old = is_theta ? other * xold : xold * other;
-            // the sums of the state with coordinate idx at v; S_v, m_v, ls_v stay those of the last call
-            double S_v = T.S, m_v = T.m, ls_v = T.ls;
-            auto eval = [&](double v) -> double {
-                double xv[E];
-#pragma unroll
-                for (int j = 0; j < E; ++j) xv[j] = (idx >> 6) == j && lane == (idx & 63) ? v : T.x[j];
-                const double b_new = is_theta ? other * v : v * other;
-                m_v = is_theta ? T.m : (T.m - xold) + v;
-                double lsum = 0.0;
-                const bool moved = tempered && b_new != b_old;
-                if (moved) lsum = T.column_pass(col, b_old, b_new);
-                T.sums(xv, lsum, S_v, ls_v);
-                if (!moved) ls_v = T.ls;
-                return T.path_lp(S_v, m_v, ls_v);
-            };
-            // coordinate idx ends at v, whose sums are S_f, m_f, ls_f
-            auto commit = [&](double v, double S_f, double m_f, double ls_f) {
-                const double b_new = is_theta ? other * v : v * other;
-                if (tempered && b_new != b_old) T.column_commit(col, b_old, b_new);
-#pragma unroll
-                for (int j = 0; j < E; ++j) T.x[j] = (idx >> 6) == j && lane == (idx & 63) ? v : T.x[j];
-                T.S = S_f; T.m = m_f; T.ls = ls_f;
-            };
-            if (!is_theta) {
-                // slice_sample_coord!(..., ::Type{Bool}): the full conditional, one evaluation at the flipped value, one rand(rng)
-                const bool on = xold != 0.0;
-                const double lpf = eval(on ? 0.0 : 1.0);
-                const double lp0 = on ? lpf : lp, lp1 = on ? lp : lpf;
-                const double prob_ratio = exp(lp1 - lp0);
-                const double prob_zero = 1.0 / (1.0 + prob_ratio);
-                const bool zero = dr.rand(lane) < prob_zero;
-                if (zero == on) { commit(zero ? 0.0 : 1.0, S_v, m_v, ls_v); lp = lpf; }
-                if (!isfinite(lp)) { if (lane == 0) set_error(e, ERR_SLICE_INVALID_LP, (int)c, idx); return; }
-                continue;
-            }
-            double Ex;
-            {
-                const uint64_t raw = dr.next_raw(lane);
-                const uint64_t ri = raw & MASK52;
-                const int ti = (int)(ri & 0xFF);
-                Ex = (double)ri * ZIG_WE[ti];
-                if (!(ri < ZIG_KE[ti])) { SeqRng sq = dr.to_seq(); Ex = randexp_from_raw(sq, raw); dr.from_seq(sq, lane); }
-            }
-            const double z = lp - Ex;
-            double L = xold - w * dr.rand(lane);
-            double R = L + w;
-            int K = ap.slice_p;
-            double lp_L = eval(L), lp_R = eval(R);
-            while (K > 0 && (z < lp_L || z < lp_R)) {
-                const double V = dr.rand(lane);
-                if (V <= 0.5) { L = L - (R - L); lp_L = eval(L); }
-                else { R = R + (R - L); lp_R = eval(R); }
-                K -= 1;
-            }
-            steps_sum += ap.slice_p - K; steps_n += 1;
-            double Lbar = L, Rbar = R;
-            bool done = false;
-            for (int n = 1; n <= ap.slice_max_iter; ++n) {
-                const double newpos = Lbar + dr.rand(lane) * (Rbar - Lbar);
-                const double newlp = eval(newpos);
-                const double S_n = S_v, m_n = m_v, ls_n = ls_v;
-                bool take = z < newlp;
-                if (take) {                              // slice_accept
-                    double Lhat = L, Rhat = R, aL = lp_L, aR = lp_R;
-                    bool Rstale = false, Lstale = false, D = false;
-                    while (Rhat - Lhat > w11) {
-                        const double Mid = (Lhat + Rhat) / 2.0;
-                        if ((xold < Mid && newpos >= Mid) || (xold >= Mid && newpos < Mid)) D = true;
-                        if (newpos < Mid) { Rhat = Mid; Rstale = true; } else { Lhat = Mid; Lstale = true; }
-                        if (D) {
-                            if (Lstale) { aL = eval(Lhat); Lstale = false; }
-                            if (Rstale) { aR = eval(Rhat); Rstale = false; }
-                            if (z >= aL && z >= aR) { take = false; break; }
-                        }
-                    }
-                    acc_sum += take ? 1.0 : 0.0; acc_n += 1;
-                }
-                if (take) {
-                    commit(newpos, S_n, m_n, ls_n); lp = newlp;
-                    steps_sum += n; steps_n += 1; done = true; break;
-                }
-                if (newpos < xold) Lbar = newpos; else Rbar = newpos;
-                if (jl_isapprox(Lbar, Rbar)) {
-                    lp = eval(xold);
-                    steps_sum += n; steps_n += 1; done = true; break;
-                }
-            }
-            if (!done) { if (lane == 0) set_error(e, ERR_SLICE_MAX_ITER, (int)c, idx); return; }
-            if (!isfinite(lp)) { if (lane == 0) set_error(e, ERR_SLICE_INVALID_LP, (int)c, idx); return; }
+            const double other = T.get(T.x, is_theta ? idx + d : idx - d);
+            Coord coord{T, idx, is_theta ? idx : idx - d, is_theta, T.beta != 0.0, xold, other, is_theta ? other * xold : xold * other, T.S, T.m, T.ls};
+            const int err = is_theta ? slice_coord<double>(coord, dr, lane, kn, tally, xold, kn.w, lp) : slice_coord_bool(coord, dr, lane, xold, lp);
+            if (err) { if (lane == 0) set_error(e, err, (int)c, idx); return; }
         }
     }
 #pragma unroll
@@ -285,8 +225,8 @@ __global__ __launch_bounds__(64) void k_explore_varsel(EngineDev e, AmParams ap,
     if (lane == 0) {
         e.suff[slot] = T.S; e.suff2[slot] = l2;
         e.rng[2 * slot] = dr.final_seed();
-        e.expl_steps_sum[cl] += (double)steps_sum; e.expl_steps_n[cl] += steps_n;
-        e.expl_acc_sum[cl] += acc_sum;             e.expl_acc_n[cl] += acc_n;
+        e.expl_steps_sum[cl] += (double)tally.steps_sum; e.expl_steps_n[cl] += tally.steps_n;
+        e.expl_acc_sum[cl] += tally.acc_sum;             e.expl_acc_n[cl] += tally.acc_n;
     }
     record_after_explore(e, cl, c, slot, lane, lp_before, T.S, l2);
 }

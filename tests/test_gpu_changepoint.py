@@ -34,9 +34,9 @@ def _data(n, K, seed=1):
     return g.poisson(rates[seg]).astype(np.float64)
 
 
-def _pt(P, y, K, prec, N, n_passes=3, record=(), **kw):
+def _pt(P, y, K, prec, N, n_passes=3, record=(), slice_kw=None, **kw):
     return P.PT(P.Inputs(target=P.PoissonChangePoint(y, K), reference=P.ScaledPrecisionNormalLogPotential(prec, K + 1), n_chains=N,
-                         n_rounds=2, explorer=P.SliceSampler(n_passes=n_passes), record=list(record), show_report=False, **kw))
+                         n_rounds=2, explorer=P.SliceSampler(n_passes=n_passes, **(slice_kw or {})), record=list(record), show_report=False, **kw))
 
 
 def _random_states(pt, N, K, n, seed, scale=1.0):
@@ -135,15 +135,23 @@ def test_log_density_at_every_beta(P, n, K):
         assert any(len(set(row)) < K for row in taus)
 
 
-@pytest.mark.parametrize("n,K,form", [(40, 3, "auto"), (200, 31, "auto"), (130, 32, "auto"), (300, 63, "auto"), (200, 31, "other")])
-def test_one_slice_transition_parity(P, n, K, form):
+_NARROW = dict(w=2.0, p=2)           # a first interval that the doubling cap p keeps from covering the slice (the default w = 10, p = 20 never
+                                     # binds); w stays integral: the Integer method's midpoints are integral only then
+
+
+_PARITY = [(40, 3, "auto", {}), (200, 31, "auto", {}), (130, 32, "auto", {}), (300, 63, "auto", {}), (200, 31, "other", {}),
+           (40, 3, "auto", _NARROW), (40, 3, "other", _NARROW)]
+
+
+@pytest.mark.parametrize("n,K,form,slice_kw", _PARITY, ids=["-".join(map(str, c[:3])) + ("-narrow" if c[3] else "") for c in _PARITY])
+def test_one_slice_transition_parity(P, n, K, form, slice_kw):
     """every replica's transition from its own RNG words against oracle.MixedSliceSampler on the restatement's call-back: the same draws in
     the same order (final RNG words equal), every Integer coordinate equal, the Float64 ones within X_RTOL, the explorer recorders equal;
-    the reference chain's i.i.d. draw: K + 1 normals, then rand(rng, 0:n) per tau.  The last case runs the evaluation form that the engine
-    does not choose by itself"""
+    the reference chain's i.i.d. draw: K + 1 normals, then rand(rng, 0:n) per tau.  The "other" cases run the evaluation form that the
+    engine does not choose by itself, the last two cases both forms with the doubling cut short at p = 2"""
     y = _data(n, K, seed=7 * n + K)
     N, prec, dim = 8, 0.5, 2 * K + 1
-    pt = _pt(P, y, K, prec, N)
+    pt = _pt(P, y, K, prec, N, slice_kw=slice_kw)
     eng = pt.replicas
     if form == "other":
         eng.set_changepoint_form(P._lib.CHANGEPOINT_FORM_FULL)      # (the engine's own choice is the cached form: DESIGN 4.13)
@@ -163,7 +171,7 @@ def test_one_slice_transition_parity(P, n, K, form):
             yv = np.array([r.randn() / math.sqrt(prec) for _ in range(K + 1)] + [float(r.rand_range(0, n)) for _ in range(K)])
             assert an[c] == 0 and sn[c] == 0
         else:
-            s = O.MixedSliceSampler(R.ChangePointChain(cp, betas[c], prec).path_lp, kinds)
+            s = O.MixedSliceSampler(R.ChangePointChain(cp, betas[c], prec).path_lp, kinds, **slice_kw)
             yv = x[i].copy()
             s.step(r, yv)
             assert an[c] == s.stats.acc_n and sn[c] == s.stats.steps_n and ss[c] == s.stats.steps_sum, (i, c)
@@ -173,6 +181,28 @@ def test_one_slice_transition_parity(P, n, K, form):
         assert np.array_equal(x1[i, K + 1:], yv[K + 1:]), (i, c, x1[i, K + 1:], yv[K + 1:])
         np.testing.assert_allclose(x1[i, :K + 1], yv[:K + 1], rtol=X_RTOL, atol=1e-12, err_msg="replica %d chain %d" % (i, c))
     assert moved > 0
+
+
+def test_the_shrink_cap_is_an_error_with_the_coordinate(P):
+    """slice_shrink!'s "Maximum number of iterations reached" (SliceSampler.jl:179-185): w = 4096 with max_iter = 2.  The oracle on the same
+    streams ends in its own error in every chain but the reference; the engine reports a tempered chain and one of the 2 K + 1 coordinates"""
+    n, K, N, prec = 40, 3, 8, 0.5
+    slice_kw = dict(w=4096.0, max_iter=2)
+    y = _data(n, K, seed=7 * n + K)
+    pt = _pt(P, y, K, prec, N, slice_kw=slice_kw)
+    betas, x, chain, rng = _random_states(pt, N, K, n, seed=n, scale=0.5)
+    cp = R.ChangePoint(y, K, prec)
+    kinds = np.array([O.COORD_FLOAT64] * (K + 1) + [O.COORD_INTEGER] * K, dtype=np.int32)
+    for i in range(N):
+        c = int(chain[i])
+        if c != 0:
+            s = O.MixedSliceSampler(R.ChangePointChain(cp, betas[c], prec).path_lp, kinds, **slice_kw)
+            with pytest.raises(RuntimeError, match="maximum number of iterations"):
+                s.step(O.OracleRng(state=(int(rng[i, 0]), int(rng[i, 1]))), x[i].copy())
+    eng = pt.replicas
+    with pytest.raises(P.PteError, match=r"Maximum number of iterations reached in slice_shrink! \(chain [1-7], index [0-6]\)"):
+        eng.explore(1)
+        eng.reduce()
 
 
 def test_both_forms_give_the_same_bits(P):

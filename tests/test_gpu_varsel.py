@@ -36,10 +36,10 @@ def _data(n, d, lik, seed=1, noise_sd=1.0):
     return X, y
 
 
-def _pt(P, X, y, lik, prec, N, pi=0.5, noise_sd=1.0, n_passes=3, record=(), **kw):
+def _pt(P, X, y, lik, prec, N, pi=0.5, noise_sd=1.0, n_passes=3, record=(), slice_kw=None, **kw):
     return P.PT(P.Inputs(target=P.SpikeSlabRegression(X, y, likelihood=lik, noise_sd=noise_sd, inclusion_prob=pi),
                          reference=P.ScaledPrecisionNormalLogPotential(prec, X.shape[1]), n_chains=N, n_rounds=2,
-                         explorer=P.SliceSampler(n_passes=n_passes), record=list(record), show_report=False, **kw))
+                         explorer=P.SliceSampler(n_passes=n_passes, **(slice_kw or {})), record=list(record), show_report=False, **kw))
 
 
 def _random_states(pt, N, d, seed, scale=1.5):
@@ -120,15 +120,22 @@ def test_log_density_at_every_beta(P, lik, n, d, pi):
         assert math.isclose(tr[c, 2 * d], want, rel_tol=LP_RTOL, abs_tol=1e-11), (c, betas[c], tr[c, 2 * d], want)
 
 
-@pytest.mark.parametrize("lik,n,d,pi", [("bernoulli_logit", 50, 3, 0.5), ("normal_identity", 70, 5, 0.3), ("bernoulli_logit", 130, 40, 0.2),
-                                        ("normal_identity", 90, 32, 0.5)])
-def test_one_slice_transition_parity(P, lik, n, d, pi):
+_NARROW = dict(w=0.25, p=3)          # a first interval that the doubling cap p keeps from covering the slice (the default w = 10, p = 20 never binds)
+
+
+_PARITY = [("bernoulli_logit", 50, 3, 0.5, {}), ("normal_identity", 70, 5, 0.3, {}), ("bernoulli_logit", 130, 40, 0.2, {}),
+           ("normal_identity", 90, 32, 0.5, {}), ("bernoulli_logit", 50, 3, 0.5, _NARROW), ("normal_identity", 70, 5, 0.3, _NARROW)]
+
+
+@pytest.mark.parametrize("lik,n,d,pi,slice_kw", _PARITY, ids=["-".join(map(str, c[:4])) + ("-narrow" if c[4] else "") for c in _PARITY])
+def test_one_slice_transition_parity(P, lik, n, d, pi, slice_kw):
     """every replica's transition from its own RNG words against oracle.MixedSliceSampler on the restatement's cached-predictor call-back:
     the same draws in the same order (final RNG words equal), every Bool coordinate equal, the Float64 ones within RTOL, the explorer
-    recorders equal (the Bool method records nothing); the reference chain's i.i.d. draw: d thetas, then d Bools"""
+    recorders equal (the Bool method records nothing); the reference chain's i.i.d. draw: d thetas, then d Bools.  The last two cases run
+    with the doubling cut short at p = 3"""
     X, y = _data(n, d, lik, seed=7 * n + d)
     N, prec = 10, 0.5
-    pt = _pt(P, X, y, lik, prec, N, pi=pi)
+    pt = _pt(P, X, y, lik, prec, N, pi=pi, slice_kw=slice_kw)
     betas, x, chain, rng = _random_states(pt, N, d, seed=n, scale=1.0)
     eng = pt.replicas
     eng.explore(1)
@@ -146,7 +153,7 @@ def test_one_slice_transition_parity(P, lik, n, d, pi):
             yv = np.array([r.randn() / math.sqrt(prec) for _ in range(d)] + [float(r.rand_bool()) for _ in range(d)])
             assert an[c] == 0 and sn[c] == 0
         else:
-            s = O.MixedSliceSampler(R.VarSelChain(vs, betas[c], prec).path_lp, kinds)
+            s = O.MixedSliceSampler(R.VarSelChain(vs, betas[c], prec).path_lp, kinds, **slice_kw)
             yv = x[i].copy()
             s.step(r, yv)
             assert an[c] == s.stats.acc_n and sn[c] == s.stats.steps_n and ss[c] == s.stats.steps_sum, (i, c)
@@ -156,6 +163,29 @@ def test_one_slice_transition_parity(P, lik, n, d, pi):
         assert np.array_equal(x1[i, d:], yv[d:]), (i, c, x1[i, d:], yv[d:])
         np.testing.assert_allclose(x1[i, :d], yv[:d], rtol=RTOL, atol=1e-12, err_msg="replica %d chain %d" % (i, c))
     assert flipped > 0
+
+
+def test_the_shrink_cap_is_an_error_with_the_coordinate(P):
+    """slice_shrink!'s "Maximum number of iterations reached" (SliceSampler.jl:179-185): w = 1000 with max_iter = 2.  The oracle on the same
+    streams ends in its own error in every chain but the reference; the engine reports a tempered chain and one of the thetas (the Bool
+    method has no cap)"""
+    n, d, N, prec = 50, 3, 8, 0.5
+    slice_kw = dict(w=1000.0, max_iter=2)
+    X, y = _data(n, d, "bernoulli_logit", seed=7 * n + d)
+    pt = _pt(P, X, y, "bernoulli_logit", prec, N, slice_kw=slice_kw)
+    betas, x, chain, rng = _random_states(pt, N, d, seed=n, scale=1.0)
+    vs = R.VarSel(X, y, "bernoulli_logit", 1.0, prec, 0.5)
+    kinds = np.array([O.COORD_FLOAT64] * d + [O.COORD_BOOL] * d, dtype=np.int32)
+    for i in range(N):
+        c = int(chain[i])
+        if c != 0:
+            s = O.MixedSliceSampler(R.VarSelChain(vs, betas[c], prec).path_lp, kinds, **slice_kw)
+            with pytest.raises(RuntimeError, match="maximum number of iterations"):
+                s.step(O.OracleRng(state=(int(rng[i, 0]), int(rng[i, 1]))), x[i].copy())
+    eng = pt.replicas
+    with pytest.raises(P.PteError, match=r"Maximum number of iterations reached in slice_shrink! \(chain [1-7], index [0-2]\)"):
+        eng.explore(1)
+        eng.reduce()
 
 
 # ---- whole runs ------------------------------------------------------------------------------------------------------------------------
