@@ -56,9 +56,17 @@ enum {
     PTE_TARGET_VARIABLE_SELECTION = 7,   /* spike-and-slab regression on data X, y (pte_set_target_varsel): the state is [theta, gamma],
                                             d Float64 coefficients then d Bool indicators stored as 0.0 / 1.0, dim = 2 d, d <= 256;
                                             SliceSampler only (its Float64 and Bool coordinate methods) */
-    PTE_TARGET_CHANGE_POINT = 8          /* K Poisson change points on n counts (pte_set_target_changepoint): the state is [r, tau],
+    PTE_TARGET_CHANGE_POINT = 8,         /* K Poisson change points on n counts (pte_set_target_changepoint): the state is [r, tau],
                                             K + 1 Float64 log rates then K Integer change points stored as integral doubles in 0..n,
                                             dim = 2 K + 1, K <= 63; SliceSampler only (its Float64 and Integer coordinate methods) */
+    PTE_TARGET_HIERARCHICAL_NORMAL = 9   /* InterpolatingPath(normal ref, hierarchical normal-means posterior of J group estimates;
+                                            pte_set_target_hier): the state is [mu, log tau, one coordinate per group], dim = J + 2 in
+                                            3..512; SliceSampler / AutoMALA / MALA / Compose of them */
+};
+/* PTE_TARGET_HIERARCHICAL_NORMAL: what the group coordinates are */
+enum {
+    PTE_HIER_CENTERED = 0,               /* x[2 + j] = theta_j ~ N(mu, tau^2)                                                       */
+    PTE_HIER_NONCENTERED = 1             /* x[2 + j] = eta_j ~ N(0, 1), theta_j = mu + tau eta_j                                    */
 };
 /* PTE_TARGET_BAYESIAN_GLM: the likelihood of each observation */
 enum {
@@ -251,6 +259,14 @@ int pte_set_target_glm(pte_engine *h, int32_t likelihood, int64_t n_obs, const d
  * statistics of the current states; may be called again to replace the data.  Until the first call pte_explore, pte_swap, pte_run_scans,
  * pte_group_run_scans and pte_get_state fail.  stepping_stone estimates log p(y) - (d/2) log(2 pi / p).  DESIGN 4.11. */
 int pte_set_target_mixture_model(pte_engine *h, int64_t n_obs, const double *y /*[n_obs]*/);
+/* PTE_TARGET_HIERARCHICAL_NORMAL: the data of the target N(mu; 0, mu_sd^2) HalfCauchy(tau; 0, tau_scale) tau prod_j N(theta_j; mu, tau^2)
+ * N(y_j; theta_j, sigma_j^2) in x = [mu, log tau, theta or eta] (parameterization PTE_HIER_*; the density is normalised in x).  Validates in
+ * this order (the engine's target; the parameterization; n_groups == dim - 2; y and sigma not NULL; every y[j] finite and sigma[j] positive
+ * and finite, in j; mu_sd, then tau_scale, positive and finite), uploads and refreshes the swap statistics of the current states; may be
+ * called again to replace the data.  Until the first call pte_explore, pte_swap, pte_run_scans, pte_group_run_scans and pte_get_state fail.
+ * stepping_stone estimates log p(y) - (d/2) log(2 pi / p), p = target_params[0] the reference's precision.  DESIGN 4.14. */
+int pte_set_target_hier(pte_engine *h, int32_t parameterization, int64_t n_groups, const double *y /*[n_groups]*/,
+                        const double *sigma /*[n_groups]*/, double mu_sd, double tau_scale);
 /* PTE_TARGET_VARIABLE_SELECTION: the data of the target N(theta; 0, I / p) prod_j pi^gamma_j (1 - pi)^(1 - gamma_j)
  * prod_i p(y_i | eta_i = sum_j X[i][j] gamma_j theta_j) (p = target_params[0], the reference's precision; pi = inclusion_prob; X row-major
  * [n_obs][d] with d = dim / 2; likelihood PTE_GLM_*, noise_sd read by PTE_GLM_NORMAL_IDENTITY only).  Validates as pte_set_target_glm does

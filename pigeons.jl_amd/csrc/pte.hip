@@ -26,6 +26,7 @@
 #include "pte_aaps_params.hpp"
 #include "pte_mixture_params.hpp"
 #include "pte_glm_params.hpp"
+#include "pte_hier_params.hpp"
 #include "pte_mixture_model_params.hpp"
 #include "pte_varsel_params.hpp"
 #include "pte_changepoint_params.hpp"
@@ -34,6 +35,7 @@
 #include "pte_aaps.hpp"
 #include "pte_mixture.hpp"
 #include "pte_glm.hpp"
+#include "pte_hier.hpp"
 #include "pte_mixture_model.hpp"
 #include "pte_varsel.hpp"
 #include "pte_changepoint.hpp"
@@ -109,6 +111,9 @@ struct pte_engine {
     double *d_changepoint = nullptr;    // PTE_TARGET_CHANGE_POINT: the prefix table C [65537], sized once for the largest n
     ChangepointParams changepoint{};    // the uploaded table as the kernels read it; changepoint.n = 0 until pte_set_target_changepoint
     int changepoint_form = CHANGEPOINT_FORM_AUTO;      // pte_set_changepoint_form
+    double *d_hier = nullptr;       // PTE_TARGET_HIERARCHICAL_NORMAL: y, 1 / sigma, log sigma, [512] each, by state coordinate
+    HierParams hier{};              // the uploaded data as the kernels read it; hier.n = 0 until pte_set_target_hier
+    int hier_param = 0;
     double step_size = 1.0;
     int am_n_refresh = 0;
     std::vector<double> fac_mean, rev_mean; std::vector<int64_t> fac_n, rev_n;
@@ -238,7 +243,8 @@ const PathFamily *path_family(int target) {
                             glm{"Bayesian-GLM", "data", "pte_set_target_glm", "one kernel serves it", "k_explore_glm"},
                             mixmodel{"mixture-model", "data", "pte_set_target_mixture_model", "one kernel serves it", "k_explore_mixture_model"},
                             varsel{"variable-selection", "data", "pte_set_target_varsel", "one kernel serves it", "k_explore_varsel"},
-                            changepoint{"change-point", "data", "pte_set_target_changepoint", "one kernel serves it", "k_explore_changepoint"};
+                            changepoint{"change-point", "data", "pte_set_target_changepoint", "one kernel serves it", "k_explore_changepoint"},
+                            hier{"hierarchical-normal", "data", "pte_set_target_hier", "one register-resident kernel serves it", "k_explore_hier"};
     switch (target) {
     case PTE_TARGET_FUNNEL: return &funnel;
     case PTE_TARGET_GAUSSIAN_MIXTURE: return &mixture;
@@ -246,6 +252,7 @@ const PathFamily *path_family(int target) {
     case PTE_TARGET_MIXTURE_MODEL: return &mixmodel;
     case PTE_TARGET_VARIABLE_SELECTION: return &varsel;
     case PTE_TARGET_CHANGE_POINT: return &changepoint;
+    case PTE_TARGET_HIERARCHICAL_NORMAL: return &hier;
     default: return nullptr;
     }
 }
@@ -258,6 +265,7 @@ bool family_ready(const pte_engine *h) {
     case PTE_TARGET_MIXTURE_MODEL: return h->mixmodel.n > 0;
     case PTE_TARGET_VARIABLE_SELECTION: return h->varsel.n > 0;
     case PTE_TARGET_CHANGE_POINT: return h->changepoint.n > 0;
+    case PTE_TARGET_HIERARCHICAL_NORMAL: return h->hier.n > 0;
     default: return true;
     }
 }
@@ -283,12 +291,13 @@ MixParams mixture_params(const pte_engine *h) {
 bool changepoint_cached(const pte_engine *h) { return h->changepoint_form != CHANGEPOINT_FORM_FULL; }
 
 // One launch of the engine's AutoMALA / MALA / SliceSampler-on-the-path kernel over N replicas (one workgroup each): the family's own on the
-// mixture, GLM and mixture-model paths, the Langevin family's on the funnel and scaled-precision MVN paths.  The open timing bracket's events ride on it.
+// mixture, GLM, mixture-model and hierarchical-normal paths, the Langevin family's on the funnel and scaled-precision MVN paths.  The open timing bracket's events ride on it.
 int launch_path_kernel(pte_engine *h, int E, bool slice, bool full, int64_t N, const AmParams &ap) {
     const LaunchSite at = launch_site(h, (unsigned)N);
     switch (h->cfg.target) {
     case PTE_TARGET_GAUSSIAN_MIXTURE: return mixture_launch(MixtureLaunch{E, slice, full, at}, h->dev, ap, mixture_params(h)) ? family_no_kernel_error(h) : 0;
     case PTE_TARGET_BAYESIAN_GLM: return glm_launch(GlmLaunch{E, h->glm_lik, slice, full, at}, h->dev, ap, h->glm) ? family_no_kernel_error(h) : 0;
+    case PTE_TARGET_HIERARCHICAL_NORMAL: return hier_launch(HierLaunch{E, h->hier_param, slice, full, at}, h->dev, ap, h->hier) ? family_no_kernel_error(h) : 0;
     case PTE_TARGET_MIXTURE_MODEL: return mixture_model_launch(MixModelLaunch{(int)(h->d / 3), slice, at}, h->dev, ap, h->mixmodel) ? family_no_kernel_error(h) : 0;
     case PTE_TARGET_VARIABLE_SELECTION:      // SliceSampler alone (validate_config); whole blocks: 2 d == 64 E
         return varsel_launch(VarselLaunch{E, h->varsel_lik, h->d == 64 * (int64_t)E, at}, h->dev, ap, h->varsel) ? family_no_kernel_error(h) : 0;
@@ -311,6 +320,7 @@ int refresh_path_stats(pte_engine *h) {
     case PTE_TARGET_FUNNEL: langevin_refresh_funnel_stats(E, N, h->stream, h->dev, std::log(3.0)); break;
     case PTE_TARGET_GAUSSIAN_MIXTURE: if (mixture_refresh_stats(E, N, h->stream, h->dev, mixture_params(h))) return family_no_kernel_error(h); break;
     case PTE_TARGET_BAYESIAN_GLM: if (glm_refresh_stats(E, h->glm_lik, N, h->stream, h->dev, h->glm, h->cfg.target_params[0])) return family_no_kernel_error(h); break;
+    case PTE_TARGET_HIERARCHICAL_NORMAL: if (hier_refresh_stats(E, h->hier_param, N, h->stream, h->dev, h->hier)) return family_no_kernel_error(h); break;
     case PTE_TARGET_MIXTURE_MODEL: if (mixture_model_refresh_stats((int)(h->d / 3), N, h->stream, h->dev, h->mixmodel, h->cfg.target_params[0])) return family_no_kernel_error(h); break;
     case PTE_TARGET_VARIABLE_SELECTION: if (varsel_refresh_stats(E, h->varsel_lik, N, h->stream, h->dev, h->varsel, h->cfg.target_params[0])) return family_no_kernel_error(h); break;
     case PTE_TARGET_CHANGE_POINT: if (changepoint_refresh_stats(N, h->stream, h->dev, h->changepoint, h->cfg.target_params[0])) return family_no_kernel_error(h); break;
@@ -1022,13 +1032,15 @@ int validate_config(const pte_config *cfg) {
         if (cfg->slice_w != std::floor(cfg->slice_w) || !std::isfinite(cfg->slice_w))      // SliceSampler.jl:137 (@assert), the oracle's text
             return fail(nullptr, "pte_create: for integer variables, the width should be an integer. Got: %g", cfg->slice_w);
     }
-    if (family && !funnel) {    // the families with kernels of their own -- Gaussian mixture, Bayesian GLM, mixture model: one wave per replica, SliceSampler / AutoMALA / MALA (AAPS: refused above)
+    if (family && !funnel) {    // the families with kernels of their own -- Gaussian mixture, Bayesian GLM, mixture model, hierarchical normal means: one wave per replica, SliceSampler / AutoMALA / MALA (AAPS: refused above)
         auto on_family = [](int k) { return k == PTE_EXPLORER_SLICE || k == PTE_EXPLORER_AUTOMALA || k == PTE_EXPLORER_MALA; };
         if (!on_family(cfg->explorer) || (cfg->explorer2 != PTE_EXPLORER_NONE && !on_family(cfg->explorer2)))
             return fail(nullptr, "pte_create: the %s path is implemented for SliceSampler / AutoMALA / MALA (and Compose of them) only (got explorers %d, %d)",
                         family->name, cfg->explorer, cfg->explorer2);
         if (cfg->target == PTE_TARGET_MIXTURE_MODEL && (cfg->dim < 3 || cfg->dim > 24 || cfg->dim % 3 != 0))
             return fail(nullptr, "pte_create: the mixture-model path holds theta = [mu, s, alpha] of 1..8 components, dim must be in {3, 6, ..., 24} (got %lld)", (long long)cfg->dim);
+        if (cfg->target == PTE_TARGET_HIERARCHICAL_NORMAL && (cfg->dim < 3 || cfg->dim > 512))
+            return fail(nullptr, "pte_create: the hierarchical-normal path holds [mu, log tau] and 1..510 group coordinates, dim must be in 3..512 (got %lld)", (long long)cfg->dim);
         if (cfg->dim < 1 || cfg->dim > 512)
             return fail(nullptr, "pte_create: the %s path keeps the replica in the registers of one wave, dim must be in 1..512 (got %lld)", family->name, (long long)cfg->dim);
         if ((cfg->debug_kernel & ~(PTE_KERNEL_FLAG_BITS | PTE_KERNEL_TEST_BITS)) != 0)
@@ -2142,6 +2154,46 @@ int pte_set_target_glm(pte_engine *h, int32_t likelihood, int64_t n_obs, const d
     g.w1 = likelihood == PTE_GLM_NORMAL_IDENTITY ? 1.0 / (noise_sd * noise_sd) : 0.0;
     g.w2 = likelihood == PTE_GLM_NORMAL_IDENTITY ? 1.0 / (2.0 * (noise_sd * noise_sd)) : 0.0;
     h->glm_lik = likelihood;
+    return refresh_path_stats(h);                                  // suff / suff2 of the current states
+}
+
+// The hierarchical normal-means posterior.  Host, once per call: 1 / sigma_j, log sigma_j, 1 / mu_sd, log mu_sd,
+// log 2 - log pi - log tau_scale, 1 / tau_scale; y, 1 / sigma and log sigma are uploaded indexed by state coordinate (entries 0, 1 and d.. zero)
+// into one allocation of 3 x 512 doubles.
+int pte_set_target_hier(pte_engine *h, int32_t parameterization, int64_t n_groups, const double *y, const double *sigma, double mu_sd, double tau_scale) {
+    if (!h) return 1;
+    PTE_ALIVE(h, "pte_set_target_hier");
+    if (h->cfg.target != PTE_TARGET_HIERARCHICAL_NORMAL)
+        return fail(h, "pte_set_target_hier: this engine's target is %d, not PTE_TARGET_HIERARCHICAL_NORMAL", h->cfg.target);
+    if (parameterization != PTE_HIER_CENTERED && parameterization != PTE_HIER_NONCENTERED)
+        return fail(h, "pte_set_target_hier: parameterization must be PTE_HIER_CENTERED (0) or PTE_HIER_NONCENTERED (1) (got %d)", parameterization);
+    const int64_t d = h->d;
+    if (n_groups != d - 2)
+        return fail(h, "pte_set_target_hier: n_groups must be dim - 2 = %lld (got %lld)", (long long)(d - 2), (long long)n_groups);
+    if (!y || !sigma) return fail(h, "pte_set_target_hier: null argument");
+    for (int64_t j = 0; j < n_groups; ++j) {
+        if (!std::isfinite(y[j])) return fail(h, "pte_set_target_hier: y[%lld] must be finite (got %g)", (long long)j, y[j]);
+        if (!(sigma[j] > 0) || !std::isfinite(sigma[j]))
+            return fail(h, "pte_set_target_hier: sigma[%lld] must be positive and finite (got %g)", (long long)j, sigma[j]);
+    }
+    if (!(mu_sd > 0) || !std::isfinite(mu_sd)) return fail(h, "pte_set_target_hier: mu_sd must be positive and finite (got %g)", mu_sd);
+    if (!(tau_scale > 0) || !std::isfinite(tau_scale)) return fail(h, "pte_set_target_hier: tau_scale must be positive and finite (got %g)", tau_scale);
+    HIP_OK(h, hipSetDevice(h->cfg.device));
+    std::vector<double> buf((size_t)(3 * HIER_DATA_LEN), 0.0);
+    for (int64_t j = 0; j < n_groups; ++j) {
+        buf[(size_t)(2 + j)] = y[j];
+        buf[(size_t)(HIER_DATA_LEN + 2 + j)] = 1.0 / sigma[j];
+        buf[(size_t)(2 * HIER_DATA_LEN + 2 + j)] = std::log(sigma[j]);
+    }
+    if (!h->d_hier && dev_alloc(h, &h->d_hier, buf.size(), false)) return 1;
+    HIP_OK(h, hipMemcpyAsync(h->d_hier, buf.data(), sizeof(double) * buf.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    HierParams &p = h->hier;
+    p.y = h->d_hier; p.isig = h->d_hier + HIER_DATA_LEN; p.lsig = h->d_hier + 2 * HIER_DATA_LEN;
+    p.n = (int)n_groups;
+    p.imu = 1.0 / mu_sd; p.lmu = std::log(mu_sd);
+    p.c_tau = std::log(2.0) - std::log(M_PI) - std::log(tau_scale); p.its = 1.0 / tau_scale;
+    h->hier_param = parameterization;
     return refresh_path_stats(h);                                  // suff / suff2 of the current states
 }
 

@@ -14,10 +14,13 @@
 //              that reads data -- through LDS, outside the register-only scheme above
 //   TGT_MIXMODEL the same path with prior x likelihood of a finite mixture model given data y as the target (DESIGN 4.11;
 //              pte_mixture_model.hpp): theta = [mu, s, alpha] in one block, lanes over observations, K <= KB components
+//   TGT_HIER   the same path with a hierarchical normal-means posterior as the target, LIK = HIER_* the parameterisation (DESIGN 4.14;
+//              pte_hier.hpp): x = [mu, log tau, one coordinate per group], elementwise but for the two hyper-parameters' gradient sums
 #pragma once
 #include "pte_automala_params.hpp"
 #include "pte_glm_params.hpp"
 #include "pte_mixture_model_params.hpp"
+#include "pte_hier_params.hpp"
 #include "pte_slice_coord.hpp"
 
 namespace pte {
@@ -108,9 +111,17 @@ template <> struct AmGlmData<true> { GlmParams gl; double *glds; };
 // TGT_MIXMODEL's data and its number of components (d / 3): the same arrangement
 template <bool ON> struct AmMixModelData {};
 template <> struct AmMixModelData<true> { MixModelParams mm; int mk; };
+// TGT_HIER's data: the same arrangement.  y, 1 / sigma and log sigma of this lane's coordinates stay in registers for the replica's
+// lifetime at E <= 2 (3 E doubles); from E = 4 on they are read again from L2 in every evaluation
+template <bool ON, int E> struct AmHierData {};
+template <int E> struct AmHierData<true, E> {
+    static constexpr bool H_IN_REGS = (E <= 2);
+    HierParams hp;
+    double hy[H_IN_REGS ? E : 1], his[H_IN_REGS ? E : 1], hls[H_IN_REGS ? E : 1];
+};
 
 template <int E, int TGT, bool FULL = false, int KB = 1, int LIK = 0>
-struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL> {
+struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>, AmHierData<TGT == TGT_HIER, E> {
     int64_t d; int lane;
     double nhp, nprec;          // MVN: -0.5*prec, -prec of this chain
     double beta, omb, ref_nhp, ref_nprec, log3;   // funnel path
@@ -431,9 +442,77 @@ struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>
         double S, Q, dummy[E];
         return mixmodel_and_sqr_norm<false, false>(x, dummy, S, x, Q);
     }
+    // the hierarchical normal-means posterior: x = [mu, lt = log tau, x_2 .. x_{J+1}], LIK = HIER_CENTERED (x_{2+j} = theta_j) or
+    // HIER_NONCENTERED (x_{2+j} = eta_j, theta_j = mu + tau eta_j).  The density is one sum over the fixed tree with the leaves in state order:
+    // leaf 0 the prior of mu, leaf 1 the half-Cauchy of tau with the Jacobian of lt, leaf 2 + j = log N(y_j; theta_j, sigma_j^2) + the group
+    // coordinate's prior.  tau = exp(lt), 1 / tau = exp(-lt) and log1p((tau / tau_scale)^2) are computed once, on the value lanes 0 and 1 of
+    // block 0 hold.  GRAD: the group coordinates' derivatives are elementwise; those of mu and lt are two more sums over the same tree, in
+    // lockstep with the density, S = sum x^2 and (WITH_Q) Q = sum q^2.  Lanes past d are masked by index and contribute exactly 0.
+    __device__ __forceinline__ void load_hier(const HierParams &h) {
+        this->hp = h;
+        if constexpr (AmHierData<true, E>::H_IN_REGS) {
+#pragma unroll
+            for (int j = 0; j < E; ++j) { this->hy[j] = h.y[64 * j + lane]; this->his[j] = h.isig[64 * j + lane]; this->hls[j] = h.lsig[64 * j + lane]; }
+        }
+    }
+    template <bool GRAD, bool WITH_Q>
+    __device__ __forceinline__ double hier_and_sqr_norm(const double (&x)[E], double (&g)[E], double &S, const double (&q)[E], double &Q) const {
+        constexpr bool NC = (LIK == HIER_NONCENTERED);
+        constexpr bool IN_REGS = AmHierData<true, E>::H_IN_REGS;
+        const HierParams &hp = this->hp;
+        const double LOG2PI = 1.8378770664093453;
+        const double mu = readlane_f64(x[0], 0), lt = readlane_f64(x[0], 1);
+        const double tau = exp(lt);
+        const double itau = NC ? 0.0 : exp(-lt);
+        const double ts = tau * hp.its, r = ts * ts;
+        constexpr int K = 2 + (GRAD ? 2 : 0) + (WITH_Q ? 1 : 0), KM = 2, KT = 3, KQ = GRAD ? 4 : 2;
+        double t[K][E], out[K];
+#pragma unroll
+        for (int j = 0; j < E; ++j) {
+            const bool grp = (j > 0 || lane >= 2) && valid(j);          // this lane's coordinate of block j is a group's
+            double yj, is, ls;
+            if constexpr (IN_REGS) { yj = this->hy[j]; is = this->his[j]; ls = this->hls[j]; }
+            else { yj = hp.y[64 * j + lane]; is = hp.isig[64 * j + lane]; ls = hp.lsig[64 * j + lane]; }      // ([512]: in bounds whatever d)
+            const double xj = x[j];
+            t[0][j] = xj * xj;
+            double lf, gj, gm, gt;
+            if constexpr (NC) {
+                const double th = mu + tau * xj;
+                const double z = (yj - th) * is, zi = z * is, zt = zi * tau;
+                lf = (-(z * z + LOG2PI) / 2.0 - ls) + (-(xj * xj + LOG2PI) / 2.0);
+                gj = zt - xj; gm = zi; gt = zt * xj;
+            } else {
+                const double z = (yj - xj) * is, u = (xj - mu) * itau, ui = u * itau;
+                lf = (-(z * z + LOG2PI) / 2.0 - ls) + (-(u * u + LOG2PI) / 2.0 - lt);
+                gj = z * is - ui; gm = ui; gt = u * u - 1.0;
+            }
+            t[1][j] = grp ? lf : 0.0;
+            if (GRAD) { g[j] = grp ? gj : 0.0; t[KM % K][j] = grp ? gm : 0.0; t[KT % K][j] = grp ? gt : 0.0; }
+            if (WITH_Q) t[KQ % K][j] = q[j] * q[j];
+        }
+        const double m = mu * hp.imu;
+        if (lane == 0) { t[1][0] = -(m * m + LOG2PI) / 2.0 - hp.lmu; if (GRAD) t[KM % K][0] = -m * hp.imu; }
+        if (lane == 1) { t[1][0] = (hp.c_tau - log1p(r)) + lt; if (GRAD) t[KT % K][0] = 1.0 - (2.0 * r) / (1.0 + r); }
+        tree_sum_regs_multi<E, K>(t, out);
+        S = out[0];
+        if (GRAD) g[0] = lane == 0 ? out[KM % K] : lane == 1 ? out[KT % K] : g[0];
+        if (WITH_Q) Q = out[KQ % K];
+        return out[1];
+    }
+    __device__ __forceinline__ double hier(const double (&x)[E]) const {
+        double S, Q, dummy[E];
+        return hier_and_sqr_norm<false, false>(x, dummy, S, x, Q);
+    }
     // log_potentials[chain](x) as a plain callable: InterpolatedLogPotential(x) (src/paths/InterpolatedLogPotential.jl:9-16)
     // WITH its beta == 0 / beta == 1 short-circuits -- what SliceSampler evaluates (the AD form below has none)
     __device__ __forceinline__ double path_lp(const double (&x)[E]) const {
+        if constexpr (TGT == TGT_HIER) {
+            if (beta == 0.0) return ref_nhp * sqr_norm_regs<E>(x);
+            double S, Q, dummy[E];
+            const double l2 = hier_and_sqr_norm<false, false>(x, dummy, S, x, Q);
+            if (beta == 1.0) return l2;
+            return omb * (ref_nhp * S) + beta * l2;
+        }
         if constexpr (TGT == TGT_MIXMODEL) {
             if (beta == 0.0) return ref_nhp * sqr_norm_regs<E>(x);
             double S, Q, dummy[E];
@@ -467,6 +546,10 @@ struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>
     __device__ __forceinline__ double logdensity(const double (&x)[E]) const {
         if (TGT == TGT_MVN) return nhp * sqr_norm_regs<E>(x);
         double S, l2, dummy[E], dq;
+        if constexpr (TGT == TGT_HIER) {
+            l2 = hier_and_sqr_norm<false, false>(x, dummy, S, x, dq);
+            return omb * (ref_nhp * S) + beta * l2;
+        }
         if constexpr (TGT == TGT_MIXMODEL) {
             l2 = mixmodel_and_sqr_norm<false, false>(x, dummy, S, x, dq);
             return omb * (ref_nhp * S) + beta * l2;
@@ -503,6 +586,14 @@ struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>
         double logdens = 0.0;
         double g2[E];
         double l2;
+        if constexpr (TGT == TGT_HIER) {
+            l2 = hier_and_sqr_norm<true, WITH_Q>(x, g2, S, q, Q);
+            logdens += (ref_nhp * S) * omb;
+            logdens += l2 * beta;
+#pragma unroll
+            for (int j = 0; j < E; ++j) g[j] = (ref_nprec * x[j]) * omb + g2[j] * beta;
+            return logdens;
+        }
         if constexpr (TGT == TGT_MIXMODEL) {
             l2 = mixmodel_and_sqr_norm<true, WITH_Q>(x, g2, S, q, Q);
             logdens += (ref_nhp * S) * omb;
@@ -565,9 +656,11 @@ __device__ __forceinline__ int64_t am_chain_of_workgroup(int64_t K, int64_t wg) 
 // wave-level wait instead of a workgroup barrier -- every wave writes all the (identical) entries itself, so it only has to see its own stores
 // KB, mp: TGT_MIXTURE only -- the components' bucket (K <= KB) and parameters.  LIK, gp: TGT_GLM only -- the likelihood and the data
 // (the workgroup's dynamic LDS holds theta and r: pte_glm.hpp).  mm: TGT_MIXMODEL only -- the observations (pte_mixture_model.hpp)
+// hp: TGT_HIER only -- the groups' data, LIK its parameterisation (pte_hier.hpp)
 template <int E, int TGT, bool SLICE = false, bool FULL = false, bool DIRECT = false, int KB = 1, int LIK = 0>
 __device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const int64_t wg, const MixParams &mp = MixParams{},
-                                              const GlmParams &gp = GlmParams{}, const MixModelParams &mm = MixModelParams{}) {      // wg: blockIdx.x
+                                              const GlmParams &gp = GlmParams{}, const MixModelParams &mm = MixModelParams{},
+                                              const HierParams &hp = HierParams{}) {      // wg: blockIdx.x
     constexpr int NLU = (E == 1 ? 0 : E == 2 ? 1 : E == 4 ? 2 : E == 8 ? 3 : 4);
     const int lane = lane_id();
     // the ziggurat tables of the momentum draws, staged once: a global gather per block of draws costs a memory round trip each time
@@ -593,6 +686,7 @@ __device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const in
         T.gl = gp; T.glds = glm_lds;
     }
     if constexpr (TGT == TGT_MIXMODEL) { T.mm = mm; T.mk = (int)(d / 3); }
+    if constexpr (TGT == TGT_HIER) T.load_hier(hp);
     T.nhp = e.nhp[c]; T.nprec = e.nprec[c];
     T.beta = e.beta[c]; T.omb = 1.0 - T.beta;
     T.ref_nhp = -0.5 * ap.ref_prec; T.ref_nprec = -ap.ref_prec; T.log3 = ap.log3;
@@ -641,6 +735,10 @@ __device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const in
         }
         if constexpr (TGT == TGT_MIXMODEL) {
             l20 = T.mixmodel(x);
+            if (lane == 0) e.suff2[slot] = l20;
+        }
+        if constexpr (TGT == TGT_HIER) {
+            l20 = T.hier(x);
             if (lane == 0) e.suff2[slot] = l20;
         }
         record_after_explore_impl(e, cl, c, slot, lane, lp0, S0, l20, l30);
@@ -916,10 +1014,11 @@ __device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const in
     if (TGT == TGT_MIXTURE) l2 = T.mixture(x);
     if constexpr (TGT == TGT_GLM) l2 = T.glm(x);
     if constexpr (TGT == TGT_MIXMODEL) l2 = T.mixmodel(x);
+    if constexpr (TGT == TGT_HIER) l2 = T.hier(x);
     if (v_on) l3 = T.variational_lp(x);
     if (lane == 0) {
         e.suff[slot] = S;
-        if (TGT == TGT_FUNNEL || TGT == TGT_MIXTURE || TGT == TGT_GLM || TGT == TGT_MIXMODEL) e.suff2[slot] = l2;
+        if (TGT == TGT_FUNNEL || TGT == TGT_MIXTURE || TGT == TGT_GLM || TGT == TGT_MIXMODEL || TGT == TGT_HIER) e.suff2[slot] = l2;
         if (v_on) e.suff3[slot] = l3;
         e.rng[2 * slot] = r.seed;
         e.expl_steps_sum[cl] += (double)steps_sum; e.expl_steps_n[cl] += steps_n;

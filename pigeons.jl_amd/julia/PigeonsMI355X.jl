@@ -39,6 +39,8 @@ const TARGET_BAYESIAN_GLM = Int32(5)
 const TARGET_MIXTURE_MODEL = Int32(6)
 const TARGET_VARIABLE_SELECTION = Int32(7)
 const TARGET_CHANGE_POINT = Int32(8)
+const TARGET_HIERARCHICAL_NORMAL = Int32(9)
+const HIER_CENTERED, HIER_NONCENTERED = Int32(0), Int32(1)
 const GLM_BERNOULLI_LOGIT, GLM_NORMAL_IDENTITY = Int32(0), Int32(1)
 const EXPLORER_NONE, EXPLORER_TOY, EXPLORER_SLICE, EXPLORER_AUTOMALA, EXPLORER_ISING, EXPLORER_MALA, EXPLORER_AAPS = Int32.((0, 1, 2, 3, 4, 5, 6))
 const RECORD_ROUND_TRIP, RECORD_INDEX_PROCESS, RECORD_ONLINE, RECORD_TRACES, RECORD_ENERGY_AC1, RECORD_TRACES_EXTENDED =
@@ -135,6 +137,12 @@ unordered -- segment j lies between the j-th and (j+1)-th smallest -- with prior
 SliceSampler())` -- SliceSampler is the one explorer of this family, and its width must be integral.
 stepping_stone(pt) + ((K+1)/2) log(2 pi / p) + K log(n + 1) is the log evidence."""
 struct DevicePoissonChangePoint; y::Vector{Float64}; n_changepoints::Int; end
+"""The posterior of a hierarchical normal-means model ("eight schools"), the device family PTE_TARGET_HIERARCHICAL_NORMAL (DESIGN 4.14):
+J group estimates `y` with known standard errors `sigma`, theta_j ~ N(mu, tau^2), mu ~ N(0, mu_sd^2), tau ~ HalfCauchy(0, tau_scale); the
+state is [mu; log tau; theta] (`parameterization = :centered`) or [mu; log tau; eta] with theta = mu .+ tau .* eta (`:noncentered`),
+dim = J + 2 <= 512.  Used as `Inputs(target = on_mi355x(DeviceHierarchicalNormalMeans(y, sigma, 5.0, 5.0, :noncentered)), reference =
+ScaledPrecisionNormalLogPotential(p, J + 2))`.  stepping_stone(pt) + (dim/2) log(2 pi / p) is the log evidence."""
+struct DeviceHierarchicalNormalMeans; y::Vector{Float64}; sigma::Vector{Float64}; mu_sd::Float64; tau_scale::Float64; parameterization::Symbol; end
 
 # (target code, dim, target_params, reference precision check) of a wrapped target
 device_family(t::ScaledPrecisionNormalPath, inputs) = (TARGET_MVN, t.dim, (t.precision0, t.precision1, 0.0, 0.0))
@@ -171,6 +179,16 @@ function device_family(t::DeviceMixtureModelPosterior, inputs)
     ref isa ScaledPrecisionNormalLogPotential && ref.dim == dim ||
         error("the device mixture-model path needs reference = ScaledPrecisionNormalLogPotential(precision, $dim) (the prior); keep the CPU path otherwise")
     return (TARGET_MIXTURE_MODEL, dim, (ref.precision, 0.0, 0.0, 0.0))
+end
+function device_family(t::DeviceHierarchicalNormalMeans, inputs)
+    1 <= length(t.y) <= 510 || error("DeviceHierarchicalNormalMeans: the device holds 1..510 groups")
+    length(t.sigma) == length(t.y) || error("DeviceHierarchicalNormalMeans: sigma has one standard error per group")
+    t.parameterization in (:centered, :noncentered) || error("DeviceHierarchicalNormalMeans: parameterization :centered or :noncentered")
+    dim = length(t.y) + 2
+    ref = inputs.reference
+    ref isa ScaledPrecisionNormalLogPotential && ref.dim == dim ||
+        error("the device hierarchical-normal path needs reference = ScaledPrecisionNormalLogPotential(precision, $dim); keep the CPU path otherwise")
+    return (TARGET_HIERARCHICAL_NORMAL, dim, (ref.precision, 0.0, 0.0, 0.0))
 end
 function device_family(t::DeviceSpikeSlabRegression, inputs)
     n, d = size(t.X)
@@ -319,6 +337,12 @@ function Pigeons.create_replicas(inputs::Inputs{<:OnDevice}, shared::Shared, sou
         lik = g.likelihood === :normal_identity ? GLM_NORMAL_IDENTITY : GLM_BERNOULLI_LOGIT
         check(r, ccall((:pte_set_target_varsel, libpte), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int32, Float64, Float64),
                        r.handle, collect(vec(permutedims(g.X))), g.y, length(g.y), size(g.X, 2), lik, g.noise_sd, g.inclusion_prob))
+    end
+    if t.target isa DeviceHierarchicalNormalMeans   # the groups' estimates and standard errors as pte_set_target_hier reads them
+        g = t.target
+        par = g.parameterization === :noncentered ? HIER_NONCENTERED : HIER_CENTERED
+        check(r, ccall((:pte_set_target_hier, libpte), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Float64, Float64),
+                       r.handle, par, length(g.y), g.y, g.sigma, g.mu_sd, g.tau_scale))
     end
     if t.target isa DevicePoissonChangePoint        # the counts as pte_set_target_changepoint reads them
         check(r, ccall((:pte_set_target_changepoint, libpte), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), r.handle, t.target.y, length(t.target.y)))

@@ -124,6 +124,14 @@ class Engine:
         """pte_set_changepoint_form: CHANGEPOINT_FORM_AUTO / _FULL / _CACHED, the same bits either way"""
         self._chk(self.L.pte_set_changepoint_form(self.h, int(form)))
 
+    def set_target_hier(self, parameterization, y, sigma, mu_sd=5.0, tau_scale=5.0):
+        """pte_set_target_hier: parameterization HIER_*, the groups' estimates y [J] and standard errors sigma [J], J = dim - 2"""
+        ya = np.ascontiguousarray(y, dtype=np.float64).ravel()
+        sa = np.ascontiguousarray(sigma, dtype=np.float64).ravel()
+        if sa.size != ya.size:
+            raise ValueError("set_target_hier: y and sigma must have one entry per group (got %d and %d)" % (ya.size, sa.size))
+        self._chk(self.L.pte_set_target_hier(self.h, int(parameterization), ya.size, _dp(ya), _dp(sa), float(mu_sd), float(tau_scale)))
+
     # --- hot path
     def explore(self, scan):
         self._chk(self.L.pte_explore(self.h, scan))

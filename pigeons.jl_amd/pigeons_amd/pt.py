@@ -198,6 +198,64 @@ class MixtureModelPosterior:
         return "MixtureModelPosterior(n=%d, K=%d)" % (self.n_obs, self.n_components)
 
 
+class HierarchicalNormalMeans:
+    """The posterior of a hierarchical normal-means model, the device's funnel-with-data target ("eight schools"): J groups with
+    estimates y_j and known standard errors sigma_j,
+        y_j ~ N(theta_j, sigma_j^2),  theta_j ~ N(mu, tau^2),  mu ~ N(0, mu_sd^2),  tau ~ HalfCauchy(0, tau_scale)
+    with the state x = [mu, log tau, x_2 .. x_{J+1}] (dim = J + 2, 1 <= J <= 510) and
+        parameterization="centered"      x_{2+j} = theta_j
+        parameterization="noncentered"   x_{2+j} = eta_j ~ N(0, 1), theta_j = mu + tau eta_j
+    The density is normalised in x (it includes the Jacobian of log tau).  Tempered through the default InterpolatingPath(reference, target)
+    (src/targets/target.jl:72-75) from reference=ScaledPrecisionNormalLogPotential(p, dim), unnormalised; initialization = zeros(dim);
+    default explorer SliceSampler (target.jl:20).
+
+    Evidence: stepping_stone(pt) estimates log Z1 / Z0 = log p(y) - (d/2) log(2 pi / p) in either parameterization, so the log evidence
+    (marginal likelihood) is stepping_stone(pt) - evidence_offset(p): see evidence_offset."""
+
+    PARAMETERIZATIONS = {"centered": 0, "noncentered": 1}
+
+    def __init__(self, y, sigma, mu_sd=5.0, tau_scale=5.0, parameterization="centered"):
+        if parameterization not in self.PARAMETERIZATIONS:
+            raise ValueError("HierarchicalNormalMeans: parameterization must be 'centered' or 'noncentered' (got %r)" % (parameterization,))
+        y = np.array(y, dtype=np.float64)
+        sigma = np.array(sigma, dtype=np.float64)
+        if y.ndim != 1 or not 1 <= y.size <= 510:
+            raise ValueError("HierarchicalNormalMeans: y must be a vector of 1..510 group estimates (got shape %s)" % (y.shape,))
+        if sigma.shape != y.shape:
+            raise ValueError("HierarchicalNormalMeans: sigma must hold one standard error per group, %d of them (got shape %s)" % (y.size, sigma.shape))
+        if not np.all(np.isfinite(y)):
+            raise ValueError("HierarchicalNormalMeans: y[%d] must be finite" % int(np.flatnonzero(~np.isfinite(y))[0]))
+        bad = ~(np.isfinite(sigma) & (sigma > 0))
+        if np.any(bad):
+            raise ValueError("HierarchicalNormalMeans: sigma[%d] must be positive and finite" % int(np.flatnonzero(bad)[0]))
+        mu_sd, tau_scale = float(mu_sd), float(tau_scale)
+        if not (mu_sd > 0 and math.isfinite(mu_sd)):
+            raise ValueError("HierarchicalNormalMeans: mu_sd must be positive and finite (got %r)" % (mu_sd,))
+        if not (tau_scale > 0 and math.isfinite(tau_scale)):
+            raise ValueError("HierarchicalNormalMeans: tau_scale must be positive and finite (got %r)" % (tau_scale,))
+        self.y, self.sigma, self.mu_sd, self.tau_scale, self.parameterization = y, sigma, mu_sd, tau_scale, parameterization
+
+    @property
+    def n_groups(self):
+        return self.y.size
+
+    @property
+    def dim(self):
+        return self.y.size + 2
+
+    @property
+    def parameterization_code(self):
+        return self.PARAMETERIZATIONS[self.parameterization]
+
+    def evidence_offset(self, precision):
+        """what stepping_stone(pt) is off the log evidence by: stepping_stone(pt) = log p(y) + evidence_offset(p), with
+        evidence_offset(p) = -(d/2) log(2 pi / p), d = dim and p the reference's precision"""
+        return -(self.dim / 2.0) * math.log(2.0 * math.pi / float(precision))
+
+    def __repr__(self):
+        return "HierarchicalNormalMeans(%s, J=%d, dim=%d)" % (self.parameterization, self.n_groups, self.dim)
+
+
 class SpikeSlabRegression:
     """Bayesian variable selection, a spike-and-slab regression: the data of BayesianGLM (X: n x d, y: n, the same two
     likelihoods) with an inclusion indicator per column.  The state is
@@ -615,6 +673,11 @@ class PT:
             if not isinstance(ref, ScaledPrecisionNormalLogPotential) or ref.dim != target.dim:
                 raise NotImplementedError("the device mixture-model path needs reference=ScaledPrecisionNormalLogPotential(prec, dim) -- the prior")
             kw.update(target=_lib.TARGET_MIXTURE_MODEL, dim=target.dim, target_params=[ref.precision])
+        elif isinstance(target, HierarchicalNormalMeans):
+            ref = inputs.reference
+            if not isinstance(ref, ScaledPrecisionNormalLogPotential) or ref.dim != target.dim:
+                raise NotImplementedError("the device hierarchical-normal path needs reference=ScaledPrecisionNormalLogPotential(prec, dim)")
+            kw.update(target=_lib.TARGET_HIERARCHICAL_NORMAL, dim=target.dim, target_params=[ref.precision])
         elif isinstance(target, SpikeSlabRegression):
             ref = inputs.reference
             if not isinstance(ref, ScaledPrecisionNormalLogPotential) or ref.dim != target.n_columns:
@@ -698,6 +761,9 @@ class PT:
         if isinstance(target, MixtureModelPosterior):    # every engine (rank) holds the observations
             for eng in (self.shards.engines if hasattr(self.shards, "engines") else [self.replicas]):
                 eng.set_target_mixture_model(target.y)
+        if isinstance(target, HierarchicalNormalMeans):  # every engine (rank) holds the data
+            for eng in (self.shards.engines if hasattr(self.shards, "engines") else [self.replicas]):
+                eng.set_target_hier(target.parameterization_code, target.y, target.sigma, target.mu_sd, target.tau_scale)
         if isinstance(target, SpikeSlabRegression):      # every engine (rank) holds the data
             for eng in (self.shards.engines if hasattr(self.shards, "engines") else [self.replicas]):
                 eng.set_target_varsel(target.likelihood_code, target.X, target.y, target.noise_sd, target.inclusion_prob)
