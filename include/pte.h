@@ -59,9 +59,17 @@ enum {
     PTE_TARGET_CHANGE_POINT = 8,         /* K Poisson change points on n counts (pte_set_target_changepoint): the state is [r, tau],
                                             K + 1 Float64 log rates then K Integer change points stored as integral doubles in 0..n,
                                             dim = 2 K + 1, K <= 63; SliceSampler only (its Float64 and Integer coordinate methods) */
-    PTE_TARGET_HIERARCHICAL_NORMAL = 9   /* InterpolatingPath(normal ref, hierarchical normal-means posterior of J group estimates;
+    PTE_TARGET_HIERARCHICAL_NORMAL = 9,  /* InterpolatingPath(normal ref, hierarchical normal-means posterior of J group estimates;
                                             pte_set_target_hier): the state is [mu, log tau, one coordinate per group], dim = J + 2 in
                                             3..512; SliceSampler / AutoMALA / MALA / Compose of them */
+    PTE_TARGET_LATENT_AR1 = 10           /* InterpolatingPath(normal ref, posterior of a latent AR(1) state-space model of T observations;
+                                            pte_set_target_ar1): the state is [mu, atanh phi, log sigma, h_0 .. h_{T-1}], dim = T + 3 in
+                                            4..512; SliceSampler / AutoMALA / MALA / Compose of them */
+};
+/* PTE_TARGET_LATENT_AR1: the observation model */
+enum {
+    PTE_AR1_STOCHASTIC_VOLATILITY = 0,   /* y_t ~ N(0, exp(h_t))                                                                    */
+    PTE_AR1_NORMAL_IDENTITY = 1          /* y_t ~ N(h_t, obs_sd^2): linear-Gaussian given (phi, sigma)                              */
 };
 /* PTE_TARGET_HIERARCHICAL_NORMAL: what the group coordinates are */
 enum {
@@ -267,6 +275,15 @@ int pte_set_target_mixture_model(pte_engine *h, int64_t n_obs, const double *y /
  * stepping_stone estimates log p(y) - (d/2) log(2 pi / p), p = target_params[0] the reference's precision.  DESIGN 4.14. */
 int pte_set_target_hier(pte_engine *h, int32_t parameterization, int64_t n_groups, const double *y /*[n_groups]*/,
                         const double *sigma /*[n_groups]*/, double mu_sd, double tau_scale);
+/* PTE_TARGET_LATENT_AR1: the data of the target N(mu; 0, mu_sd^2) N(a; phi_loc, phi_scale^2) HalfCauchy(sigma; 0, sigma_scale) sigma
+ * N(h_0; mu, sigma^2 / (1 - phi^2)) prod_{t>0} N(h_t; mu + phi (h_{t-1} - mu), sigma^2) prod_t p(y_t | h_t) in x = [mu, a, ls, h], phi = tanh(a),
+ * sigma = exp(ls) (likelihood PTE_AR1_*; obs_sd is read by PTE_AR1_NORMAL_IDENTITY only; the density is normalised in x).  Validates in this
+ * order (the engine's target; the likelihood; n_obs == dim - 3; y not NULL; every y[t] finite, in t; obs_sd -- the normal model only --, then
+ * mu_sd, phi_scale, sigma_scale positive and finite; phi_loc finite), uploads and refreshes the swap statistics of the current states; may be
+ * called again to replace the data.  Until the first call pte_explore, pte_swap, pte_run_scans, pte_group_run_scans and pte_get_state fail.
+ * stepping_stone estimates log p(y) - (d/2) log(2 pi / p), p = target_params[0] the reference's precision.  DESIGN 4.15. */
+int pte_set_target_ar1(pte_engine *h, int32_t likelihood, int64_t n_obs, const double *y /*[n_obs]*/, double obs_sd, double mu_sd,
+                       double phi_loc, double phi_scale, double sigma_scale);
 /* PTE_TARGET_VARIABLE_SELECTION: the data of the target N(theta; 0, I / p) prod_j pi^gamma_j (1 - pi)^(1 - gamma_j)
  * prod_i p(y_i | eta_i = sum_j X[i][j] gamma_j theta_j) (p = target_params[0], the reference's precision; pi = inclusion_prob; X row-major
  * [n_obs][d] with d = dim / 2; likelihood PTE_GLM_*, noise_sd read by PTE_GLM_NORMAL_IDENTITY only).  Validates as pte_set_target_glm does

@@ -27,6 +27,7 @@
 #include "pte_mixture_params.hpp"
 #include "pte_glm_params.hpp"
 #include "pte_hier_params.hpp"
+#include "pte_ar1_params.hpp"
 #include "pte_mixture_model_params.hpp"
 #include "pte_varsel_params.hpp"
 #include "pte_changepoint_params.hpp"
@@ -36,6 +37,7 @@
 #include "pte_mixture.hpp"
 #include "pte_glm.hpp"
 #include "pte_hier.hpp"
+#include "pte_ar1.hpp"
 #include "pte_mixture_model.hpp"
 #include "pte_varsel.hpp"
 #include "pte_changepoint.hpp"
@@ -114,6 +116,9 @@ struct pte_engine {
     double *d_hier = nullptr;       // PTE_TARGET_HIERARCHICAL_NORMAL: y, 1 / sigma, log sigma, [512] each, by state coordinate
     HierParams hier{};              // the uploaded data as the kernels read it; hier.n = 0 until pte_set_target_hier
     int hier_param = 0;
+    double *d_ar1 = nullptr;        // PTE_TARGET_LATENT_AR1: y, y^2, [512] each, by state coordinate
+    Ar1Params ar1{};                // the uploaded data as the kernels read it; ar1.n = 0 until pte_set_target_ar1
+    int ar1_lik = 0;
     double step_size = 1.0;
     int am_n_refresh = 0;
     std::vector<double> fac_mean, rev_mean; std::vector<int64_t> fac_n, rev_n;
@@ -244,7 +249,8 @@ const PathFamily *path_family(int target) {
                             mixmodel{"mixture-model", "data", "pte_set_target_mixture_model", "one kernel serves it", "k_explore_mixture_model"},
                             varsel{"variable-selection", "data", "pte_set_target_varsel", "one kernel serves it", "k_explore_varsel"},
                             changepoint{"change-point", "data", "pte_set_target_changepoint", "one kernel serves it", "k_explore_changepoint"},
-                            hier{"hierarchical-normal", "data", "pte_set_target_hier", "one register-resident kernel serves it", "k_explore_hier"};
+                            hier{"hierarchical-normal", "data", "pte_set_target_hier", "one register-resident kernel serves it", "k_explore_hier"},
+                            ar1{"latent-AR(1)", "data", "pte_set_target_ar1", "one register-resident kernel serves it", "k_explore_ar1"};
     switch (target) {
     case PTE_TARGET_FUNNEL: return &funnel;
     case PTE_TARGET_GAUSSIAN_MIXTURE: return &mixture;
@@ -253,6 +259,7 @@ const PathFamily *path_family(int target) {
     case PTE_TARGET_VARIABLE_SELECTION: return &varsel;
     case PTE_TARGET_CHANGE_POINT: return &changepoint;
     case PTE_TARGET_HIERARCHICAL_NORMAL: return &hier;
+    case PTE_TARGET_LATENT_AR1: return &ar1;
     default: return nullptr;
     }
 }
@@ -266,6 +273,7 @@ bool family_ready(const pte_engine *h) {
     case PTE_TARGET_VARIABLE_SELECTION: return h->varsel.n > 0;
     case PTE_TARGET_CHANGE_POINT: return h->changepoint.n > 0;
     case PTE_TARGET_HIERARCHICAL_NORMAL: return h->hier.n > 0;
+    case PTE_TARGET_LATENT_AR1: return h->ar1.n > 0;
     default: return true;
     }
 }
@@ -291,13 +299,14 @@ MixParams mixture_params(const pte_engine *h) {
 bool changepoint_cached(const pte_engine *h) { return h->changepoint_form != CHANGEPOINT_FORM_FULL; }
 
 // One launch of the engine's AutoMALA / MALA / SliceSampler-on-the-path kernel over N replicas (one workgroup each): the family's own on the
-// mixture, GLM, mixture-model and hierarchical-normal paths, the Langevin family's on the funnel and scaled-precision MVN paths.  The open timing bracket's events ride on it.
+// mixture, GLM, mixture-model, hierarchical-normal and latent-AR(1) paths, the Langevin family's on the funnel and scaled-precision MVN paths.  The open timing bracket's events ride on it.
 int launch_path_kernel(pte_engine *h, int E, bool slice, bool full, int64_t N, const AmParams &ap) {
     const LaunchSite at = launch_site(h, (unsigned)N);
     switch (h->cfg.target) {
     case PTE_TARGET_GAUSSIAN_MIXTURE: return mixture_launch(MixtureLaunch{E, slice, full, at}, h->dev, ap, mixture_params(h)) ? family_no_kernel_error(h) : 0;
     case PTE_TARGET_BAYESIAN_GLM: return glm_launch(GlmLaunch{E, h->glm_lik, slice, full, at}, h->dev, ap, h->glm) ? family_no_kernel_error(h) : 0;
     case PTE_TARGET_HIERARCHICAL_NORMAL: return hier_launch(HierLaunch{E, h->hier_param, slice, full, at}, h->dev, ap, h->hier) ? family_no_kernel_error(h) : 0;
+    case PTE_TARGET_LATENT_AR1: return ar1_launch(Ar1Launch{E, h->ar1_lik, slice, full, at}, h->dev, ap, h->ar1) ? family_no_kernel_error(h) : 0;
     case PTE_TARGET_MIXTURE_MODEL: return mixture_model_launch(MixModelLaunch{(int)(h->d / 3), slice, at}, h->dev, ap, h->mixmodel) ? family_no_kernel_error(h) : 0;
     case PTE_TARGET_VARIABLE_SELECTION:      // SliceSampler alone (validate_config); whole blocks: 2 d == 64 E
         return varsel_launch(VarselLaunch{E, h->varsel_lik, h->d == 64 * (int64_t)E, at}, h->dev, ap, h->varsel) ? family_no_kernel_error(h) : 0;
@@ -321,6 +330,7 @@ int refresh_path_stats(pte_engine *h) {
     case PTE_TARGET_GAUSSIAN_MIXTURE: if (mixture_refresh_stats(E, N, h->stream, h->dev, mixture_params(h))) return family_no_kernel_error(h); break;
     case PTE_TARGET_BAYESIAN_GLM: if (glm_refresh_stats(E, h->glm_lik, N, h->stream, h->dev, h->glm, h->cfg.target_params[0])) return family_no_kernel_error(h); break;
     case PTE_TARGET_HIERARCHICAL_NORMAL: if (hier_refresh_stats(E, h->hier_param, N, h->stream, h->dev, h->hier)) return family_no_kernel_error(h); break;
+    case PTE_TARGET_LATENT_AR1: if (ar1_refresh_stats(E, h->ar1_lik, N, h->stream, h->dev, h->ar1)) return family_no_kernel_error(h); break;
     case PTE_TARGET_MIXTURE_MODEL: if (mixture_model_refresh_stats((int)(h->d / 3), N, h->stream, h->dev, h->mixmodel, h->cfg.target_params[0])) return family_no_kernel_error(h); break;
     case PTE_TARGET_VARIABLE_SELECTION: if (varsel_refresh_stats(E, h->varsel_lik, N, h->stream, h->dev, h->varsel, h->cfg.target_params[0])) return family_no_kernel_error(h); break;
     case PTE_TARGET_CHANGE_POINT: if (changepoint_refresh_stats(N, h->stream, h->dev, h->changepoint, h->cfg.target_params[0])) return family_no_kernel_error(h); break;
@@ -1032,7 +1042,7 @@ int validate_config(const pte_config *cfg) {
         if (cfg->slice_w != std::floor(cfg->slice_w) || !std::isfinite(cfg->slice_w))      // SliceSampler.jl:137 (@assert), the oracle's text
             return fail(nullptr, "pte_create: for integer variables, the width should be an integer. Got: %g", cfg->slice_w);
     }
-    if (family && !funnel) {    // the families with kernels of their own -- Gaussian mixture, Bayesian GLM, mixture model, hierarchical normal means: one wave per replica, SliceSampler / AutoMALA / MALA (AAPS: refused above)
+    if (family && !funnel) {    // the families with kernels of their own -- Gaussian mixture, Bayesian GLM, mixture model, hierarchical normal means, latent AR(1): one wave per replica, SliceSampler / AutoMALA / MALA (AAPS: refused above)
         auto on_family = [](int k) { return k == PTE_EXPLORER_SLICE || k == PTE_EXPLORER_AUTOMALA || k == PTE_EXPLORER_MALA; };
         if (!on_family(cfg->explorer) || (cfg->explorer2 != PTE_EXPLORER_NONE && !on_family(cfg->explorer2)))
             return fail(nullptr, "pte_create: the %s path is implemented for SliceSampler / AutoMALA / MALA (and Compose of them) only (got explorers %d, %d)",
@@ -1041,6 +1051,8 @@ int validate_config(const pte_config *cfg) {
             return fail(nullptr, "pte_create: the mixture-model path holds theta = [mu, s, alpha] of 1..8 components, dim must be in {3, 6, ..., 24} (got %lld)", (long long)cfg->dim);
         if (cfg->target == PTE_TARGET_HIERARCHICAL_NORMAL && (cfg->dim < 3 || cfg->dim > 512))
             return fail(nullptr, "pte_create: the hierarchical-normal path holds [mu, log tau] and 1..510 group coordinates, dim must be in 3..512 (got %lld)", (long long)cfg->dim);
+        if (cfg->target == PTE_TARGET_LATENT_AR1 && (cfg->dim < 4 || cfg->dim > 512))
+            return fail(nullptr, "pte_create: the latent-AR(1) path holds [mu, a, ls] and 1..509 latent states, dim must be in 4..512 (got %lld)", (long long)cfg->dim);
         if (cfg->dim < 1 || cfg->dim > 512)
             return fail(nullptr, "pte_create: the %s path keeps the replica in the registers of one wave, dim must be in 1..512 (got %lld)", family->name, (long long)cfg->dim);
         if ((cfg->debug_kernel & ~(PTE_KERNEL_FLAG_BITS | PTE_KERNEL_TEST_BITS)) != 0)
@@ -2194,6 +2206,48 @@ int pte_set_target_hier(pte_engine *h, int32_t parameterization, int64_t n_group
     p.imu = 1.0 / mu_sd; p.lmu = std::log(mu_sd);
     p.c_tau = std::log(2.0) - std::log(M_PI) - std::log(tau_scale); p.its = 1.0 / tau_scale;
     h->hier_param = parameterization;
+    return refresh_path_stats(h);                                  // suff / suff2 of the current states
+}
+
+// The latent-AR(1) state-space posterior.  Host, once per call: y_t^2, the priors' reciprocals and logarithms; y and y^2 are
+// uploaded indexed by state coordinate (entries 0..2 and d.. zero) into one allocation of 2 x 512 doubles.
+int pte_set_target_ar1(pte_engine *h, int32_t likelihood, int64_t n_obs, const double *y, double obs_sd, double mu_sd, double phi_loc,
+                       double phi_scale, double sigma_scale) {
+    if (!h) return 1;
+    PTE_ALIVE(h, "pte_set_target_ar1");
+    if (h->cfg.target != PTE_TARGET_LATENT_AR1)
+        return fail(h, "pte_set_target_ar1: this engine's target is %d, not PTE_TARGET_LATENT_AR1", h->cfg.target);
+    if (likelihood != PTE_AR1_STOCHASTIC_VOLATILITY && likelihood != PTE_AR1_NORMAL_IDENTITY)
+        return fail(h, "pte_set_target_ar1: likelihood must be PTE_AR1_STOCHASTIC_VOLATILITY (0) or PTE_AR1_NORMAL_IDENTITY (1) (got %d)", likelihood);
+    const int64_t d = h->d;
+    if (n_obs != d - 3)
+        return fail(h, "pte_set_target_ar1: n_obs must be dim - 3 = %lld (got %lld)", (long long)(d - 3), (long long)n_obs);
+    if (!y) return fail(h, "pte_set_target_ar1: null argument");
+    for (int64_t t = 0; t < n_obs; ++t)
+        if (!std::isfinite(y[t])) return fail(h, "pte_set_target_ar1: y[%lld] must be finite (got %g)", (long long)t, y[t]);
+    const bool normal = likelihood == PTE_AR1_NORMAL_IDENTITY;
+    if (normal && (!(obs_sd > 0) || !std::isfinite(obs_sd))) return fail(h, "pte_set_target_ar1: obs_sd must be positive and finite (got %g)", obs_sd);
+    if (!(mu_sd > 0) || !std::isfinite(mu_sd)) return fail(h, "pte_set_target_ar1: mu_sd must be positive and finite (got %g)", mu_sd);
+    if (!(phi_scale > 0) || !std::isfinite(phi_scale)) return fail(h, "pte_set_target_ar1: phi_scale must be positive and finite (got %g)", phi_scale);
+    if (!(sigma_scale > 0) || !std::isfinite(sigma_scale)) return fail(h, "pte_set_target_ar1: sigma_scale must be positive and finite (got %g)", sigma_scale);
+    if (!std::isfinite(phi_loc)) return fail(h, "pte_set_target_ar1: phi_loc must be finite (got %g)", phi_loc);
+    HIP_OK(h, hipSetDevice(h->cfg.device));
+    std::vector<double> buf((size_t)(2 * AR1_DATA_LEN), 0.0);
+    for (int64_t t = 0; t < n_obs; ++t) {
+        buf[(size_t)(3 + t)] = y[t];
+        buf[(size_t)(AR1_DATA_LEN + 3 + t)] = y[t] * y[t];
+    }
+    if (!h->d_ar1 && dev_alloc(h, &h->d_ar1, buf.size(), false)) return 1;
+    HIP_OK(h, hipMemcpyAsync(h->d_ar1, buf.data(), sizeof(double) * buf.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    Ar1Params &p = h->ar1;
+    p.y = h->d_ar1; p.y2 = h->d_ar1 + AR1_DATA_LEN;
+    p.n = (int)n_obs;
+    p.imu = 1.0 / mu_sd; p.lmu = std::log(mu_sd);
+    p.phi_loc = phi_loc; p.ips = 1.0 / phi_scale; p.lps = std::log(phi_scale);
+    p.c_sigma = std::log(2.0) - std::log(M_PI) - std::log(sigma_scale); p.iss = 1.0 / sigma_scale;
+    p.iobs = normal ? 1.0 / obs_sd : 0.0; p.lobs = normal ? std::log(obs_sd) : 0.0;
+    h->ar1_lik = likelihood;
     return refresh_path_stats(h);                                  // suff / suff2 of the current states
 }
 

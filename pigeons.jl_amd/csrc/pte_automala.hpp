@@ -16,11 +16,14 @@
 //              pte_mixture_model.hpp): theta = [mu, s, alpha] in one block, lanes over observations, K <= KB components
 //   TGT_HIER   the same path with a hierarchical normal-means posterior as the target, LIK = HIER_* the parameterisation (DESIGN 4.14;
 //              pte_hier.hpp): x = [mu, log tau, one coordinate per group], elementwise but for the two hyper-parameters' gradient sums
+//   TGT_AR1    the same path with a latent-AR(1) state-space posterior as the target, LIK = AR1_* the observation model (DESIGN 4.15;
+//              pte_ar1.hpp): x = [mu, a, ls, h_0 .. h_{T-1}], every h coupled to its two neighbours through a one-lane wave shift
 #pragma once
 #include "pte_automala_params.hpp"
 #include "pte_glm_params.hpp"
 #include "pte_mixture_model_params.hpp"
 #include "pte_hier_params.hpp"
+#include "pte_ar1_params.hpp"
 #include "pte_slice_coord.hpp"
 
 namespace pte {
@@ -119,9 +122,30 @@ template <int E> struct AmHierData<true, E> {
     HierParams hp;
     double hy[H_IN_REGS ? E : 1], his[H_IN_REGS ? E : 1], hls[H_IN_REGS ? E : 1];
 };
+// TGT_AR1's data: the same arrangement.  The datum of this lane's coordinates that the observation model reads (y^2 under stochastic
+// volatility, y under the normal model) stays in registers at E <= 2 (E doubles); from E = 4 on it is read again from L2
+template <bool ON, int E> struct AmAr1Data {};
+template <int E> struct AmAr1Data<true, E> {
+    static constexpr bool A_IN_REGS = (E <= 2);
+    Ar1Params ar;
+    double ad[A_IN_REGS ? E : 1];
+};
+// The whole wave shifted by one lane (DPP wave_shr:1 / wave_shl:1, two v_mov_b32_dpp per double): lane l takes v of lane l - 1 (l + 1); the
+// lane at the end that has no source keeps `edge` -- the neighbouring 64-block's value (uniform), so a chain over coordinates 64 j + lane
+// reaches its predecessor and its successor without LDS or memory (TGT_AR1)
+__device__ __forceinline__ double wave_from_below_f64(double v, double edge) {
+    const int lo = __builtin_amdgcn_update_dpp(__double2loint(edge), __double2loint(v), 0x138, 0xF, 0xF, false);
+    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(edge), __double2hiint(v), 0x138, 0xF, 0xF, false);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double wave_from_above_f64(double v, double edge) {
+    const int lo = __builtin_amdgcn_update_dpp(__double2loint(edge), __double2loint(v), 0x130, 0xF, 0xF, false);
+    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(edge), __double2hiint(v), 0x130, 0xF, 0xF, false);
+    return __hiloint2double(hi, lo);
+}
 
 template <int E, int TGT, bool FULL = false, int KB = 1, int LIK = 0>
-struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>, AmHierData<TGT == TGT_HIER, E> {
+struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>, AmHierData<TGT == TGT_HIER, E>, AmAr1Data<TGT == TGT_AR1, E> {
     int64_t d; int lane;
     double nhp, nprec;          // MVN: -0.5*prec, -prec of this chain
     double beta, omb, ref_nhp, ref_nprec, log3;   // funnel path
@@ -503,9 +527,107 @@ struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>
         double S, Q, dummy[E];
         return hier_and_sqr_norm<false, false>(x, dummy, S, x, Q);
     }
+    // the latent-AR(1) posterior: x = [mu, a, ls, h_0 .. h_{T-1}], phi = tanh(a), sigma = exp(ls), LIK = AR1_STOCHASTIC_VOLATILITY
+    // (y_t ~ N(0, exp(h_t))) or AR1_NORMAL_IDENTITY (y_t ~ N(h_t, obs_sd^2)).  The density is one sum over the fixed tree with the leaves in
+    // state order: leaves 0..2 the priors of mu, a and sigma (with the Jacobian of ls), leaf 3 + t = the transition term of h_t + its
+    // observation term.  phi, om = 1 - phi^2, sqrt(om), log(om), isg = exp(-ls) and r = (sigma / sigma_scale)^2 are computed once, on the values
+    // lanes 0..2 of block 0 hold.  The predecessor's h - mu comes from the lane below (lane 0: lane 63 of the block before); coordinate 3 = h_0
+    // has the stationary law and reads no neighbour.  GRAD: the h components are elementwise given the successor's residual, which comes from
+    // the lane above (lane 63: lane 0 of the block after); those of mu, a and ls are three more sums over the same tree, in lockstep with the
+    // density, S = sum x^2 and (WITH_Q) Q = sum q^2.  Lanes past d are masked by index and contribute exactly 0.
+    __device__ __forceinline__ void load_ar1(const Ar1Params &a) {
+        this->ar = a;
+        if constexpr (AmAr1Data<true, E>::A_IN_REGS) {
+            const double *src = LIK == AR1_NORMAL_IDENTITY ? a.y : a.y2;
+#pragma unroll
+            for (int j = 0; j < E; ++j) this->ad[j] = src[64 * j + lane];
+        }
+    }
+    template <bool GRAD, bool WITH_Q>
+    __device__ __forceinline__ double ar1_and_sqr_norm(const double (&x)[E], double (&g)[E], double &S, const double (&q)[E], double &Q) const {
+        constexpr bool NORMAL = (LIK == AR1_NORMAL_IDENTITY);
+        constexpr bool IN_REGS = AmAr1Data<true, E>::A_IN_REGS;
+        const Ar1Params &ar = this->ar;
+        const double LOG2PI = 1.8378770664093453;
+        const double mu = readlane_f64(x[0], 0), a = readlane_f64(x[0], 1), ls = readlane_f64(x[0], 2);
+        const double phi = tanh(a);
+        const double om = 1.0 - phi * phi, sqom = sqrt(om), lom = log(om);
+        const double isg = exp(-ls), sg = exp(ls);
+        const double ts = sg * ar.iss, r = ts * ts;
+        const double c0 = isg * sqom, pis = phi * isg, cm = (1.0 - phi) * isg, ca = isg * om;
+        constexpr int K = 2 + (GRAD ? 3 : 0) + (WITH_Q ? 1 : 0), KM = 2, KA = 3, KL = 4, KQ = GRAD ? 5 : 2;
+        double t[K][E], out[K];
+        double hm[E], u[E], ut[E], obd[E];
+#pragma unroll
+        for (int j = 0; j < E; ++j) hm[j] = x[j] - mu;
+#pragma unroll
+        for (int j = 0; j < E; ++j) {
+            const bool lat = (j > 0 || lane >= 3) && valid(j);           // this lane's coordinate of block j is a latent state h_t
+            const bool first = (j == 0 && lane == 3);                   // ... and it is h_0
+            const double pv = wave_from_below_f64(hm[j], j > 0 ? readlane_f64(hm[j > 0 ? j - 1 : 0], 63) : 0.0);      // h_{t-1} - mu
+            double dj;
+            if constexpr (IN_REGS) dj = this->ad[j];
+            else dj = (NORMAL ? ar.y : ar.y2)[64 * j + lane];            // ([512]: in bounds whatever d)
+            const double xj = x[j];
+            t[0][j] = xj * xj;
+            const double u1 = (hm[j] - phi * pv) * isg, u0 = (hm[j] * isg) * sqom;
+            const double uj = first ? u0 : u1;
+            double tr = -(uj * uj + LOG2PI) / 2.0 - ls;
+            if (j == 0) tr = first ? tr + lom / 2.0 : tr;
+            double ob;
+            if constexpr (NORMAL) {
+                const double z = (dj - xj) * ar.iobs;
+                ob = -(z * z + LOG2PI) / 2.0 - ar.lobs;
+                obd[j] = z * ar.iobs;
+            } else {
+                const double ye = dj * exp(-xj);
+                ob = -((ye + xj) + LOG2PI) / 2.0;
+                obd[j] = (ye - 1.0) / 2.0;
+            }
+            t[1][j] = lat ? tr + ob : 0.0;
+            u[j] = lat ? uj : 0.0;
+            ut[j] = (lat && !first) ? uj : 0.0;                          // the residuals that read a predecessor
+            if constexpr (GRAD) {
+                t[KM][j] = lat ? (first ? uj * c0 : uj * cm) : 0.0;
+                t[KA][j] = lat ? (first ? (uj * uj - 1.0) * phi : (uj * pv) * ca) : 0.0;
+                t[KL][j] = lat ? uj * uj - 1.0 : 0.0;
+            }
+            if constexpr (WITH_Q) t[KQ][j] = q[j] * q[j];
+        }
+        if constexpr (GRAD) {
+#pragma unroll
+            for (int j = 0; j < E; ++j) {
+                const bool lat = (j > 0 || lane >= 3) && valid(j);
+                const bool first = (j == 0 && lane == 3);
+                const double us = wave_from_above_f64(ut[j], j + 1 < E ? readlane_f64(ut[j + 1 < E ? j + 1 : j], 0) : 0.0);      // u_{t+1}
+                const double ow = first ? u[j] * c0 : u[j] * isg;
+                g[j] = lat ? (us * pis - ow) + obd[j] : 0.0;
+            }
+        }
+        const double m = mu * ar.imu, za = (a - ar.phi_loc) * ar.ips;
+        if (lane == 0) { t[1][0] = -(m * m + LOG2PI) / 2.0 - ar.lmu; if constexpr (GRAD) t[KM][0] = -m * ar.imu; }
+        if (lane == 1) { t[1][0] = -(za * za + LOG2PI) / 2.0 - ar.lps; if constexpr (GRAD) t[KA][0] = -za * ar.ips; }
+        if (lane == 2) { t[1][0] = (ar.c_sigma - log1p(r)) + ls; if constexpr (GRAD) t[KL][0] = 1.0 - (2.0 * r) / (1.0 + r); }
+        tree_sum_regs_multi<E, K>(t, out);
+        S = out[0];
+        if constexpr (GRAD) g[0] = lane == 0 ? out[KM] : lane == 1 ? out[KA] : lane == 2 ? out[KL] : g[0];
+        if constexpr (WITH_Q) Q = out[KQ];
+        return out[1];
+    }
+    __device__ __forceinline__ double ar1(const double (&x)[E]) const {
+        double S, Q, dummy[E];
+        return ar1_and_sqr_norm<false, false>(x, dummy, S, x, Q);
+    }
     // log_potentials[chain](x) as a plain callable: InterpolatedLogPotential(x) (src/paths/InterpolatedLogPotential.jl:9-16)
     // WITH its beta == 0 / beta == 1 short-circuits -- what SliceSampler evaluates (the AD form below has none)
     __device__ __forceinline__ double path_lp(const double (&x)[E]) const {
+        if constexpr (TGT == TGT_AR1) {
+            if (beta == 0.0) return ref_nhp * sqr_norm_regs<E>(x);
+            double S, Q, dummy[E];
+            const double l2 = ar1_and_sqr_norm<false, false>(x, dummy, S, x, Q);
+            if (beta == 1.0) return l2;
+            return omb * (ref_nhp * S) + beta * l2;
+        }
         if constexpr (TGT == TGT_HIER) {
             if (beta == 0.0) return ref_nhp * sqr_norm_regs<E>(x);
             double S, Q, dummy[E];
@@ -546,6 +668,10 @@ struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>
     __device__ __forceinline__ double logdensity(const double (&x)[E]) const {
         if (TGT == TGT_MVN) return nhp * sqr_norm_regs<E>(x);
         double S, l2, dummy[E], dq;
+        if constexpr (TGT == TGT_AR1) {
+            l2 = ar1_and_sqr_norm<false, false>(x, dummy, S, x, dq);
+            return omb * (ref_nhp * S) + beta * l2;
+        }
         if constexpr (TGT == TGT_HIER) {
             l2 = hier_and_sqr_norm<false, false>(x, dummy, S, x, dq);
             return omb * (ref_nhp * S) + beta * l2;
@@ -586,6 +712,14 @@ struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>
         double logdens = 0.0;
         double g2[E];
         double l2;
+        if constexpr (TGT == TGT_AR1) {
+            l2 = ar1_and_sqr_norm<true, WITH_Q>(x, g2, S, q, Q);
+            logdens += (ref_nhp * S) * omb;
+            logdens += l2 * beta;
+#pragma unroll
+            for (int j = 0; j < E; ++j) g[j] = (ref_nprec * x[j]) * omb + g2[j] * beta;
+            return logdens;
+        }
         if constexpr (TGT == TGT_HIER) {
             l2 = hier_and_sqr_norm<true, WITH_Q>(x, g2, S, q, Q);
             logdens += (ref_nhp * S) * omb;
@@ -656,11 +790,12 @@ __device__ __forceinline__ int64_t am_chain_of_workgroup(int64_t K, int64_t wg) 
 // wave-level wait instead of a workgroup barrier -- every wave writes all the (identical) entries itself, so it only has to see its own stores
 // KB, mp: TGT_MIXTURE only -- the components' bucket (K <= KB) and parameters.  LIK, gp: TGT_GLM only -- the likelihood and the data
 // (the workgroup's dynamic LDS holds theta and r: pte_glm.hpp).  mm: TGT_MIXMODEL only -- the observations (pte_mixture_model.hpp)
-// hp: TGT_HIER only -- the groups' data, LIK its parameterisation (pte_hier.hpp)
+// hp: TGT_HIER only -- the groups' data, LIK its parameterisation (pte_hier.hpp).  ar: TGT_AR1 only -- the observations, LIK the observation
+// model (pte_ar1.hpp)
 template <int E, int TGT, bool SLICE = false, bool FULL = false, bool DIRECT = false, int KB = 1, int LIK = 0>
 __device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const int64_t wg, const MixParams &mp = MixParams{},
                                               const GlmParams &gp = GlmParams{}, const MixModelParams &mm = MixModelParams{},
-                                              const HierParams &hp = HierParams{}) {      // wg: blockIdx.x
+                                              const HierParams &hp = HierParams{}, const Ar1Params &ar = Ar1Params{}) {      // wg: blockIdx.x
     constexpr int NLU = (E == 1 ? 0 : E == 2 ? 1 : E == 4 ? 2 : E == 8 ? 3 : 4);
     const int lane = lane_id();
     // the ziggurat tables of the momentum draws, staged once: a global gather per block of draws costs a memory round trip each time
@@ -687,6 +822,7 @@ __device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const in
     }
     if constexpr (TGT == TGT_MIXMODEL) { T.mm = mm; T.mk = (int)(d / 3); }
     if constexpr (TGT == TGT_HIER) T.load_hier(hp);
+    if constexpr (TGT == TGT_AR1) T.load_ar1(ar);
     T.nhp = e.nhp[c]; T.nprec = e.nprec[c];
     T.beta = e.beta[c]; T.omb = 1.0 - T.beta;
     T.ref_nhp = -0.5 * ap.ref_prec; T.ref_nprec = -ap.ref_prec; T.log3 = ap.log3;
@@ -739,6 +875,10 @@ __device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const in
         }
         if constexpr (TGT == TGT_HIER) {
             l20 = T.hier(x);
+            if (lane == 0) e.suff2[slot] = l20;
+        }
+        if constexpr (TGT == TGT_AR1) {
+            l20 = T.ar1(x);
             if (lane == 0) e.suff2[slot] = l20;
         }
         record_after_explore_impl(e, cl, c, slot, lane, lp0, S0, l20, l30);
@@ -1015,10 +1155,11 @@ __device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const in
     if constexpr (TGT == TGT_GLM) l2 = T.glm(x);
     if constexpr (TGT == TGT_MIXMODEL) l2 = T.mixmodel(x);
     if constexpr (TGT == TGT_HIER) l2 = T.hier(x);
+    if constexpr (TGT == TGT_AR1) l2 = T.ar1(x);
     if (v_on) l3 = T.variational_lp(x);
     if (lane == 0) {
         e.suff[slot] = S;
-        if (TGT == TGT_FUNNEL || TGT == TGT_MIXTURE || TGT == TGT_GLM || TGT == TGT_MIXMODEL || TGT == TGT_HIER) e.suff2[slot] = l2;
+        if (TGT == TGT_FUNNEL || TGT == TGT_MIXTURE || TGT == TGT_GLM || TGT == TGT_MIXMODEL || TGT == TGT_HIER || TGT == TGT_AR1) e.suff2[slot] = l2;
         if (v_on) e.suff3[slot] = l3;
         e.rng[2 * slot] = r.seed;
         e.expl_steps_sum[cl] += (double)steps_sum; e.expl_steps_n[cl] += steps_n;

@@ -41,6 +41,8 @@ const TARGET_VARIABLE_SELECTION = Int32(7)
 const TARGET_CHANGE_POINT = Int32(8)
 const TARGET_HIERARCHICAL_NORMAL = Int32(9)
 const HIER_CENTERED, HIER_NONCENTERED = Int32(0), Int32(1)
+const TARGET_LATENT_AR1 = Int32(10)
+const AR1_STOCHASTIC_VOLATILITY, AR1_NORMAL_IDENTITY = Int32(0), Int32(1)
 const GLM_BERNOULLI_LOGIT, GLM_NORMAL_IDENTITY = Int32(0), Int32(1)
 const EXPLORER_NONE, EXPLORER_TOY, EXPLORER_SLICE, EXPLORER_AUTOMALA, EXPLORER_ISING, EXPLORER_MALA, EXPLORER_AAPS = Int32.((0, 1, 2, 3, 4, 5, 6))
 const RECORD_ROUND_TRIP, RECORD_INDEX_PROCESS, RECORD_ONLINE, RECORD_TRACES, RECORD_ENERGY_AC1, RECORD_TRACES_EXTENDED =
@@ -143,6 +145,13 @@ state is [mu; log tau; theta] (`parameterization = :centered`) or [mu; log tau; 
 dim = J + 2 <= 512.  Used as `Inputs(target = on_mi355x(DeviceHierarchicalNormalMeans(y, sigma, 5.0, 5.0, :noncentered)), reference =
 ScaledPrecisionNormalLogPotential(p, J + 2))`.  stepping_stone(pt) + (dim/2) log(2 pi / p) is the log evidence."""
 struct DeviceHierarchicalNormalMeans; y::Vector{Float64}; sigma::Vector{Float64}; mu_sd::Float64; tau_scale::Float64; parameterization::Symbol; end
+"""The posterior of a latent AR(1) state-space model, the device family PTE_TARGET_LATENT_AR1 (DESIGN 4.15): T observations `y` of a latent
+state h_t | h_{t-1} ~ N(mu + phi (h_{t-1} - mu), sigma^2), h_0 from the stationary law, mu ~ N(0, mu_sd^2), atanh(phi) ~ N(phi_loc, phi_scale^2),
+sigma ~ HalfCauchy(0, sigma_scale), observed as y_t ~ N(0, exp(h_t)) (`likelihood = :stochastic_volatility`) or y_t ~ N(h_t, obs_sd^2)
+(`:normal_identity`); the state is [mu; atanh phi; log sigma; h], dim = T + 3 <= 512.  Used as `Inputs(target =
+on_mi355x(DeviceLatentAR1(y, :stochastic_volatility, 1.0, 5.0, 0.0, 1.0, 1.0)), reference = ScaledPrecisionNormalLogPotential(p, T + 3))`.
+stepping_stone(pt) + (dim/2) log(2 pi / p) is the log evidence."""
+struct DeviceLatentAR1; y::Vector{Float64}; likelihood::Symbol; obs_sd::Float64; mu_sd::Float64; phi_loc::Float64; phi_scale::Float64; sigma_scale::Float64; end
 
 # (target code, dim, target_params, reference precision check) of a wrapped target
 device_family(t::ScaledPrecisionNormalPath, inputs) = (TARGET_MVN, t.dim, (t.precision0, t.precision1, 0.0, 0.0))
@@ -189,6 +198,15 @@ function device_family(t::DeviceHierarchicalNormalMeans, inputs)
     ref isa ScaledPrecisionNormalLogPotential && ref.dim == dim ||
         error("the device hierarchical-normal path needs reference = ScaledPrecisionNormalLogPotential(precision, $dim); keep the CPU path otherwise")
     return (TARGET_HIERARCHICAL_NORMAL, dim, (ref.precision, 0.0, 0.0, 0.0))
+end
+function device_family(t::DeviceLatentAR1, inputs)
+    1 <= length(t.y) <= 509 || error("DeviceLatentAR1: the device holds 1..509 observations")
+    t.likelihood in (:stochastic_volatility, :normal_identity) || error("DeviceLatentAR1: likelihood :stochastic_volatility or :normal_identity")
+    dim = length(t.y) + 3
+    ref = inputs.reference
+    ref isa ScaledPrecisionNormalLogPotential && ref.dim == dim ||
+        error("the device latent-AR(1) path needs reference = ScaledPrecisionNormalLogPotential(precision, $dim); keep the CPU path otherwise")
+    return (TARGET_LATENT_AR1, dim, (ref.precision, 0.0, 0.0, 0.0))
 end
 function device_family(t::DeviceSpikeSlabRegression, inputs)
     n, d = size(t.X)
@@ -343,6 +361,12 @@ function Pigeons.create_replicas(inputs::Inputs{<:OnDevice}, shared::Shared, sou
         par = g.parameterization === :noncentered ? HIER_NONCENTERED : HIER_CENTERED
         check(r, ccall((:pte_set_target_hier, libpte), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Float64, Float64),
                        r.handle, par, length(g.y), g.y, g.sigma, g.mu_sd, g.tau_scale))
+    end
+    if t.target isa DeviceLatentAR1                 # the observations and the priors as pte_set_target_ar1 reads them
+        g = t.target
+        lik = g.likelihood === :normal_identity ? AR1_NORMAL_IDENTITY : AR1_STOCHASTIC_VOLATILITY
+        check(r, ccall((:pte_set_target_ar1, libpte), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Float64, Float64, Float64, Float64, Float64),
+                       r.handle, lik, length(g.y), g.y, g.obs_sd, g.mu_sd, g.phi_loc, g.phi_scale, g.sigma_scale))
     end
     if t.target isa DevicePoissonChangePoint        # the counts as pte_set_target_changepoint reads them
         check(r, ccall((:pte_set_target_changepoint, libpte), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), r.handle, t.target.y, length(t.target.y)))

@@ -132,6 +132,12 @@ class Engine:
             raise ValueError("set_target_hier: y and sigma must have one entry per group (got %d and %d)" % (ya.size, sa.size))
         self._chk(self.L.pte_set_target_hier(self.h, int(parameterization), ya.size, _dp(ya), _dp(sa), float(mu_sd), float(tau_scale)))
 
+    def set_target_ar1(self, likelihood, y, obs_sd=1.0, mu_sd=5.0, phi_loc=0.0, phi_scale=1.0, sigma_scale=1.0):
+        """pte_set_target_ar1: likelihood AR1_*, the observations y [T], T = dim - 3; obs_sd is read by AR1_NORMAL_IDENTITY only"""
+        ya = np.ascontiguousarray(y, dtype=np.float64).ravel()
+        self._chk(self.L.pte_set_target_ar1(self.h, int(likelihood), ya.size, _dp(ya), float(obs_sd), float(mu_sd), float(phi_loc),
+                                            float(phi_scale), float(sigma_scale)))
+
     # --- hot path
     def explore(self, scan):
         self._chk(self.L.pte_explore(self.h, scan))

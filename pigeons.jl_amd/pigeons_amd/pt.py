@@ -256,6 +256,61 @@ class HierarchicalNormalMeans:
         return "HierarchicalNormalMeans(%s, J=%d, dim=%d)" % (self.parameterization, self.n_groups, self.dim)
 
 
+class LatentAR1:
+    """The posterior of a latent AR(1) state-space model, the device's family with coordinates coupled to their neighbours: T
+    observations y_t of a latent state h,
+        h_0 ~ N(mu, sigma^2 / (1 - phi^2)),  h_t | h_{t-1} ~ N(mu + phi (h_{t-1} - mu), sigma^2),
+        mu ~ N(0, mu_sd^2),  a = atanh(phi) ~ N(phi_loc, phi_scale^2),  sigma ~ HalfCauchy(0, sigma_scale)
+    observed through
+        likelihood="stochastic_volatility"   y_t ~ N(0, exp(h_t))
+        likelihood="normal_identity"         y_t ~ N(h_t, obs_sd^2)   (linear-Gaussian given phi and sigma: exact evidence by quadrature)
+    with the state x = [mu, a, log sigma, h_0 .. h_{T-1}] (dim = T + 3, 1 <= T <= 509).  The density is normalised in x (it includes the Jacobian
+    of log sigma).  Tempered through the default InterpolatingPath(reference, target) (src/targets/target.jl:72-75) from
+    reference=ScaledPrecisionNormalLogPotential(p, dim), unnormalised; initialization = zeros(dim); default explorer SliceSampler (target.jl:20).
+
+    Evidence: stepping_stone(pt) estimates log Z1 / Z0 = log p(y) - (d/2) log(2 pi / p), so the log evidence (marginal likelihood) is
+    stepping_stone(pt) - evidence_offset(p): see evidence_offset."""
+
+    LIKELIHOODS = {"stochastic_volatility": 0, "normal_identity": 1}
+
+    def __init__(self, y, likelihood="stochastic_volatility", obs_sd=1.0, mu_sd=5.0, phi_loc=0.0, phi_scale=1.0, sigma_scale=1.0):
+        if likelihood not in self.LIKELIHOODS:
+            raise ValueError("LatentAR1: likelihood must be 'stochastic_volatility' or 'normal_identity' (got %r)" % (likelihood,))
+        y = np.array(y, dtype=np.float64)
+        if y.ndim != 1 or not 1 <= y.size <= 509:
+            raise ValueError("LatentAR1: y must be a vector of 1..509 observations (got shape %s)" % (y.shape,))
+        if not np.all(np.isfinite(y)):
+            raise ValueError("LatentAR1: y[%d] must be finite" % int(np.flatnonzero(~np.isfinite(y))[0]))
+        obs_sd, mu_sd, phi_loc, phi_scale, sigma_scale = float(obs_sd), float(mu_sd), float(phi_loc), float(phi_scale), float(sigma_scale)
+        for name, v in (("obs_sd", obs_sd), ("mu_sd", mu_sd), ("phi_scale", phi_scale), ("sigma_scale", sigma_scale)):
+            if not (v > 0 and math.isfinite(v)):
+                raise ValueError("LatentAR1: %s must be positive and finite (got %r)" % (name, v))
+        if not math.isfinite(phi_loc):
+            raise ValueError("LatentAR1: phi_loc must be finite (got %r)" % (phi_loc,))
+        self.y, self.likelihood = y, likelihood
+        self.obs_sd, self.mu_sd, self.phi_loc, self.phi_scale, self.sigma_scale = obs_sd, mu_sd, phi_loc, phi_scale, sigma_scale
+
+    @property
+    def n_obs(self):
+        return self.y.size
+
+    @property
+    def dim(self):
+        return self.y.size + 3
+
+    @property
+    def likelihood_code(self):
+        return self.LIKELIHOODS[self.likelihood]
+
+    def evidence_offset(self, precision):
+        """what stepping_stone(pt) is off the log evidence by: stepping_stone(pt) = log p(y) + evidence_offset(p), with
+        evidence_offset(p) = -(d/2) log(2 pi / p), d = dim and p the reference's precision"""
+        return -(self.dim / 2.0) * math.log(2.0 * math.pi / float(precision))
+
+    def __repr__(self):
+        return "LatentAR1(%s, T=%d, dim=%d)" % (self.likelihood, self.n_obs, self.dim)
+
+
 class SpikeSlabRegression:
     """Bayesian variable selection, a spike-and-slab regression: the data of BayesianGLM (X: n x d, y: n, the same two
     likelihoods) with an inclusion indicator per column.  The state is
@@ -678,6 +733,11 @@ class PT:
             if not isinstance(ref, ScaledPrecisionNormalLogPotential) or ref.dim != target.dim:
                 raise NotImplementedError("the device hierarchical-normal path needs reference=ScaledPrecisionNormalLogPotential(prec, dim)")
             kw.update(target=_lib.TARGET_HIERARCHICAL_NORMAL, dim=target.dim, target_params=[ref.precision])
+        elif isinstance(target, LatentAR1):
+            ref = inputs.reference
+            if not isinstance(ref, ScaledPrecisionNormalLogPotential) or ref.dim != target.dim:
+                raise NotImplementedError("the device latent-AR(1) path needs reference=ScaledPrecisionNormalLogPotential(prec, dim)")
+            kw.update(target=_lib.TARGET_LATENT_AR1, dim=target.dim, target_params=[ref.precision])
         elif isinstance(target, SpikeSlabRegression):
             ref = inputs.reference
             if not isinstance(ref, ScaledPrecisionNormalLogPotential) or ref.dim != target.n_columns:
@@ -764,6 +824,9 @@ class PT:
         if isinstance(target, HierarchicalNormalMeans):  # every engine (rank) holds the data
             for eng in (self.shards.engines if hasattr(self.shards, "engines") else [self.replicas]):
                 eng.set_target_hier(target.parameterization_code, target.y, target.sigma, target.mu_sd, target.tau_scale)
+        if isinstance(target, LatentAR1):                # every engine (rank) holds the data
+            for eng in (self.shards.engines if hasattr(self.shards, "engines") else [self.replicas]):
+                eng.set_target_ar1(target.likelihood_code, target.y, target.obs_sd, target.mu_sd, target.phi_loc, target.phi_scale, target.sigma_scale)
         if isinstance(target, SpikeSlabRegression):      # every engine (rank) holds the data
             for eng in (self.shards.engines if hasattr(self.shards, "engines") else [self.replicas]):
                 eng.set_target_varsel(target.likelihood_code, target.X, target.y, target.noise_sd, target.inclusion_prob)
