@@ -62,9 +62,11 @@ enum {
     PTE_TARGET_HIERARCHICAL_NORMAL = 9,  /* InterpolatingPath(normal ref, hierarchical normal-means posterior of J group estimates;
                                             pte_set_target_hier): the state is [mu, log tau, one coordinate per group], dim = J + 2 in
                                             3..512; SliceSampler / AutoMALA / MALA / Compose of them */
-    PTE_TARGET_LATENT_AR1 = 10           /* InterpolatingPath(normal ref, posterior of a latent AR(1) state-space model of T observations;
+    PTE_TARGET_LATENT_AR1 = 10,          /* InterpolatingPath(normal ref, posterior of a latent AR(1) state-space model of T observations;
                                             pte_set_target_ar1): the state is [mu, atanh phi, log sigma, h_0 .. h_{T-1}], dim = T + 3 in
                                             4..512; SliceSampler / AutoMALA / MALA / Compose of them */
+    PTE_TARGET_DENSE_NORMAL = 11         /* InterpolatingPath(normal ref, N(mean, precision^-1) with a dense precision matrix;
+                                            pte_set_target_dense): dim in 1..512; SliceSampler / AutoMALA / MALA / Compose of them */
 };
 /* PTE_TARGET_LATENT_AR1: the observation model */
 enum {
@@ -284,6 +286,16 @@ int pte_set_target_hier(pte_engine *h, int32_t parameterization, int64_t n_group
  * stepping_stone estimates log p(y) - (d/2) log(2 pi / p), p = target_params[0] the reference's precision.  DESIGN 4.15. */
 int pte_set_target_ar1(pte_engine *h, int32_t likelihood, int64_t n_obs, const double *y /*[n_obs]*/, double obs_sd, double mu_sd,
                        double phi_loc, double phi_scale, double sigma_scale);
+/* PTE_TARGET_DENSE_NORMAL: the target N(mean, precision^-1), normalised: log density c - (x - mean)' precision (x - mean) / 2 with
+ * c = log det(precision) / 2 - (dim/2) log 2 pi.  precision is row-major dim x dim.  Refuses, in this order: a null argument; an engine of
+ * another target; dim != the engine's dim; a non-finite entry of mean, then of precision (named by index); precision[i][j] != precision[j][i]
+ * compared bit for bit (the kernels read row k as column k; the first offending pair is named); a matrix that is not positive definite (the
+ * first non-positive pivot of a host Cholesky factorisation is named, which also gives c).  A refused call leaves the engine as it was.
+ * Otherwise uploads the matrix, its diagonal and the mean ((dim + 2) x 64 ceil-pow2(dim / 64) doubles: 2 MiB + 8 KiB at dim = 512) and
+ * refreshes the swap statistics of the current states; may be called again to replace the data.  Until the first call pte_explore,
+ * pte_swap, pte_run_scans, pte_group_run_scans and pte_get_state fail.  Every chain of the path is Gaussian, and stepping_stone estimates
+ * -(dim/2) log(2 pi / p), p = target_params[0] the reference's precision: the log evidence of the normalised target is 0.  DESIGN 4.16. */
+int pte_set_target_dense(pte_engine *h, int64_t dim, const double *mean /*[dim]*/, const double *precision /*[dim][dim]*/);
 /* PTE_TARGET_VARIABLE_SELECTION: the data of the target N(theta; 0, I / p) prod_j pi^gamma_j (1 - pi)^(1 - gamma_j)
  * prod_i p(y_i | eta_i = sum_j X[i][j] gamma_j theta_j) (p = target_params[0], the reference's precision; pi = inclusion_prob; X row-major
  * [n_obs][d] with d = dim / 2; likelihood PTE_GLM_*, noise_sd read by PTE_GLM_NORMAL_IDENTITY only).  Validates as pte_set_target_glm does

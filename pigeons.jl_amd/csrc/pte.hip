@@ -28,6 +28,7 @@
 #include "pte_glm_params.hpp"
 #include "pte_hier_params.hpp"
 #include "pte_ar1_params.hpp"
+#include "pte_dense_params.hpp"
 #include "pte_mixture_model_params.hpp"
 #include "pte_varsel_params.hpp"
 #include "pte_changepoint_params.hpp"
@@ -38,6 +39,7 @@
 #include "pte_glm.hpp"
 #include "pte_hier.hpp"
 #include "pte_ar1.hpp"
+#include "pte_dense.hpp"
 #include "pte_mixture_model.hpp"
 #include "pte_varsel.hpp"
 #include "pte_changepoint.hpp"
@@ -119,6 +121,8 @@ struct pte_engine {
     double *d_ar1 = nullptr;        // PTE_TARGET_LATENT_AR1: y, y^2, [512] each, by state coordinate
     Ar1Params ar1{};                // the uploaded data as the kernels read it; ar1.n = 0 until pte_set_target_ar1
     int ar1_lik = 0;
+    double *d_dense = nullptr;      // PTE_TARGET_DENSE_NORMAL: the precision matrix [d][ld], its diagonal [ld], the mean [ld], ld = 64 blocks_per_lane(d)
+    DenseParams dense{};            // the uploaded data as the kernels read it; dense.n = 0 until pte_set_target_dense
     double step_size = 1.0;
     int am_n_refresh = 0;
     std::vector<double> fac_mean, rev_mean; std::vector<int64_t> fac_n, rev_n;
@@ -250,7 +254,8 @@ const PathFamily *path_family(int target) {
                             varsel{"variable-selection", "data", "pte_set_target_varsel", "one kernel serves it", "k_explore_varsel"},
                             changepoint{"change-point", "data", "pte_set_target_changepoint", "one kernel serves it", "k_explore_changepoint"},
                             hier{"hierarchical-normal", "data", "pte_set_target_hier", "one register-resident kernel serves it", "k_explore_hier"},
-                            ar1{"latent-AR(1)", "data", "pte_set_target_ar1", "one register-resident kernel serves it", "k_explore_ar1"};
+                            ar1{"latent-AR(1)", "data", "pte_set_target_ar1", "one register-resident kernel serves it", "k_explore_ar1"},
+                            dense{"dense-normal", "mean and precision", "pte_set_target_dense", "one kernel per explorer serves it", "k_explore_dense"};
     switch (target) {
     case PTE_TARGET_FUNNEL: return &funnel;
     case PTE_TARGET_GAUSSIAN_MIXTURE: return &mixture;
@@ -260,6 +265,7 @@ const PathFamily *path_family(int target) {
     case PTE_TARGET_CHANGE_POINT: return &changepoint;
     case PTE_TARGET_HIERARCHICAL_NORMAL: return &hier;
     case PTE_TARGET_LATENT_AR1: return &ar1;
+    case PTE_TARGET_DENSE_NORMAL: return &dense;
     default: return nullptr;
     }
 }
@@ -274,6 +280,7 @@ bool family_ready(const pte_engine *h) {
     case PTE_TARGET_CHANGE_POINT: return h->changepoint.n > 0;
     case PTE_TARGET_HIERARCHICAL_NORMAL: return h->hier.n > 0;
     case PTE_TARGET_LATENT_AR1: return h->ar1.n > 0;
+    case PTE_TARGET_DENSE_NORMAL: return h->dense.n > 0;
     default: return true;
     }
 }
@@ -299,7 +306,7 @@ MixParams mixture_params(const pte_engine *h) {
 bool changepoint_cached(const pte_engine *h) { return h->changepoint_form != CHANGEPOINT_FORM_FULL; }
 
 // One launch of the engine's AutoMALA / MALA / SliceSampler-on-the-path kernel over N replicas (one workgroup each): the family's own on the
-// mixture, GLM, mixture-model, hierarchical-normal and latent-AR(1) paths, the Langevin family's on the funnel and scaled-precision MVN paths.  The open timing bracket's events ride on it.
+// mixture, GLM, mixture-model, hierarchical-normal, latent-AR(1) and dense-normal paths, the Langevin family's on the funnel and scaled-precision MVN paths.  The open timing bracket's events ride on it.
 int launch_path_kernel(pte_engine *h, int E, bool slice, bool full, int64_t N, const AmParams &ap) {
     const LaunchSite at = launch_site(h, (unsigned)N);
     switch (h->cfg.target) {
@@ -307,6 +314,8 @@ int launch_path_kernel(pte_engine *h, int E, bool slice, bool full, int64_t N, c
     case PTE_TARGET_BAYESIAN_GLM: return glm_launch(GlmLaunch{E, h->glm_lik, slice, full, at}, h->dev, ap, h->glm) ? family_no_kernel_error(h) : 0;
     case PTE_TARGET_HIERARCHICAL_NORMAL: return hier_launch(HierLaunch{E, h->hier_param, slice, full, at}, h->dev, ap, h->hier) ? family_no_kernel_error(h) : 0;
     case PTE_TARGET_LATENT_AR1: return ar1_launch(Ar1Launch{E, h->ar1_lik, slice, full, at}, h->dev, ap, h->ar1) ? family_no_kernel_error(h) : 0;
+    case PTE_TARGET_DENSE_NORMAL:            // SliceSampler: k_explore_dense_slice, a kernel of its own with a whole-block form too
+        return dense_launch(DenseLaunch{E, slice, h->d == 64 * (int64_t)E, at}, h->dev, ap, h->dense) ? family_no_kernel_error(h) : 0;
     case PTE_TARGET_MIXTURE_MODEL: return mixture_model_launch(MixModelLaunch{(int)(h->d / 3), slice, at}, h->dev, ap, h->mixmodel) ? family_no_kernel_error(h) : 0;
     case PTE_TARGET_VARIABLE_SELECTION:      // SliceSampler alone (validate_config); whole blocks: 2 d == 64 E
         return varsel_launch(VarselLaunch{E, h->varsel_lik, h->d == 64 * (int64_t)E, at}, h->dev, ap, h->varsel) ? family_no_kernel_error(h) : 0;
@@ -331,6 +340,7 @@ int refresh_path_stats(pte_engine *h) {
     case PTE_TARGET_BAYESIAN_GLM: if (glm_refresh_stats(E, h->glm_lik, N, h->stream, h->dev, h->glm, h->cfg.target_params[0])) return family_no_kernel_error(h); break;
     case PTE_TARGET_HIERARCHICAL_NORMAL: if (hier_refresh_stats(E, h->hier_param, N, h->stream, h->dev, h->hier)) return family_no_kernel_error(h); break;
     case PTE_TARGET_LATENT_AR1: if (ar1_refresh_stats(E, h->ar1_lik, N, h->stream, h->dev, h->ar1)) return family_no_kernel_error(h); break;
+    case PTE_TARGET_DENSE_NORMAL: if (dense_refresh_stats(E, N, h->stream, h->dev, h->dense)) return family_no_kernel_error(h); break;
     case PTE_TARGET_MIXTURE_MODEL: if (mixture_model_refresh_stats((int)(h->d / 3), N, h->stream, h->dev, h->mixmodel, h->cfg.target_params[0])) return family_no_kernel_error(h); break;
     case PTE_TARGET_VARIABLE_SELECTION: if (varsel_refresh_stats(E, h->varsel_lik, N, h->stream, h->dev, h->varsel, h->cfg.target_params[0])) return family_no_kernel_error(h); break;
     case PTE_TARGET_CHANGE_POINT: if (changepoint_refresh_stats(N, h->stream, h->dev, h->changepoint, h->cfg.target_params[0])) return family_no_kernel_error(h); break;
@@ -1042,7 +1052,7 @@ int validate_config(const pte_config *cfg) {
         if (cfg->slice_w != std::floor(cfg->slice_w) || !std::isfinite(cfg->slice_w))      // SliceSampler.jl:137 (@assert), the oracle's text
             return fail(nullptr, "pte_create: for integer variables, the width should be an integer. Got: %g", cfg->slice_w);
     }
-    if (family && !funnel) {    // the families with kernels of their own -- Gaussian mixture, Bayesian GLM, mixture model, hierarchical normal means, latent AR(1): one wave per replica, SliceSampler / AutoMALA / MALA (AAPS: refused above)
+    if (family && !funnel) {    // the families with kernels of their own -- Gaussian mixture, Bayesian GLM, mixture model, hierarchical normal means, latent AR(1), dense normal: one wave per replica, SliceSampler / AutoMALA / MALA (AAPS: refused above)
         auto on_family = [](int k) { return k == PTE_EXPLORER_SLICE || k == PTE_EXPLORER_AUTOMALA || k == PTE_EXPLORER_MALA; };
         if (!on_family(cfg->explorer) || (cfg->explorer2 != PTE_EXPLORER_NONE && !on_family(cfg->explorer2)))
             return fail(nullptr, "pte_create: the %s path is implemented for SliceSampler / AutoMALA / MALA (and Compose of them) only (got explorers %d, %d)",
@@ -2015,6 +2025,7 @@ const char *pte_kernel_name(const pte_engine *h) {
     case PTE_EXPLORER_SLICE:
         // SliceSampler on the interpolated path: the one-wave Langevin-family kernel in its slice mode (no momentum, gradient or trial copies:
         // its sixteen-block instantiation for d > 512 holds 255 VGPRs + 7 AGPRs and does not touch scratch)
+        if (h->cfg.target == PTE_TARGET_DENSE_NORMAL) return "k_explore_dense_slice";      // the cached-slice kernel
         if (f) return f->kernel;
         switch (h->slice_impl) {
         case 1: return "k_explore_slice"; case 2: return "k_explore_slice2"; case 5: return "k_explore_slice5";
@@ -2248,6 +2259,63 @@ int pte_set_target_ar1(pte_engine *h, int32_t likelihood, int64_t n_obs, const d
     p.c_sigma = std::log(2.0) - std::log(M_PI) - std::log(sigma_scale); p.iss = 1.0 / sigma_scale;
     p.iobs = normal ? 1.0 / obs_sd : 0.0; p.lobs = normal ? std::log(obs_sd) : 0.0;
     h->ar1_lik = likelihood;
+    return refresh_path_stats(h);                                  // suff / suff2 of the current states
+}
+
+// The dense-precision Gaussian N(mean, precision^-1).  Host, once per call: the refusals in their documented order, a
+// Cholesky factorisation for positive definiteness and c = sum_i log L_ii - (d/2) log 2 pi (the sum in index order); the matrix is uploaded
+// as [d][ld] with ld = 64 blocks_per_lane(d), zero-padded, followed by its diagonal [ld] and the mean [ld]: one allocation of (d + 2) ld
+// doubles, 2 MiB + 8 KiB at d = 512.  A refused call leaves the engine as it was.
+int pte_set_target_dense(pte_engine *h, int64_t dim, const double *mean, const double *precision) {
+    if (!h) return 1;
+    PTE_ALIVE(h, "pte_set_target_dense");
+    if (!mean || !precision) return fail(h, "pte_set_target_dense: null argument");
+    if (h->cfg.target != PTE_TARGET_DENSE_NORMAL)
+        return fail(h, "pte_set_target_dense: this engine's target is %d, not PTE_TARGET_DENSE_NORMAL", h->cfg.target);
+    const int64_t d = h->d;
+    if (dim != d) return fail(h, "pte_set_target_dense: dim must be the engine's dim = %lld (got %lld)", (long long)d, (long long)dim);
+    for (int64_t i = 0; i < d; ++i)
+        if (!std::isfinite(mean[i])) return fail(h, "pte_set_target_dense: mean[%lld] must be finite (got %g)", (long long)i, mean[i]);
+    for (int64_t i = 0; i < d; ++i)
+        for (int64_t j = 0; j < d; ++j)
+            if (!std::isfinite(precision[i * d + j]))
+                return fail(h, "pte_set_target_dense: precision[%lld][%lld] must be finite (got %g)", (long long)i, (long long)j, precision[i * d + j]);
+    for (int64_t i = 0; i < d; ++i)
+        for (int64_t j = i + 1; j < d; ++j)
+            if (std::memcmp(&precision[i * d + j], &precision[j * d + i], sizeof(double)) != 0)      // bitwise: the kernels read row k as column k
+                return fail(h, "pte_set_target_dense: precision must be symmetric bit for bit: precision[%lld][%lld] = %.17g, precision[%lld][%lld] = %.17g",
+                            (long long)i, (long long)j, precision[i * d + j], (long long)j, (long long)i, precision[j * d + i]);
+    std::vector<double> L((size_t)(d * d), 0.0);                   // Cholesky, column by column: Q = L L'
+    double sum_log = 0.0;
+    for (int64_t j = 0; j < d; ++j) {
+        double piv = precision[j * d + j];
+        for (int64_t k = 0; k < j; ++k) piv -= L[(size_t)(j * d + k)] * L[(size_t)(j * d + k)];
+        if (!(piv > 0.0) || !std::isfinite(piv))
+            return fail(h, "pte_set_target_dense: precision is not positive definite: the Cholesky pivot %lld is %g", (long long)j, piv);
+        const double ljj = std::sqrt(piv);
+        L[(size_t)(j * d + j)] = ljj;
+        sum_log += std::log(ljj);
+        for (int64_t i = j + 1; i < d; ++i) {
+            double s = precision[i * d + j];
+            for (int64_t k = 0; k < j; ++k) s -= L[(size_t)(i * d + k)] * L[(size_t)(j * d + k)];
+            L[(size_t)(i * d + j)] = s / ljj;
+        }
+    }
+    HIP_OK(h, hipSetDevice(h->cfg.device));
+    const int64_t ld = 64 * (int64_t)blocks_per_lane(d);
+    std::vector<double> buf((size_t)((d + 2) * ld), 0.0);
+    for (int64_t i = 0; i < d; ++i) {
+        for (int64_t j = 0; j < d; ++j) buf[(size_t)(i * ld + j)] = precision[i * d + j];
+        buf[(size_t)(d * ld + i)] = precision[i * d + i];
+        buf[(size_t)((d + 1) * ld + i)] = mean[i];
+    }
+    if (!h->d_dense && dev_alloc(h, &h->d_dense, buf.size(), false)) return 1;
+    HIP_OK(h, hipMemcpyAsync(h->d_dense, buf.data(), sizeof(double) * buf.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    DenseParams &p = h->dense;
+    p.q = h->d_dense; p.diag = h->d_dense + d * ld; p.mean = h->d_dense + (d + 1) * ld;
+    p.n = (int)d; p.ld = (int)ld;
+    p.c = sum_log - 0.5 * (double)d * std::log(2.0 * M_PI);
     return refresh_path_stats(h);                                  // suff / suff2 of the current states
 }
 

@@ -18,12 +18,15 @@
 //              pte_hier.hpp): x = [mu, log tau, one coordinate per group], elementwise but for the two hyper-parameters' gradient sums
 //   TGT_AR1    the same path with a latent-AR(1) state-space posterior as the target, LIK = AR1_* the observation model (DESIGN 4.15;
 //              pte_ar1.hpp): x = [mu, a, ls, h_0 .. h_{T-1}], every h coupled to its two neighbours through a one-lane wave shift
+//   TGT_DENSE  the same path with N(m, Q^-1), Q a dense precision matrix, as the target (pte_dense.hpp): O(d^2) per evaluation,
+//              the matrix read row by row from L2, every z_k broadcast by a read-lane
 #pragma once
 #include "pte_automala_params.hpp"
 #include "pte_glm_params.hpp"
 #include "pte_mixture_model_params.hpp"
 #include "pte_hier_params.hpp"
 #include "pte_ar1_params.hpp"
+#include "pte_dense_params.hpp"
 #include "pte_slice_coord.hpp"
 
 namespace pte {
@@ -130,6 +133,9 @@ template <int E> struct AmAr1Data<true, E> {
     Ar1Params ar;
     double ad[A_IN_REGS ? E : 1];
 };
+// TGT_DENSE's data: the same arrangement.  Nothing of it stays in registers: the mean is read once per evaluation, the matrix row by row
+template <bool ON, int E> struct AmDenseData {};
+template <int E> struct AmDenseData<true, E> { DenseParams dn; };
 // The whole wave shifted by one lane (DPP wave_shr:1 / wave_shl:1, two v_mov_b32_dpp per double): lane l takes v of lane l - 1 (l + 1); the
 // lane at the end that has no source keeps `edge` -- the neighbouring 64-block's value (uniform), so a chain over coordinates 64 j + lane
 // reaches its predecessor and its successor without LDS or memory (TGT_AR1)
@@ -145,7 +151,7 @@ __device__ __forceinline__ double wave_from_above_f64(double v, double edge) {
 }
 
 template <int E, int TGT, bool FULL = false, int KB = 1, int LIK = 0>
-struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>, AmHierData<TGT == TGT_HIER, E>, AmAr1Data<TGT == TGT_AR1, E> {
+struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>, AmHierData<TGT == TGT_HIER, E>, AmAr1Data<TGT == TGT_AR1, E>, AmDenseData<TGT == TGT_DENSE, E> {
     int64_t d; int lane;
     double nhp, nprec;          // MVN: -0.5*prec, -prec of this chain
     double beta, omb, ref_nhp, ref_nprec, log3;   // funnel path
@@ -618,9 +624,87 @@ struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>
         double S, Q, dummy[E];
         return ar1_and_sqr_norm<false, false>(x, dummy, S, x, Q);
     }
+    // the dense-precision Gaussian N(m, Q^-1): z = x - m, u = Q z, A = z' u, l2 = c - A / 2, gradient -u.  u_i = sum_k Q[k][i] z_k
+    // is accumulated for k = 0 .. d-1 in that order, one fused multiply-add per term from 0.0: row k of the symmetric matrix is E coalesced
+    // loads (lane l takes Q[k][64 j + l]), z_k reaches every lane through a read-lane with a uniform index -- no LDS, no memory round trip.
+    // DENSE_ROWS rows are requested before the first of their multiply-adds, so that a row costs an issue slot, not an L2 latency.  The rows
+    // are zero from d on, and so are x and m: lanes past d hold u = z = 0 without a mask.  A = the fixed-tree sum of z_i u_i, in lockstep with
+    // S = sum x^2 and (WITH_Q) Q = sum q^2.
+    static constexpr int DENSE_ROWS = 8;
+    __device__ __forceinline__ void dense_core(const double (&x)[E], double (&z)[E], double (&u)[E]) const {
+        const DenseParams &dn = this->dn;
+        const int dd = FULL ? 64 * E : (int)d;
+#pragma unroll
+        for (int j = 0; j < E; ++j) { z[j] = x[j] - dn.mean[64 * j + lane]; u[j] = 0.0; }      // ([ld]: in bounds whatever d)
+        const double *row = dn.q + lane;
+        const int64_t ld = dn.ld;
+#pragma unroll
+        for (int jb = 0; jb < E; ++jb) {
+            const int nl = FULL ? 64 : max(0, min(64, dd - 64 * jb));
+            int l = 0;
+#pragma nounroll                                           // (whole blocks have a constant trip count: unrolled further, the rows in flight spill)
+            for (; l + DENSE_ROWS <= nl; l += DENSE_ROWS, row += DENSE_ROWS * ld) {
+                double r[DENSE_ROWS][E];
+#pragma unroll
+                for (int t = 0; t < DENSE_ROWS; ++t)
+#pragma unroll
+                    for (int j = 0; j < E; ++j) r[t][j] = row[t * ld + 64 * j];
+#pragma unroll
+                for (int t = 0; t < DENSE_ROWS; ++t) {
+                    const double zk = readlane_f64(z[jb], l + t);
+#pragma unroll
+                    for (int j = 0; j < E; ++j) u[j] = __builtin_fma(r[t][j], zk, u[j]);
+                }
+            }
+#pragma nounroll
+            for (; l < nl; ++l, row += ld) {
+                const double zk = readlane_f64(z[jb], l);
+#pragma unroll
+                for (int j = 0; j < E; ++j) u[j] = __builtin_fma(row[64 * j], zk, u[j]);
+            }
+        }
+    }
+    // A and S (and Q) of a state whose z and u are at hand
+    template <bool WITH_Q>
+    __device__ __forceinline__ void dense_sums(const double (&x)[E], const double (&z)[E], const double (&u)[E], double &A, double &S,
+                                               const double (&q)[E], double &Q) const {
+        constexpr int K = 2 + (WITH_Q ? 1 : 0);
+        double t[K][E], out[K];
+#pragma unroll
+        for (int j = 0; j < E; ++j) {
+            t[0][j] = x[j] * x[j];
+            t[1][j] = z[j] * u[j];
+            if constexpr (WITH_Q) t[2][j] = q[j] * q[j];
+        }
+        tree_sum_regs_multi<E, K>(t, out);
+        S = out[0]; A = out[1];
+        if constexpr (WITH_Q) Q = out[2];
+    }
+    template <bool GRAD, bool WITH_Q>
+    __device__ __forceinline__ double dense_and_sqr_norm(const double (&x)[E], double (&g)[E], double &S, const double (&q)[E], double &Q) const {
+        double z[E], u[E], A;
+        dense_core(x, z, u);
+        dense_sums<WITH_Q>(x, z, u, A, S, q, Q);
+        if constexpr (GRAD) {
+#pragma unroll
+            for (int j = 0; j < E; ++j) g[j] = -u[j];
+        }
+        return this->dn.c - 0.5 * A;
+    }
+    __device__ __forceinline__ double dense(const double (&x)[E]) const {
+        double S, Q, dummy[E];
+        return dense_and_sqr_norm<false, false>(x, dummy, S, x, Q);
+    }
     // log_potentials[chain](x) as a plain callable: InterpolatedLogPotential(x) (src/paths/InterpolatedLogPotential.jl:9-16)
     // WITH its beta == 0 / beta == 1 short-circuits -- what SliceSampler evaluates (the AD form below has none)
     __device__ __forceinline__ double path_lp(const double (&x)[E]) const {
+        if constexpr (TGT == TGT_DENSE) {
+            if (beta == 0.0) return ref_nhp * sqr_norm_regs<E>(x);
+            double S, Q, dummy[E];
+            const double l2 = dense_and_sqr_norm<false, false>(x, dummy, S, x, Q);
+            if (beta == 1.0) return l2;
+            return omb * (ref_nhp * S) + beta * l2;
+        }
         if constexpr (TGT == TGT_AR1) {
             if (beta == 0.0) return ref_nhp * sqr_norm_regs<E>(x);
             double S, Q, dummy[E];
@@ -668,6 +752,10 @@ struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>
     __device__ __forceinline__ double logdensity(const double (&x)[E]) const {
         if (TGT == TGT_MVN) return nhp * sqr_norm_regs<E>(x);
         double S, l2, dummy[E], dq;
+        if constexpr (TGT == TGT_DENSE) {
+            l2 = dense_and_sqr_norm<false, false>(x, dummy, S, x, dq);
+            return omb * (ref_nhp * S) + beta * l2;
+        }
         if constexpr (TGT == TGT_AR1) {
             l2 = ar1_and_sqr_norm<false, false>(x, dummy, S, x, dq);
             return omb * (ref_nhp * S) + beta * l2;
@@ -712,6 +800,14 @@ struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>
         double logdens = 0.0;
         double g2[E];
         double l2;
+        if constexpr (TGT == TGT_DENSE) {
+            l2 = dense_and_sqr_norm<true, WITH_Q>(x, g2, S, q, Q);
+            logdens += (ref_nhp * S) * omb;
+            logdens += l2 * beta;
+#pragma unroll
+            for (int j = 0; j < E; ++j) g[j] = (ref_nprec * x[j]) * omb + g2[j] * beta;
+            return logdens;
+        }
         if constexpr (TGT == TGT_AR1) {
             l2 = ar1_and_sqr_norm<true, WITH_Q>(x, g2, S, q, Q);
             logdens += (ref_nhp * S) * omb;
@@ -791,11 +887,12 @@ __device__ __forceinline__ int64_t am_chain_of_workgroup(int64_t K, int64_t wg) 
 // KB, mp: TGT_MIXTURE only -- the components' bucket (K <= KB) and parameters.  LIK, gp: TGT_GLM only -- the likelihood and the data
 // (the workgroup's dynamic LDS holds theta and r: pte_glm.hpp).  mm: TGT_MIXMODEL only -- the observations (pte_mixture_model.hpp)
 // hp: TGT_HIER only -- the groups' data, LIK its parameterisation (pte_hier.hpp).  ar: TGT_AR1 only -- the observations, LIK the observation
-// model (pte_ar1.hpp)
+// model (pte_ar1.hpp).  dn: TGT_DENSE only -- the mean and the precision matrix (pte_dense.hpp)
 template <int E, int TGT, bool SLICE = false, bool FULL = false, bool DIRECT = false, int KB = 1, int LIK = 0>
 __device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const int64_t wg, const MixParams &mp = MixParams{},
                                               const GlmParams &gp = GlmParams{}, const MixModelParams &mm = MixModelParams{},
-                                              const HierParams &hp = HierParams{}, const Ar1Params &ar = Ar1Params{}) {      // wg: blockIdx.x
+                                              const HierParams &hp = HierParams{}, const Ar1Params &ar = Ar1Params{},
+                                              const DenseParams &dn = DenseParams{}) {      // wg: blockIdx.x
     constexpr int NLU = (E == 1 ? 0 : E == 2 ? 1 : E == 4 ? 2 : E == 8 ? 3 : 4);
     const int lane = lane_id();
     // the ziggurat tables of the momentum draws, staged once: a global gather per block of draws costs a memory round trip each time
@@ -823,6 +920,7 @@ __device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const in
     if constexpr (TGT == TGT_MIXMODEL) { T.mm = mm; T.mk = (int)(d / 3); }
     if constexpr (TGT == TGT_HIER) T.load_hier(hp);
     if constexpr (TGT == TGT_AR1) T.load_ar1(ar);
+    if constexpr (TGT == TGT_DENSE) T.dn = dn;
     T.nhp = e.nhp[c]; T.nprec = e.nprec[c];
     T.beta = e.beta[c]; T.omb = 1.0 - T.beta;
     T.ref_nhp = -0.5 * ap.ref_prec; T.ref_nprec = -ap.ref_prec; T.log3 = ap.log3;
@@ -879,6 +977,10 @@ __device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const in
         }
         if constexpr (TGT == TGT_AR1) {
             l20 = T.ar1(x);
+            if (lane == 0) e.suff2[slot] = l20;
+        }
+        if constexpr (TGT == TGT_DENSE) {
+            l20 = T.dense(x);
             if (lane == 0) e.suff2[slot] = l20;
         }
         record_after_explore_impl(e, cl, c, slot, lane, lp0, S0, l20, l30);
@@ -1156,10 +1258,11 @@ __device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const in
     if constexpr (TGT == TGT_MIXMODEL) l2 = T.mixmodel(x);
     if constexpr (TGT == TGT_HIER) l2 = T.hier(x);
     if constexpr (TGT == TGT_AR1) l2 = T.ar1(x);
+    if constexpr (TGT == TGT_DENSE) l2 = T.dense(x);
     if (v_on) l3 = T.variational_lp(x);
     if (lane == 0) {
         e.suff[slot] = S;
-        if (TGT == TGT_FUNNEL || TGT == TGT_MIXTURE || TGT == TGT_GLM || TGT == TGT_MIXMODEL || TGT == TGT_HIER || TGT == TGT_AR1) e.suff2[slot] = l2;
+        if (TGT == TGT_FUNNEL || TGT == TGT_MIXTURE || TGT == TGT_GLM || TGT == TGT_MIXMODEL || TGT == TGT_HIER || TGT == TGT_AR1 || TGT == TGT_DENSE) e.suff2[slot] = l2;
         if (v_on) e.suff3[slot] = l3;
         e.rng[2 * slot] = r.seed;
         e.expl_steps_sum[cl] += (double)steps_sum; e.expl_steps_n[cl] += steps_n;

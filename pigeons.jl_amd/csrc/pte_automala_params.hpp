@@ -11,7 +11,8 @@
 //                     to an existing unit moves the generated code of the kernels already in it (tests/test_codegen_*.py freeze it).
 //                     pte_glm.hip also holds the hierarchical normal-means kernels (pte_hier.hpp): they share automala_body and
 //                     the unit's RNG-policy setter with the GLM's, and the assembly of every kernel that was there before stayed identical;
-//                     so do the latent-AR(1) kernels (pte_ar1.hpp), under the same check
+//                     so do the latent-AR(1) kernels (pte_ar1.hpp) and the dense-precision Gaussian kernels (pte_dense.hpp,
+//                     DESIGN 4.16), under the same check
 // Every unit includes pte_kernels.hpp and therefore holds its own copy of the `static __device__` word g_rng_policy: PTE_KERNEL_UNITS below.
 // Tools and development builds compile pte.hip alone (no -DPTE_SPLIT_LANGEVIN): it then includes the kernel headers and their entry points itself.
 #pragma once
@@ -20,7 +21,7 @@
 
 namespace pte {
 
-enum { TGT_MVN = 0, TGT_FUNNEL = 2, TGT_MIXTURE = 4, TGT_GLM = 5, TGT_MIXMODEL = 6, TGT_HIER = 9, TGT_AR1 = 10 };
+enum { TGT_MVN = 0, TGT_FUNNEL = 2, TGT_MIXTURE = 4, TGT_GLM = 5, TGT_MIXMODEL = 6, TGT_HIER = 9, TGT_AR1 = 10, TGT_DENSE = 11 };
 
 // TGT_MIXTURE (pte_mixture.hpp): the normalised mixture of K diagonal Gaussians, shared by every replica.  mu / inv: [K][ld]
 // (ld = the state row's stride, zero-padded), c: [K]; the kernels read mu and inv as lane-coalesced global loads.

@@ -43,6 +43,7 @@ const TARGET_HIERARCHICAL_NORMAL = Int32(9)
 const HIER_CENTERED, HIER_NONCENTERED = Int32(0), Int32(1)
 const TARGET_LATENT_AR1 = Int32(10)
 const AR1_STOCHASTIC_VOLATILITY, AR1_NORMAL_IDENTITY = Int32(0), Int32(1)
+const TARGET_DENSE_NORMAL = Int32(11)
 const GLM_BERNOULLI_LOGIT, GLM_NORMAL_IDENTITY = Int32(0), Int32(1)
 const EXPLORER_NONE, EXPLORER_TOY, EXPLORER_SLICE, EXPLORER_AUTOMALA, EXPLORER_ISING, EXPLORER_MALA, EXPLORER_AAPS = Int32.((0, 1, 2, 3, 4, 5, 6))
 const RECORD_ROUND_TRIP, RECORD_INDEX_PROCESS, RECORD_ONLINE, RECORD_TRACES, RECORD_ENERGY_AC1, RECORD_TRACES_EXTENDED =
@@ -152,6 +153,11 @@ sigma ~ HalfCauchy(0, sigma_scale), observed as y_t ~ N(0, exp(h_t)) (`likelihoo
 on_mi355x(DeviceLatentAR1(y, :stochastic_volatility, 1.0, 5.0, 0.0, 1.0, 1.0)), reference = ScaledPrecisionNormalLogPotential(p, T + 3))`.
 stepping_stone(pt) + (dim/2) log(2 pi / p) is the log evidence."""
 struct DeviceLatentAR1; y::Vector{Float64}; likelihood::Symbol; obs_sd::Float64; mu_sd::Float64; phi_loc::Float64; phi_scale::Float64; sigma_scale::Float64; end
+"""The multivariate normal N(mean, precision^-1) with a dense precision matrix, the device family PTE_TARGET_DENSE_NORMAL (DESIGN 4.16):
+`precision` is dim x dim, symmetric bit for bit (pass `(Q + Q') / 2`) and positive definite, dim <= 512; the density is normalised.  Used as
+`Inputs(target = on_mi355x(DeviceDenseNormal(mean, precision)), reference = ScaledPrecisionNormalLogPotential(p, dim))`.
+stepping_stone(pt) + (dim/2) log(2 pi / p) estimates the log evidence, which is 0."""
+struct DeviceDenseNormal; mean::Vector{Float64}; precision::Matrix{Float64}; end
 
 # (target code, dim, target_params, reference precision check) of a wrapped target
 device_family(t::ScaledPrecisionNormalPath, inputs) = (TARGET_MVN, t.dim, (t.precision0, t.precision1, 0.0, 0.0))
@@ -207,6 +213,15 @@ function device_family(t::DeviceLatentAR1, inputs)
     ref isa ScaledPrecisionNormalLogPotential && ref.dim == dim ||
         error("the device latent-AR(1) path needs reference = ScaledPrecisionNormalLogPotential(precision, $dim); keep the CPU path otherwise")
     return (TARGET_LATENT_AR1, dim, (ref.precision, 0.0, 0.0, 0.0))
+end
+function device_family(t::DeviceDenseNormal, inputs)
+    dim = length(t.mean)
+    1 <= dim <= 512 || error("DeviceDenseNormal: the device holds 1..512 coordinates")
+    size(t.precision) == (dim, dim) || error("DeviceDenseNormal: precision is dim x dim, mean has the dim entries")
+    ref = inputs.reference
+    ref isa ScaledPrecisionNormalLogPotential && ref.dim == dim ||
+        error("the device dense-normal path needs reference = ScaledPrecisionNormalLogPotential(precision, $dim); keep the CPU path otherwise")
+    return (TARGET_DENSE_NORMAL, dim, (ref.precision, 0.0, 0.0, 0.0))
 end
 function device_family(t::DeviceSpikeSlabRegression, inputs)
     n, d = size(t.X)
@@ -367,6 +382,11 @@ function Pigeons.create_replicas(inputs::Inputs{<:OnDevice}, shared::Shared, sou
         lik = g.likelihood === :normal_identity ? AR1_NORMAL_IDENTITY : AR1_STOCHASTIC_VOLATILITY
         check(r, ccall((:pte_set_target_ar1, libpte), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Float64, Float64, Float64, Float64, Float64),
                        r.handle, lik, length(g.y), g.y, g.obs_sd, g.mu_sd, g.phi_loc, g.phi_scale, g.sigma_scale))
+    end
+    if t.target isa DeviceDenseNormal               # the mean and the precision matrix as pte_set_target_dense reads them
+        g = t.target
+        Q = Matrix{Float64}(permutedims(g.precision))     # row-major for the C ABI (the matrix is symmetric: the same bits)
+        check(r, ccall((:pte_set_target_dense, libpte), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}), r.handle, length(g.mean), g.mean, Q))
     end
     if t.target isa DevicePoissonChangePoint        # the counts as pte_set_target_changepoint reads them
         check(r, ccall((:pte_set_target_changepoint, libpte), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), r.handle, t.target.y, length(t.target.y)))

@@ -138,6 +138,14 @@ class Engine:
         self._chk(self.L.pte_set_target_ar1(self.h, int(likelihood), ya.size, _dp(ya), float(obs_sd), float(mu_sd), float(phi_loc),
                                             float(phi_scale), float(sigma_scale)))
 
+    def set_target_dense(self, mean, precision):
+        """pte_set_target_dense: the mean [dim] and the precision matrix [dim][dim] (row-major, symmetric bit for bit, positive definite)"""
+        ma = np.ascontiguousarray(mean, dtype=np.float64).ravel()
+        qa = np.ascontiguousarray(precision, dtype=np.float64)
+        if qa.ndim != 2 or qa.shape != (ma.size, ma.size):
+            raise ValueError("set_target_dense: precision must be dim x dim with dim = len(mean) = %d (got shape %s)" % (ma.size, qa.shape))
+        self._chk(self.L.pte_set_target_dense(self.h, ma.size, _dp(ma), _dp(qa)))
+
     # --- hot path
     def explore(self, scan):
         self._chk(self.L.pte_explore(self.h, scan))

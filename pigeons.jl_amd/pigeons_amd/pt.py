@@ -311,6 +311,67 @@ class LatentAR1:
         return "LatentAR1(%s, T=%d, dim=%d)" % (self.likelihood, self.n_obs, self.dim)
 
 
+class DenseNormal:
+    """The multivariate normal N(mean, precision^-1) with a dense precision matrix, the device's first family whose log potential costs
+    O(d^2): an ill-conditioned Gaussian, a conjugate regression posterior, a Laplace approximation.  Exactly one of
+    `precision` and `covariance` is given (dim x dim, 1 <= dim <= 512); it is symmetrised with (Q + Q') / 2 and must be positive definite.
+    The density is normalised.  Tempered through the default InterpolatingPath(reference, target) (src/targets/target.jl:72-75) from
+    reference=ScaledPrecisionNormalLogPotential(p, dim), unnormalised; initialization = zeros(dim); default explorer SliceSampler (target.jl:20),
+    which on this family evaluates a proposal in O(1) and reads one matrix row per coordinate.
+
+    Everything about the path is exact: chain beta is Gaussian (chain_moments), and the log evidence of the normalised target is 0, so
+    stepping_stone(pt) - evidence_offset(p) estimates 0."""
+
+    def __init__(self, mean, precision=None, *, covariance=None):
+        if (precision is None) == (covariance is None):
+            raise ValueError("DenseNormal: give exactly one of precision and covariance")
+        mean = np.array(mean, dtype=np.float64)
+        if mean.ndim != 1 or not 1 <= mean.size <= 512:
+            raise ValueError("DenseNormal: mean must be a vector of 1..512 entries (got shape %s)" % (mean.shape,))
+        if not np.all(np.isfinite(mean)):
+            raise ValueError("DenseNormal: mean[%d] must be finite" % int(np.flatnonzero(~np.isfinite(mean))[0]))
+        name = "precision" if covariance is None else "covariance"
+        M = np.array(precision if covariance is None else covariance, dtype=np.float64)
+        if M.ndim != 2 or M.shape != (mean.size, mean.size):
+            raise ValueError("DenseNormal: %s must be %d x %d, the mean's length (got shape %s)" % (name, mean.size, mean.size, M.shape))
+        if not np.all(np.isfinite(M)):
+            i, j = np.argwhere(~np.isfinite(M))[0]
+            raise ValueError("DenseNormal: %s[%d][%d] must be finite" % (name, i, j))
+        M = (M + M.T) / 2.0
+        try:
+            np.linalg.cholesky(M)
+        except np.linalg.LinAlgError:
+            raise ValueError("DenseNormal: %s must be positive definite" % name) from None
+        if covariance is not None:
+            M = np.linalg.inv(M)
+            M = (M + M.T) / 2.0
+            try:
+                np.linalg.cholesky(M)
+            except np.linalg.LinAlgError:
+                raise ValueError("DenseNormal: covariance is too ill-conditioned to invert to a positive-definite precision") from None
+        self.mean, self.precision = mean, np.ascontiguousarray(M)
+
+    @property
+    def dim(self):
+        return self.mean.size
+
+    def evidence_offset(self, precision):
+        """what stepping_stone(pt) is off the log evidence by: stepping_stone(pt) = log evidence + evidence_offset(p) with
+        evidence_offset(p) = -(d/2) log(2 pi / p), d = dim and p the reference's precision; the log evidence of this normalised target is 0"""
+        return -(self.dim / 2.0) * math.log(2.0 * math.pi / float(precision))
+
+    def chain_moments(self, beta, ref_precision):
+        """(mean, covariance) of chain beta of the path, exactly: its precision is P = (1 - beta) p I + beta Q and its mean P^-1 beta Q m"""
+        beta, p = float(beta), float(ref_precision)
+        P = (1.0 - beta) * p * np.eye(self.dim) + beta * self.precision
+        cov = np.linalg.inv(P)
+        cov = (cov + cov.T) / 2.0
+        return cov @ (beta * (self.precision @ self.mean)), cov
+
+    def __repr__(self):
+        return "DenseNormal(dim=%d)" % self.dim
+
+
 class SpikeSlabRegression:
     """Bayesian variable selection, a spike-and-slab regression: the data of BayesianGLM (X: n x d, y: n, the same two
     likelihoods) with an inclusion indicator per column.  The state is
@@ -738,6 +799,11 @@ class PT:
             if not isinstance(ref, ScaledPrecisionNormalLogPotential) or ref.dim != target.dim:
                 raise NotImplementedError("the device latent-AR(1) path needs reference=ScaledPrecisionNormalLogPotential(prec, dim)")
             kw.update(target=_lib.TARGET_LATENT_AR1, dim=target.dim, target_params=[ref.precision])
+        elif isinstance(target, DenseNormal):
+            ref = inputs.reference
+            if not isinstance(ref, ScaledPrecisionNormalLogPotential) or ref.dim != target.dim:
+                raise NotImplementedError("the device dense-normal path needs reference=ScaledPrecisionNormalLogPotential(prec, dim)")
+            kw.update(target=_lib.TARGET_DENSE_NORMAL, dim=target.dim, target_params=[ref.precision])
         elif isinstance(target, SpikeSlabRegression):
             ref = inputs.reference
             if not isinstance(ref, ScaledPrecisionNormalLogPotential) or ref.dim != target.n_columns:
@@ -827,6 +893,9 @@ class PT:
         if isinstance(target, LatentAR1):                # every engine (rank) holds the data
             for eng in (self.shards.engines if hasattr(self.shards, "engines") else [self.replicas]):
                 eng.set_target_ar1(target.likelihood_code, target.y, target.obs_sd, target.mu_sd, target.phi_loc, target.phi_scale, target.sigma_scale)
+        if isinstance(target, DenseNormal):              # every engine (rank) holds the data
+            for eng in (self.shards.engines if hasattr(self.shards, "engines") else [self.replicas]):
+                eng.set_target_dense(target.mean, target.precision)
         if isinstance(target, SpikeSlabRegression):      # every engine (rank) holds the data
             for eng in (self.shards.engines if hasattr(self.shards, "engines") else [self.replicas]):
                 eng.set_target_varsel(target.likelihood_code, target.X, target.y, target.noise_sd, target.inclusion_prob)
