@@ -31,6 +31,15 @@ namespace pte {
 // Straight-line variant of k_explore_slice7: the budgeted part of every stage is fully unrolled and
 // predicated (no exec-mask loops, no taken branches: a lone wave pays ~35 cycles of refetch per taken
 // branch); only the certain hypothesis (lane 0) can continue beyond the budgets, in rarely entered loops.
+// Round 8: whether lane 0 needs one of its three out-of-line paths is decided on the SCALAR side, by a bit test each, where it used to be a
+// v_cmp -> s_and -> s_cmp chain per test on the round's dependency chain (a lone wave pays ~40 cycles per trip from the vector to the scalar side):
+//   slow-path head exponential   bit p of a WIN-bit mask in SGPRs (one ballot per 64 draws when the window is filled), read through M0 at the
+//                                top of the round, in the shadow of the head's LDS round trip instead of behind it (it was ballot(E != E) & 1);
+//   more than S8_BD doublings    bit 0 of the ONE v_cmp the doubling block ends with, which is also `dbl_ok` of every lane (default range:
+//                                kd <= S8_BD < kcap holds for every lane, so neither kd nor a lane-0 mask enters);
+//   more than S8_BS proposals    bit 0 of the EXEC mask the shrinkage block ends with (an unfinished lane has made exactly S8_BS proposals, so
+//                                "may it make more" is the loop-invariant S8_BS < cap_iters, tested out of line).
+// The paths themselves, and which rounds take them, are what they were.
 #ifndef PTE_S8_BD
 #define PTE_S8_BD 3
 #endif
@@ -98,6 +107,12 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
     const double w11 = 1.1 * sp.w;
     const int cap_iters = min(sp.max_iter, CAP_ITERS);
     const int kcap = min(sp.p, 20);                    // window headroom: 2 + 20 + 24 draws per hypothesis
+    // "may lane 0 go on past the shrinkage budget?" is uniform and loop-invariant: a hypothesis that leaves the budgeted steps unfinished has
+    // made exactly S8_BS proposals (a finished one stops counting), so its n < cap_iters is this comparison (max_iter == S8_BS: false, and
+    // the unfinished coordinate goes to the exact sequential procedure, which raises what the reference raises)
+    const bool shr_more = S8_BS < cap_iters;
+    constexpr bool HAND_SHRINK = (S8_BS == PTE_S8_BS && S8_BS >= 6 && S8_BS <= 10);
+    constexpr bool N_IS_KN = (DBL_MODE == 2) && HAND_SHRINK;     // the step counter of the shrinkage block starts from kn0: it IS the chase word's count
 
     // hypothesis (g, rel) of this lane
     const int hg = s7_level(lane);
@@ -137,6 +152,12 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
     // exponentials: so  S(now) <= S(at the last exact point) + (sum of ALL exponentials of the windows used since) / |nhp|.
     // `wsum` = that sum for the current window; Sest is bumped by it at every refill and re-based at block boundaries.
     double wsum = 0.0;
+    // Which positions of the window hold a slow-path exponential (s_e[i] is NaN exactly there), as WIN bits on the scalar side: one ballot per
+    // 64 draws of the fill.  The round asks for bit p -- lane 0's position, a scalar -- before the head's LDS round trip instead of
+    // comparing what it returns.
+    typedef unsigned mask2_t __attribute__((ext_vector_type(2)));       // a lane mask as the register pair it is: a bit test of its low dword reads the register
+    typedef unsigned slow_mask_t __attribute__((ext_vector_type(WIN / 32)));
+    slow_mask_t slow_w;
     auto fill_window = [&]() __attribute__((always_inline)) {
         __syncthreads();                               // one wave per block: orders the LDS accesses
         double acc = 0.0;
@@ -151,6 +172,8 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
             s_u[i] = u52_to_unit(r);
             s_e[i] = fast ? ev : __longlong_as_double(0x7ff8000000000000LL);
             acc += fast ? ev : 0.0;
+            const uint64_t sb = ballot64(!fast);
+            slow_w[2 * k] = (unsigned)sb; slow_w[2 * k + 1] = (unsigned)(sb >> 32);
         }
         wsum = wave_sum_dpp(acc);
         p = 0;
@@ -204,7 +227,18 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                 for (int it = 0; it < S8_BD; ++it) Vd[it] = s_u[idx0 + 2 + it];
                 int ex0 = 0;
                 int cnt_base = 2;                            // draws of the head: E and u0 (+ lane 0's extra draws of a slow-path exponential)
-                if (__builtin_expect((ballot64(E != E) & 1ull) != 0ull, 0)) {
+                asm volatile("" : "+v"(cnt_base));    // (set here, ahead of the test: otherwise in a block of their own on the likely path)
+                // bit p of the window's slow-path mask: dword p >> 5 of the register tuple, selected through M0 (one wait state between the
+                // scalar write of M0 and s_movrels), shifted by p (a scalar shift looks at the low five bits of its count)
+                unsigned slow_b;
+                if constexpr (WIN == 512)
+                    asm("s_lshr_b32 m0, %[p], 5\n" "s_nop 0\n" "s_movrels_b32 %[o], s84\n" "s_lshr_b32 %[o], %[o], %[p]"
+                        : [o] "=&s"(slow_b) : [p] "s"(p), "{s[84:99]}"(slow_w) : "m0", "scc");
+                else
+                    asm("s_lshr_b32 m0, %[p], 5\n" "s_nop 0\n" "s_movrels_b32 %[o], s84\n" "s_lshr_b32 %[o], %[o], %[p]"
+                        : [o] "=&s"(slow_b) : [p] "s"(p), "{s[84:91]}"(slow_w) : "m0", "scc");
+                static_assert(WIN == 512 || WIN == 256, "the slow-path mask is sixteen or eight dwords");
+                if (__builtin_expect((slow_b & 1u) != 0u, 0)) {
                     // the certain hypothesis needs the ziggurat's slow path for its exponential (2.3 % of the coordinates):
                     // evaluate it exactly at its stream position; its other draws follow `ex0` positions later
                     SeqRng rs{wseed + (uint64_t)p * gamma, gamma};
@@ -246,6 +280,8 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                 // ---- doubling (:115-139): S8_BD predicated steps for every lane ...
                 int kd = 0;
                 double dmin_lr = 0.0;                    // min(dL, dR) after the budgeted steps (DBL_MODE 2: left by the hand-written block)
+                unsigned need_l0 = 0u;                   // (its low dword, as the statement left it: the bit test then reads the register itself)
+                uint64_t need_m = 0ull;                  // DBL_MODE 2: "still needs doubling" (dmin_lr < 0) as a lane mask, ONE compare at the end of the block
 #if PTE_S8_BD >= 1 && PTE_S8_BD <= 4 && !defined(PTE_S8_DOUBLING_SELECTS)
                 if constexpr (DBL_MODE == 2) {           // (the launcher picks this instantiation only for sp.p >= S8_BD: no second body in the loop)
                     // Round 4, the one-wave-per-SIMD kernel: a hypothesis that needs no (further) doubling drops out of EXEC by v_cmpx --
@@ -271,6 +307,7 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                     double t_, wd_;
                     int sLh_, sRh_;
                     uint64_t sv_, sx_;
+                    mask2_t sd_;
 #define PTE_S8_CSTEP(V) \
                     "v_cmp_ge_f64 vcc, 0.5, " V "\n" \
                     "v_min_f64 v[102:103], v[114:115], v[116:117]\n" \
@@ -297,14 +334,16 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                                  PTE_S8_CSTEP("%[V3]")
 #endif
                                  "s_mov_b64 exec, %[sv]\n"
-                                 "v_min_f64 v[102:103], v[114:115], v[116:117]\n"      // (all lanes: what "still needs doubling" is decided on below)
+                                 "v_min_f64 v[102:103], v[114:115], v[116:117]\n"      // (all lanes: what "still needs doubling" is decided on ...
+                                 "v_cmp_gt_f64_e64 %[sd], 0, v[102:103]\n"             //  ... here, ONCE: bit 0 sends lane 0 on, the complement is `dbl_ok` of every lane)
                                  : "+{v[96:97]}"(LL), "+{v[98:99]}"(RR), "+{v[114:115]}"(dL), "+{v[116:117]}"(dR), "+{v[104:105]}"(dmin), [kd] "+v"(kd),
-                                   "=&{v[102:103]}"(t_), "=&{v[112:113]}"(wd_), "=&{v119}"(sLh_), "=&{v121}"(sRh_), [sv] "=&s"(sv_), [sx] "=&s"(sx_)
+                                   "=&{v[102:103]}"(t_), "=&{v[112:113]}"(wd_), "=&{v119}"(sLh_), "=&{v121}"(sRh_), [sv] "=&s"(sv_), [sx] "=&s"(sx_), [sd] "=&s"(sd_)
                                  : "{v[110:111]}"(Q), "{v118}"(dbl_z0), "{v120}"(dbl_z1), [one] "v"(dbl_one_hi),
                                    [V0] "v"(Vd[0]), [V1] "v"(Vd[S8_BD > 1 ? 1 : 0]), [V2] "v"(Vd[S8_BD > 2 ? 2 : 0]), [V3] "v"(Vd[S8_BD > 3 ? 3 : 0])
                                  : "vcc", "scc");
 #undef PTE_S8_CSTEP
                     dmin_lr = t_;
+                    need_m = (uint64_t)sd_.x | ((uint64_t)sd_.y << 32); need_l0 = __builtin_amdgcn_readfirstlane(sd_.x);
                 } else
                 if (DBL_MODE == 1 && sp.p >= S8_BD) {    // (uniform; compile-time per kernel)
                     // Hand-written: a step runs under EXEC = "this hypothesis still needs doubling", the left / right extension under
@@ -389,7 +428,12 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                 // ... and the rest for the certain hypothesis only.  (Round 4 built the alternative -- no test inside the round, a round whose
                 // lane 0 ran out of a budget or met a slow-path exponential redoes lane 0 without budgets out of line and runs the tail again --
                 // and measured 0.948 against 0.762 ms: lane 0 IS the hypothesis that ended the chase before, a quarter of the rounds need it.)
-                if (__builtin_expect(ballot64(lane == 0 && (dmin_lr < 0.0) && kd < kcap) != 0ull, 0)) {
+                // FAST (S8_BD < p <= 20): every lane leaves the budgeted steps with kd <= S8_BD < kcap, so lane 0 goes on iff it still needs
+                // doubling -- bit 0 of the mask the block left, a scalar bit test: no compare, no lane-0 masking, no second trip to the scalar side
+                unsigned more_dbl;
+                if constexpr (FAST) more_dbl = need_l0 & 1u;
+                else more_dbl = ballot64(lane == 0 && (dmin_lr < 0.0) && kd < kcap) != 0ull ? 1u : 0u;
+                if (__builtin_expect(more_dbl != 0u, 0)) {
                     bool need = (lane == 0);
                     while (need) {
                         const double V = s_u[idx0 + 2 + kd];
@@ -406,11 +450,15 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                     }
                     asm volatile("" : "+v"(dL), "+v"(dR), "+v"(kd));
                     dmin_lr = fmin(dL, dR);
-                    if constexpr (FAST) dmin_lr = (kd >= sp.p) ? 0.0 : dmin_lr;   // (the reference's own limit p ended it: not a budget)
+                    if constexpr (FAST) {
+                        dmin_lr = (kd >= sp.p) ? 0.0 : dmin_lr;                   // (the reference's own limit p ended it: not a budget)
+                        need_m = ballot64(dmin_lr < 0.0);                         // (the other lanes' bits come out as they were)
+                        need_l0 = (unsigned)need_m;
+                    }
                 }
                 // ended by itself, not by a budget.  FAST (S8_BD < p <= 20): a speculative lane has kd <= S8_BD < p, and lane 0 leaves
                 // the loop above either satisfied or at kd = p, so "still needs doubling" alone decides
-                const bool dbl_ok = FAST ? !(dmin_lr < 0.0) : !((kd < sp.p) && (dmin_lr < 0.0));
+                const bool dbl_ok = FAST ? !__builtin_amdgcn_inverse_ballot_w64(need_m) : !((kd < sp.p) && (dmin_lr < 0.0));
                 double thr2 = 1e-6 * fmax(fabs(LL), fabs(RR));
                 if constexpr (DBL_MODE == 2) asm volatile("" : "+v"(thr2));       // (taken here: LL / RR then live on only as the shrinkage block's bracket, in place)
 #ifdef PTE_PROFILE_SECTIONS
@@ -428,19 +476,26 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                 // successor's window, "is this coordinate in the block", "did the doubling end by itself" as lane masks
                 double mthr = 2e-12 * Bq;
                 int kn0 = cnt_base + kd + succ_off;          // + n: offset of the successor in the next level's window
-                uint64_t pre_ok = ballot64(active && dbl_ok);
-                if constexpr (FAST) asm volatile("" : "+v"(mthr), "+v"(kn0), "+s"(pre_ok));
+                uint64_t pre_ok;
+                if constexpr (FAST) pre_ok = ballot64(active) & ~need_m;          // (the block's compare serves both: `dbl_ok` is not taken a second time)
+                else pre_ok = ballot64(active && dbl_ok);
                 double Lbar = LL, Rbar = RR, xf = xold, W = 0.0;
-                int n = 0;
+                int n = N_IS_KN ? kn0 : 0;                   // proposals made (+ kn0 where the hand-written tail takes the sum as it stands)
+                if constexpr (FAST) {
+                    if constexpr (N_IS_KN) asm volatile("" : "+v"(mthr), "+v"(n), "+s"(pre_ok));
+                    else asm volatile("" : "+v"(mthr), "+v"(kn0), "+s"(pre_ok));
+                }
                 bool fin = false;
-                uint64_t fin_m = 0ull;                       // `fin` as a lane mask, for the hand-written tail (hipcc moves a mask through v_cndmask + v_cmp otherwise)
+                unsigned unf_l0 = 0u;                        // (its low dword, as the block left it)
+                uint64_t unf_m = 0ull;                       // `!fin` as a lane mask -- the EXEC the block ends with -- for the test below and the hand-written tail (hipcc moves a mask through v_cndmask + v_cmp otherwise)
                 if constexpr (S8_BS == PTE_S8_BS && S8_BS >= 6 && S8_BS <= 10) {
                     // Hand-scheduled: a lane whose proposal lands inside the slice drops out of EXEC (v_cmpx), which freezes
                     // its result, step count and bracket -- no per-step selects, no mask arithmetic, no branches.  Fixed
                     // registers because the 64-bit selects address register halves.  (>= 2 instructions between a VALU
                     // write of VCC and its use as a lane mask; EXEC restored before the block ends.)
                     double t_;
-                    uint64_t fin_mask, exec_save;
+                    mask2_t unf_mask;
+                    uint64_t exec_save;
 #define PTE_S8_STEP(U) \
                     "v_add_f64 v[112:113], v[98:99], -v[96:97]\n" \
                     "v_mul_f64 v[102:103], " U ", v[112:113]\n" \
@@ -470,18 +525,18 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
 #if PTE_S8_BS >= 10
                                  PTE_S8_STEP("%[u9]")
 #endif
-                                 "s_andn2_b64 %[fin], %[sv], exec\n"
+                                 "s_mov_b64 %[unf], exec\n"
                                  "s_mov_b64 exec, %[sv]\n"
                                  "s_nop 3\n"
                                  : "+{v[96:97]}"(Lbar), "+{v[98:99]}"(Rbar), "=&{v[100:101]}"(xf), "=&{v[102:103]}"(t_),
-                                   "+{v[104:105]}"(dmin), "+{v106}"(n), "=&{v[112:113]}"(W), [fin] "=&s"(fin_mask), [sv] "=&s"(exec_save)
+                                   "+{v[104:105]}"(dmin), "+{v106}"(n), "=&{v[112:113]}"(W), [unf] "=&s"(unf_mask), [sv] "=&s"(exec_save)
                                  : "{v[108:109]}"(xold), "{v[110:111]}"(Q), [u0] "v"(u[0]), [u1] "v"(u[1]), [u2] "v"(u[2]), [u3] "v"(u[3]),
                                    [u4] "v"(u[4]), [u5] "v"(u[5]), [u6] "v"(u[S8_BS > 6 ? 6 : 0]), [u7] "v"(u[S8_BS > 7 ? 7 : 0]),
                                    [u8] "v"(u[S8_BS > 8 ? 8 : 0]), [u9] "v"(u[S8_BS > 9 ? 9 : 0])
-                                 : "vcc", "scc");        // (s_andn2 writes SCC)
+                                 : "vcc");
 #undef PTE_S8_STEP
-                    fin = __builtin_amdgcn_inverse_ballot_w64(fin_mask);
-                    fin_m = fin_mask;
+                    unf_m = (uint64_t)unf_mask.x | ((uint64_t)unf_mask.y << 32); unf_l0 = __builtin_amdgcn_readfirstlane(unf_mask.x);
+                    fin = !__builtin_amdgcn_inverse_ballot_w64(unf_m);
                 } else {
 #pragma unroll
                     for (int k = 0; k < S8_BS; ++k) {
@@ -496,25 +551,31 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                         Rbar = below ? Rbar : v;
                         fin = fin || (dv < 0.0);
                     }
-                    fin_m = ballot64(fin);
+                    unf_m = ballot64(!fin);
+                    unf_l0 = (unsigned)unf_m;
                 }
-                if (__builtin_expect(ballot64(lane == 0 && !fin && n < cap_iters) != 0ull, 0)) {
+                // lane 0 unfinished <=> bit 0 of the mask the block left (a scalar bit test); it has made S8_BS proposals then, and whether it may
+                // make more is `shr_more`, decided before the loops
+                if (__builtin_expect((unf_l0 & 1u) != 0u, 0)) {
+                  if (shr_more) {
                     // the certain hypothesis continues from its state after S8_BS rejected proposals
                     double dx = 1.0;
                     bool go = (lane == 0);
+                    const int n_off = N_IS_KN ? cnt_base + kd + succ_off : 0;      // (= kn0)
                     while (go) {
                         W = Rbar - Lbar;
-                        xf = Lbar + us[n] * W;
+                        xf = Lbar + us[n - n_off] * W;
                         n += 1;
                         dx = test(xf);
                         const bool below = xf < xold;
                         Lbar = below ? xf : Lbar;
                         Rbar = below ? Rbar : xf;
-                        go = !(dx < 0.0) && n < cap_iters;
+                        go = !(dx < 0.0) && n - n_off < cap_iters;
                     }
                     asm volatile("" : "+v"(dx), "+v"(n), "+v"(W));
                     fin = fin || (lane == 0 && dx < 0.0);
-                    fin_m = ballot64(fin);
+                    unf_m = ballot64(!fin);
+                  }
                 }
                 // W > thr2 at the last step (widths only shrink) rules out isapprox(Lbar, Rbar) at every step
                 // FAST drops two tests that cannot fail there: a NaN exponential makes Q, every d, dmin and Bq NaN, so it fails the margin
@@ -538,20 +599,20 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                     // word of a valid hypothesis: bits 0-5 its successor lane (0: none), bits 9-17 its draw count, bit 20 "one more
                     // coordinate done" -- the five words of the path are summed as they stand (successors pile up below bit 9, counts
                     // below bit 18).  An invalid hypothesis has word 0; so has lane 0 in `pk`, where a broken path ends up.
-                    const int kn = kn0 + n;
+                    const int kn = N_IS_KN ? n : kn0 + n;
                     const int wsucc = ((unsigned)kn < (unsigned)succ_wd) ? kn + succ_base : 0;
                     const int word_v = (kn << 9) + word_c9 + wsucc;
                     unsigned acc; uint64_t tmask, sA_, sB_; int w_, pk_, s0_, s1_, s2_, s3_, s4_;
                     asm volatile("v_cmp_gt_f64 vcc, %[W], %[thr]\n"
                                  "v_cndmask_b32_e64 %[w], 0, %[wv], %[pre]\n"          // in the block, doubling ended by itself
                                  "v_cmp_gt_f64_e64 %[sA], %[dm], %[mthr]\n"
-                                 "v_cndmask_b32_e64 %[w], 0, %[w], %[fin]\n"           // a proposal inside the slice within the budget
+                                 "v_cndmask_b32_e64 %[w], %[w], 0, %[unf]\n"           // a proposal inside the slice within the budget
                                  "v_cndmask_b32_e32 %[w], 0, %[w], vcc\n"              // interval still wider than the isapprox threshold
                                  "s_nop 0\n"
                                  "v_cndmask_b32_e64 %[w], 0, %[w], %[sA]\n"            // every decision clears the filter's margin
                                  "v_cndmask_b32_e64 %[pk], 0, %[w], %[nz]\n"
                                  : [w] "=&v"(w_), [pk] "=&v"(pk_), [sA] "=&s"(sA_)
-                                 : [wv] "v"(word_v), [pre] "s"(pre_ok), [fin] "s"(fin_m), [nz] "s"(0xFFFFFFFFFFFFFFFEull),
+                                 : [wv] "v"(word_v), [pre] "s"(pre_ok), [unf] "s"(unf_m), [nz] "s"(0xFFFFFFFFFFFFFFFEull),
                                    [W] "v"(W), [thr] "v"(thr2), [dm] "v"(dmin), [mthr] "v"(mthr)
                                  : "vcc");
                     // (a second statement: with vector outputs in the same one hipcc takes the scalar results for divergent and routes
@@ -610,7 +671,7 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                 {   // why the true path ends where it ends (slots 8..15: all 5 levels done, then the causes)
                     const bool mg = dmin > 2e-12 * Bq;
                     const int rc = !active ? 7 : (E != E) ? 1 : !dbl_ok ? 2 : !fin ? 3 : !valid ? 4 : !mg ? 5 : 0;
-                    const int cnt_ = cnt_base + kd + n;
+                    const int cnt_ = N_IS_KN ? n - succ_off : cnt_base + kd + n;
                     int o_ = 0, g_ = 0, why = 0;
                     for (g_ = 0; g_ < G; ++g_) {
                         if (l + g_ >= nl) { why = 7; break; }
@@ -628,7 +689,7 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                 // ================= chase the true path through the hypotheses =======================
                 // Branch free: every lane names its successor, the chase is one v_readlane per level.  An invalid
                 // hypothesis packs 0, so a broken path falls back to lane 0, which never carries the level >= 1 flag.
-                const int kn = kn0 + n;
+                const int kn = N_IS_KN ? n : kn0 + n;
                 const bool inw = (unsigned)kn < (unsigned)succ_wd;
                 const uint64_t vmask = ballot64(valid);
                 // word of a valid hypothesis: bits 0-7 its draw count, bit 16 "one more coordinate done", bits 24-29 its successor lane
