@@ -65,8 +65,11 @@ enum {
     PTE_TARGET_LATENT_AR1 = 10,          /* InterpolatingPath(normal ref, posterior of a latent AR(1) state-space model of T observations;
                                             pte_set_target_ar1): the state is [mu, atanh phi, log sigma, h_0 .. h_{T-1}], dim = T + 3 in
                                             4..512; SliceSampler / AutoMALA / MALA / Compose of them */
-    PTE_TARGET_DENSE_NORMAL = 11         /* InterpolatingPath(normal ref, N(mean, precision^-1) with a dense precision matrix;
+    PTE_TARGET_DENSE_NORMAL = 11,        /* InterpolatingPath(normal ref, N(mean, precision^-1) with a dense precision matrix;
                                             pte_set_target_dense): dim in 1..512; SliceSampler / AutoMALA / MALA / Compose of them */
+    PTE_TARGET_SPIN_GLASS = 12           /* InterpolatingPath(SpinGlass(0), SpinGlass(beta)): the +-J Edwards-Anderson model, PTE_TARGET_ISING with
+                                            quenched bonds (pte_set_target_spin_glass): dim = base_length^2, 2 <= base_length, dim <= 65536;
+                                            target_params[0] = beta; PTE_EXPLORER_ISING_METROPOLIS only */
 };
 /* PTE_TARGET_LATENT_AR1: the observation model */
 enum {
@@ -296,6 +299,16 @@ int pte_set_target_ar1(pte_engine *h, int32_t likelihood, int64_t n_obs, const d
  * pte_swap, pte_run_scans, pte_group_run_scans and pte_get_state fail.  Every chain of the path is Gaussian, and stepping_stone estimates
  * -(dim/2) log(2 pi / p), p = target_params[0] the reference's precision: the log evidence of the normalised target is 0.  DESIGN 4.16. */
 int pte_set_target_dense(pte_engine *h, int64_t dim, const double *mean /*[dim]*/, const double *precision /*[dim][dim]*/);
+/* PTE_TARGET_SPIN_GLASS: the quenched bonds of the base_length x base_length periodic lattice, row-major, every entry +1 or -1:
+ * bonds_right[i][j] couples site (i, j) with (i, (j + 1) mod L), bonds_down[i][j] couples (i, j) with ((i + 1) mod L, j).  The target is
+ * exp(beta S), S = sum_ij s_ij (bonds_right_ij s_i,j+1 + bonds_down_ij s_i+1,j) (at L = 2 the two bonds between the same pair of sites are
+ * distinct terms); with every bond +1 the family is PTE_TARGET_ISING bit for bit.  Refuses an engine of another target, a base_length
+ * that is not the engine's, a null argument, and the first entry that is not +-1 (by plane and index): +-J is the supported disorder --
+ * real-valued or diluted couplings break the two-threshold filter and the bit packing of the sweep.  A refused call leaves the engine as it
+ * was.  Otherwise uploads the bonds (one copy shared by all replicas) and recounts the swap statistic of the current states; may be called
+ * again to replace the bonds.  Until the first call pte_explore, pte_swap, pte_run_scans, pte_group_run_scans and pte_get_state fail.
+ * DESIGN 4.17. */
+int pte_set_target_spin_glass(pte_engine *h, int64_t base_length, const int8_t *bonds_right /*[L][L]*/, const int8_t *bonds_down /*[L][L]*/);
 /* PTE_TARGET_VARIABLE_SELECTION: the data of the target N(theta; 0, I / p) prod_j pi^gamma_j (1 - pi)^(1 - gamma_j)
  * prod_i p(y_i | eta_i = sum_j X[i][j] gamma_j theta_j) (p = target_params[0], the reference's precision; pi = inclusion_prob; X row-major
  * [n_obs][d] with d = dim / 2; likelihood PTE_GLM_*, noise_sd read by PTE_GLM_NORMAL_IDENTITY only).  Validates as pte_set_target_glm does

@@ -32,6 +32,7 @@
 #include "pte_mixture_model_params.hpp"
 #include "pte_varsel_params.hpp"
 #include "pte_changepoint_params.hpp"
+#include "pte_spinglass_params.hpp"
 #else                              // tools / development builds: one translation unit
 #include "pte_langevin_launch.hpp"
 #include "pte_aaps.hpp"
@@ -43,6 +44,7 @@
 #include "pte_mixture_model.hpp"
 #include "pte_varsel.hpp"
 #include "pte_changepoint.hpp"
+#include "pte_spinglass.hpp"
 #endif
 #include "pte_ising.hpp"
 #if defined(PTE_PROFILE_AM)               // debug builds only (tools/prof_automala.py): 12 words per wave, section times of k_explore_automala
@@ -123,6 +125,8 @@ struct pte_engine {
     int ar1_lik = 0;
     double *d_dense = nullptr;      // PTE_TARGET_DENSE_NORMAL: the precision matrix [d][ld], its diagonal [ld], the mean [ld], ld = 64 blocks_per_lane(d)
     DenseParams dense{};            // the uploaded data as the kernels read it; dense.n = 0 until pte_set_target_dense
+    unsigned char *d_sg_bytes = nullptr; unsigned *d_sg_words = nullptr;   // PTE_TARGET_SPIN_GLASS: the bonds, a byte per site and (L % 32 == 0) two bit-packed planes
+    SpinGlassParams spinglass{};    // the uploaded bonds as the kernels read them; spinglass.jb = nullptr until pte_set_target_spin_glass
     double step_size = 1.0;
     int am_n_refresh = 0;
     std::vector<double> fac_mean, rev_mean; std::vector<int64_t> fac_n, rev_n;
@@ -270,6 +274,9 @@ const PathFamily *path_family(int target) {
     }
 }
 bool on_interpolated_path(int target) { return path_family(target) != nullptr; }
+// the lattice targets: Bool states bit-packed in HBM, IsingMetropolis, no k_init; the device sees both as PTE_TARGET_ISING (suff = the pair sum,
+// bond-weighted on the spin glass: DESIGN 4.17)
+bool on_lattice(int target) { return target == PTE_TARGET_ISING || target == PTE_TARGET_SPIN_GLASS; }
 // the family's data has been uploaded (true for every target that needs none)
 bool family_ready(const pte_engine *h) {
     switch (h->cfg.target) {
@@ -281,12 +288,15 @@ bool family_ready(const pte_engine *h) {
     case PTE_TARGET_HIERARCHICAL_NORMAL: return h->hier.n > 0;
     case PTE_TARGET_LATENT_AR1: return h->ar1.n > 0;
     case PTE_TARGET_DENSE_NORMAL: return h->dense.n > 0;
+    case PTE_TARGET_SPIN_GLASS: return h->spinglass.jb != nullptr;
     default: return true;
     }
 }
 // (`h` reports; `of` is the engine that is not ready -- another one in pte_group_run_scans)
 int family_missing_error(pte_engine *h, const char *what, const pte_engine *of = nullptr) {
-    const PathFamily *f = path_family((of ? of : h)->cfg.target);
+    static const PathFamily spinglass{"spin-glass", "bonds", "pte_set_target_spin_glass", "", "k_explore_spinglass"};       // (a lattice target, on no interpolated normal path)
+    const int target = (of ? of : h)->cfg.target;
+    const PathFamily *f = target == PTE_TARGET_SPIN_GLASS ? &spinglass : path_family(target);
     return fail(h, "%s: the %s target has no %s yet; call %s first", what, f->name, f->data, f->setter);
 }
 int family_no_kernel_error(pte_engine *h) {
@@ -606,6 +616,13 @@ int launch_explorer_kind(pte_engine *h, int64_t scan, int kind) {
     case PTE_EXPLORER_ISING_METROPOLIS: {
         IsingParams ip{(int)std::llround(std::sqrt((double)h->d)), h->cfg.slice_n_passes, h->cfg.target_params[0]};
         time_begin(h, 0, true);
+        if (h->cfg.target == PTE_TARGET_SPIN_GLASS) {        // the same sweep with bond-weighted neighbours, kernels of its own (pte_spinglass.hpp)
+            SpinGlassParams gp = h->spinglass;
+            gp.n_steps = ip.n_steps;
+            if (spinglass_launch(SpinGlassLaunch{h->ising_impl == 2, launch_site(h, (unsigned)N)}, h->dev, gp)) return fail(h, "this build holds no spin-glass kernel for dim %lld", (long long)h->d);
+            time_end(h);
+            break;
+        }
         // L % 32 == 0: lane-speculative bit-packed sweep; other lattice sizes: the scalar byte-lattice kernel
         if (ip.L % 32 == 0 && h->ising_impl == 0) {
             if (ip.L == 32) PTE_LAUNCH1(k_explore_ising_spec<true>, dim3((unsigned)N), dim3(64), (size_t)(h->d / 8 + 8), h->stream, h->dev, ip);
@@ -829,7 +846,7 @@ int run_scans_fused(pte_engine *h, int64_t first_scan, int64_t n_scans) {
 int alloc_engine(pte_engine *h) {
     const pte_config *cfg = &h->cfg;
     const int64_t N = h->N, K = h->K, d = h->d;
-    const bool funnel = cfg->target == PTE_TARGET_FUNNEL, ising = cfg->target == PTE_TARGET_ISING, aaps = cfg->explorer == PTE_EXPLORER_AAPS;
+    const bool funnel = cfg->target == PTE_TARGET_FUNNEL, ising = on_lattice(cfg->target), aaps = cfg->explorer == PTE_EXPLORER_AAPS;
     auto grad_based = [](int k) { return k == PTE_EXPLORER_AUTOMALA || k == PTE_EXPLORER_MALA; };
     const bool uses_grad = grad_based(cfg->explorer) || grad_based(cfg->explorer2);
     EngineDev &e = h->dev;
@@ -840,7 +857,7 @@ int alloc_engine(pte_engine *h) {
         e.ld = (lw + 1) / 2; e.sw = e.ld;
     }
     // (the swap and recorder kernels see every family on an interpolated path as the funnel's: suff = sum x^2 for the reference, suff2 = the target's log density)
-    e.record_flags = cfg->record_flags; e.target = on_interpolated_path(cfg->target) ? PTE_TARGET_FUNNEL : cfg->target; e.test_swapper_pr = cfg->target_params[0];
+    e.record_flags = cfg->record_flags; e.target = on_interpolated_path(cfg->target) ? PTE_TARGET_FUNNEL : (ising ? PTE_TARGET_ISING : cfg->target); e.test_swapper_pr = cfg->target_params[0];
     const int64_t dd = d > 0 ? d : 1;
     int rc = 0;
     rc |= dev_alloc(h, &e.x, (size_t)(K * (e.ld > 0 ? e.ld : 1)));
@@ -930,7 +947,7 @@ int init_replicas(pte_engine *h) {
     const pte_config *cfg = &h->cfg;
     EngineDev &e = h->dev;
     const int64_t K = h->K;
-    const bool swapper = cfg->target == PTE_TARGET_TEST_SWAPPER, ising = cfg->target == PTE_TARGET_ISING;
+    const bool swapper = cfg->target == PTE_TARGET_TEST_SWAPPER, ising = on_lattice(cfg->target);
     const double init_sd = swapper ? 1.0 : std::sqrt(cfg->target_params[1]);   // toy_mvn_target.jl:10-11
     hipEvent_t init_a = nullptr, init_b = nullptr;       // k_init's duration: pte_timing_get(kernel = 2), one event pair per engine
     if (!ising) {
@@ -980,7 +997,7 @@ int init_zero_state(pte_engine *h) {
     const pte_config *cfg = &h->cfg;
     EngineDev &e = h->dev;
     const int64_t K = h->K, d = h->d;
-    const bool ising = cfg->target == PTE_TARGET_ISING;
+    const bool ising = on_lattice(cfg->target);
     std::vector<uint64_t> rngs((size_t)(2 * K));
     const uint64_t G = 0x9e3779b97f4a7c15ULL;
     auto mix64h = [](uint64_t z) { z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL; z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL; return z ^ (z >> 31); };
@@ -995,7 +1012,7 @@ int init_zero_state(pte_engine *h) {
     hipMemsetAsync(e.suff, 0, sizeof(double) * K, h->stream);
     std::vector<double> s2((size_t)K, funnel_at_zero(d));
     hipMemcpyAsync(e.suff2, s2.data(), sizeof(double) * K, hipMemcpyHostToDevice, h->stream);
-    if (ising) {   // all spins -1: every site contributes (-1)(-4) = 4, halved: sum_pair_products = 2 L^2
+    if (ising) {   // all spins -1: every site contributes (-1)(-4) = 4, halved: sum_pair_products = 2 L^2 (the spin glass: replaced by the sum of its bonds when they arrive)
         std::vector<double> spp((size_t)K, 2.0 * (double)d);
         hipMemcpyAsync(e.suff, spp.data(), sizeof(double) * K, hipMemcpyHostToDevice, h->stream);
         if (hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "ising init failed"; return 1; }
@@ -1016,7 +1033,7 @@ int validate_config(const pte_config *cfg) {
     if (cfg->n_chains % cfg->world_size != 0) return fail(nullptr, "pte_create: n_chains (%lld) must be a multiple of world_size (%d)", (long long)cfg->n_chains, cfg->world_size);
     const bool swapper = cfg->target == PTE_TARGET_TEST_SWAPPER;
     const bool funnel = cfg->target == PTE_TARGET_FUNNEL;
-    const bool ising = cfg->target == PTE_TARGET_ISING;
+    const bool ising = on_lattice(cfg->target), spin_glass = cfg->target == PTE_TARGET_SPIN_GLASS;
     const PathFamily *family = path_family(cfg->target);
     if (cfg->explorer == PTE_EXPLORER_AAPS || cfg->explorer2 == PTE_EXPLORER_AAPS) {       // AAPS (pte_aaps.hpp): one wave per replica, one explorer
         if (cfg->explorer2 != PTE_EXPLORER_NONE)
@@ -1072,11 +1089,14 @@ int validate_config(const pte_config *cfg) {
     }
     if (ising) {
         const int64_t L = (int64_t)std::llround(std::sqrt((double)cfg->dim));
+        if (spin_glass && (L < 2 || L * L != cfg->dim || cfg->dim > 65536))
+            return fail(nullptr, "pte_create: the spin-glass path needs dim = base_length^2 with 2 <= base_length and dim <= 65536 (got %lld)", (long long)cfg->dim);
         if (L < 2 || L * L != cfg->dim || cfg->dim > 65536) return fail(nullptr, "pte_create: Ising needs dim = base_length^2 <= 65536");
         if (cfg->explorer == PTE_EXPLORER_SLICE || cfg->explorer2 == PTE_EXPLORER_SLICE)   // spins are Bool coordinates: SliceSampler.jl:65-86 (and :136-142, :189 for Integer ones)
             return fail(nullptr, "pte_create: SliceSampler's Bool / Integer coordinate methods are not available on the device (its Float64 methods are); "
-                                 "the Ising path is explored by IsingMetropolis only -- use the reference CPU path for Bool / Integer states");
-        if (cfg->explorer != PTE_EXPLORER_ISING_METROPOLIS) return fail(nullptr, "pte_create: the Ising path is explored by IsingMetropolis only");
+                                 "the %s path is explored by IsingMetropolis only -- use the reference CPU path for Bool / Integer states", spin_glass ? "spin-glass" : "Ising");
+        if (cfg->explorer != PTE_EXPLORER_ISING_METROPOLIS || (spin_glass && cfg->explorer2 != PTE_EXPLORER_NONE))
+            return fail(nullptr, "pte_create: the %s path is explored by IsingMetropolis only", spin_glass ? "spin-glass" : "Ising");
     } else if (cfg->explorer == PTE_EXPLORER_ISING_METROPOLIS) return fail(nullptr, "pte_create: IsingMetropolis needs the Ising target");
     if (!swapper && !family && !ising && cfg->target != PTE_TARGET_MVN_SCALED_PRECISION)
         return fail(nullptr, "pte_create: target %d has no device log-potential; use the reference CPU path", cfg->target);
@@ -1118,7 +1138,7 @@ int validate_config(const pte_config *cfg) {
         const bool slice = cfg->explorer == PTE_EXPLORER_SLICE || cfg->explorer2 == PTE_EXPLORER_SLICE;
         bool ok = dk == 0 || (slice && dk == PTE_KERNEL_SLICE_SEQUENTIAL) || (ising && dk == PTE_KERNEL_ISING_BYTES);
 #ifdef PTE_TEST_KERNELS
-        ok = ok || (slice && (dk == 2 || dk == 5 || dk == 7 || dk == 8)) || (ising && dk == PTE_KERNEL_ISING_BITS);
+        ok = ok || (slice && (dk == 2 || dk == 5 || dk == 7 || dk == 8)) || (ising && !spin_glass && dk == PTE_KERNEL_ISING_BITS);
 #endif
         if (!ok) return fail(nullptr, "pte_create: debug_kernel %d is not available for this explorer in this build of libpte "
                                       "(0 = default, %d = sequential SliceSampler kernel; the other generations live in the test build libpte_test.so)",
@@ -1195,7 +1215,7 @@ int pte_create(const pte_config *cfg, pte_engine **out) {
     if (upload_ladder(h)) return bail(1);
     if (reset_recorders(h)) return bail(1);
     if (init_replicas(h)) return bail(1);
-    if ((on_interpolated_path(cfg->target) || cfg->target == PTE_TARGET_ISING) && init_zero_state(h)) return bail(1);
+    if ((on_interpolated_path(cfg->target) || on_lattice(cfg->target)) && init_zero_state(h)) return bail(1);
     *out = h;
     return 0;
 }
@@ -2043,6 +2063,7 @@ const char *pte_kernel_name(const pte_engine *h) {
     case PTE_EXPLORER_AAPS: return "k_explore_aaps";
     case PTE_EXPLORER_ISING_METROPOLIS: {
         const int64_t L = (int64_t)std::llround(std::sqrt((double)h->d));
+        if (h->cfg.target == PTE_TARGET_SPIN_GLASS) return (L % 32 == 0 && h->ising_impl == 0) ? "k_explore_spinglass_spec" : "k_explore_spinglass";
         return (L % 32 == 0 && h->ising_impl == 0) ? "k_explore_ising_spec" : (L % 32 == 0 && h->ising_impl == 1) ? "k_explore_ising_bits" : "k_explore_ising";
     }
     default: return "";
@@ -2319,6 +2340,49 @@ int pte_set_target_dense(pte_engine *h, int64_t dim, const double *mean, const d
     return refresh_path_stats(h);                                  // suff / suff2 of the current states
 }
 
+// The +-J spin glass.  Host, once per call: the refusals, then the bonds as the kernels read them -- one byte per site (bit 1:
+// the right bond is -1, bit 2: the down bond is -1) and, where base_length % 32 == 0, the two planes bit-packed like the lattice -- and suff
+// of every slot recounted under the new bonds.  May be called again: the allocation is made once.  A refused call leaves the engine as it was.
+int pte_set_target_spin_glass(pte_engine *h, int64_t base_length, const int8_t *bonds_right, const int8_t *bonds_down) {
+    if (!h) return 1;
+    PTE_ALIVE(h, "pte_set_target_spin_glass");
+    if (h->cfg.target != PTE_TARGET_SPIN_GLASS)
+        return fail(h, "pte_set_target_spin_glass: this engine's target is %d, not PTE_TARGET_SPIN_GLASS", h->cfg.target);
+    const int64_t d = h->d, L = (int64_t)std::llround(std::sqrt((double)d));
+    if (base_length != L)
+        return fail(h, "pte_set_target_spin_glass: base_length must be the engine's %lld (dim = %lld) (got %lld)", (long long)L, (long long)d, (long long)base_length);
+    if (!bonds_right || !bonds_down) return fail(h, "pte_set_target_spin_glass: null argument");
+    for (int plane = 0; plane < 2; ++plane) {
+        const int8_t *b = plane == 0 ? bonds_right : bonds_down;
+        for (int64_t s = 0; s < d; ++s)
+            if (b[s] != 1 && b[s] != -1)
+                return fail(h, "pte_set_target_spin_glass: %s[%lld] must be +1 or -1 (got %d): ±J is the supported disorder -- real-valued or diluted "
+                               "couplings break the two-threshold filter and the bit packing of the sweep", plane == 0 ? "bonds_right" : "bonds_down", (long long)s, (int)b[s]);
+    }
+    HIP_OK(h, hipSetDevice(h->cfg.device));
+    const int64_t NW = d / 32;
+    const bool packed = L % 32 == 0;
+    std::vector<unsigned char> jb((size_t)d);
+    std::vector<unsigned> jw(packed ? (size_t)(2 * NW) : 0, 0u);
+    for (int64_t s = 0; s < d; ++s) {
+        const unsigned r = bonds_right[s] < 0, dn = bonds_down[s] < 0;
+        jb[(size_t)s] = (unsigned char)((r << 1) | (dn << 2));
+        if (packed) { jw[(size_t)(s >> 5)] |= r << (s & 31); jw[(size_t)(NW + (s >> 5))] |= dn << (s & 31); }
+    }
+    if (!h->d_sg_bytes && dev_alloc(h, &h->d_sg_bytes, (size_t)d, false)) return 1;
+    if (packed && !h->d_sg_words && dev_alloc(h, &h->d_sg_words, (size_t)(2 * NW), false)) return 1;
+    HIP_OK(h, hipMemcpyAsync(h->d_sg_bytes, jb.data(), jb.size(), hipMemcpyHostToDevice, h->stream));
+    if (packed) HIP_OK(h, hipMemcpyAsync(h->d_sg_words, jw.data(), sizeof(unsigned) * jw.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    SpinGlassParams &p = h->spinglass;
+    p.L = (int)L; p.n_steps = h->cfg.slice_n_passes; p.beta_target = h->cfg.target_params[0];
+    p.jb = h->d_sg_bytes; p.jw = packed ? h->d_sg_words : nullptr;
+    spinglass_refresh_stats((unsigned)h->K, h->stream, h->dev, p);          // suff of the current states
+    HIP_OK(h, hipGetLastError());
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
 // The posterior of a finite mixture model.  Host, once per call: c_prior = -(d/2) log(2 pi / p), c_obs = -(n/2) log(2 pi); y is
 // uploaded zero-padded into one allocation sized once for the largest n.
 int pte_set_target_mixture_model(pte_engine *h, int64_t n_obs, const double *y) {
@@ -2483,7 +2547,7 @@ int pte_get_state(const pte_engine *hc, double *state, int64_t *chain, uint64_t 
     if (!family_ready(h)) return family_missing_error(h, "pte_get_state");
     HIP_OK(h, hipSetDevice(h->cfg.device));
     const int64_t N = h->K, d = h->d;
-    const bool ising = h->cfg.target == PTE_TARGET_ISING;
+    const bool ising = on_lattice(h->cfg.target);
     std::vector<uint32_t> packed;
     if (state && d > 0 && ising) {      // the Replica.state contract of the ABI stays 0.0 / 1.0 per site; the device row is bit-packed
         packed.resize((size_t)(N * h->dev.ld * 2));
@@ -2523,7 +2587,7 @@ int pte_set_state(pte_engine *h, const double *state, const int64_t *chain, cons
         h->poisoned = false;
     }
     std::vector<uint32_t> packed;
-    if (state && d > 0 && h->cfg.target == PTE_TARGET_ISING) {
+    if (state && d > 0 && on_lattice(h->cfg.target)) {
         packed.assign((size_t)(N * h->dev.ld * 2), 0u);
         for (int64_t r = 0; r < N; ++r) {
             uint32_t *w = packed.data() + (size_t)(r * h->dev.ld * 2);
@@ -2545,7 +2609,13 @@ int pte_set_state(pte_engine *h, const double *state, const int64_t *chain, cons
     }
     if (rng) HIP_OK(h, hipMemcpyAsync(h->dev.rng, rng, sizeof(uint64_t) * 2 * N, hipMemcpyHostToDevice, h->stream));
     HIP_OK(h, hipStreamSynchronize(h->stream));
-    if (state && d > 0 && h->cfg.target == PTE_TARGET_ISING) {   // sum_pair_products of every slot (examples/ising.jl:27-35)
+    if (state && d > 0 && h->cfg.target == PTE_TARGET_SPIN_GLASS) {   // the bond-weighted pair sum of every slot, once the bonds are there (k_refresh_spinglass_stats)
+        if (family_ready(h)) {
+            spinglass_refresh_stats((unsigned)N, h->stream, h->dev, h->spinglass);
+            HIP_OK(h, hipGetLastError());
+            HIP_OK(h, hipStreamSynchronize(h->stream));
+        }
+    } else if (state && d > 0 && h->cfg.target == PTE_TARGET_ISING) {   // sum_pair_products of every slot (examples/ising.jl:27-35)
         const int64_t L = (int64_t)std::llround(std::sqrt((double)d));
         std::vector<double> spp((size_t)N);
         for (int64_t r = 0; r < N; ++r) {

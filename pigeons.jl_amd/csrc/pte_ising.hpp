@@ -50,6 +50,7 @@ __device__ inline long long ising_recompute(const unsigned char *sp, int L, int 
     return acc / 2;
 }
 
+#ifndef PTE_TU_LANGEVIN          // (a non-template kernel: pte.hip holds it; the other units take this header's helpers only)
 __global__ __launch_bounds__(64) void k_explore_ising(EngineDev e, IsingParams ip) {
     extern __shared__ unsigned char spins[];
     const int lane = lane_id();
@@ -151,6 +152,8 @@ __global__ __launch_bounds__(64) void k_explore_ising(EngineDev e, IsingParams i
     record_after_explore(e, cl, c, slot, lane, lp_before, (double)spp, 0.0);
 }
 
+#endif  // PTE_TU_LANGEVIN
+
 }  // namespace pte
 
 namespace pte {
@@ -163,7 +166,7 @@ namespace pte {
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ unsigned lds_word(const unsigned *w, int i) { return (unsigned)__builtin_amdgcn_readfirstlane((int)w[i]); }
 
-#ifdef PTE_TEST_KERNELS   // scalar bit-packed sweep: dominated by k_explore_ising_spec, kept in libpte_test.so for A/B parity
+#if defined(PTE_TEST_KERNELS) && !defined(PTE_TU_LANGEVIN)   // scalar bit-packed sweep: dominated by k_explore_ising_spec, kept in libpte_test.so for A/B parity
 __global__ __launch_bounds__(64) void k_explore_ising_bits(EngineDev e, IsingParams ip) {
     extern __shared__ unsigned words[];
     const int lane = lane_id();

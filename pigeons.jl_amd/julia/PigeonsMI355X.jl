@@ -44,6 +44,7 @@ const HIER_CENTERED, HIER_NONCENTERED = Int32(0), Int32(1)
 const TARGET_LATENT_AR1 = Int32(10)
 const AR1_STOCHASTIC_VOLATILITY, AR1_NORMAL_IDENTITY = Int32(0), Int32(1)
 const TARGET_DENSE_NORMAL = Int32(11)
+const TARGET_SPIN_GLASS = Int32(12)
 const GLM_BERNOULLI_LOGIT, GLM_NORMAL_IDENTITY = Int32(0), Int32(1)
 const EXPLORER_NONE, EXPLORER_TOY, EXPLORER_SLICE, EXPLORER_AUTOMALA, EXPLORER_ISING, EXPLORER_MALA, EXPLORER_AAPS = Int32.((0, 1, 2, 3, 4, 5, 6))
 const RECORD_ROUND_TRIP, RECORD_INDEX_PROCESS, RECORD_ONLINE, RECORD_TRACES, RECORD_ENERGY_AC1, RECORD_TRACES_EXTENDED =
@@ -110,6 +111,10 @@ struct DeviceFunnel; dim::Int; end
 """The Ising model of examples/ising.jl:13-37 (`IsingLogPotential(beta, base_length)`, defined in user code there):
 PTE_TARGET_ISING, explorer = the Metropolis sweeps of examples/ising.jl:91-116 (n_sweeps passes)."""
 struct DeviceIsing; beta::Float64; base_length::Int; n_sweeps::Int; end
+"""The +-J Edwards-Anderson spin glass, the device family PTE_TARGET_SPIN_GLASS (DESIGN 4.17): examples/ising.jl with every neighbour product
+multiplied by a quenched bond.  `bonds_right[i, j]` couples site (i, j) with (i, j + 1), `bonds_down[i, j]` couples (i, j) with (i + 1, j)
+(periodic), every entry +1 or -1; explorer = the Metropolis sweeps of examples/ising.jl:91-116 (n_sweeps passes)."""
+struct DeviceSpinGlass; beta::Float64; bonds_right::Matrix{Int8}; bonds_down::Matrix{Int8}; n_sweeps::Int; end
 """A normalised mixture of K <= 8 diagonal Gaussians, the device family PTE_TARGET_GAUSSIAN_MIXTURE (DESIGN 4.8): the device form of
 `DistributionLogPotential(MixtureModel([MvNormal(means[k], Diagonal(std_devs[k] .^ 2)) for k in 1:K], weights))`.  `means` and
 `std_devs` are K x dim.  Used as `Inputs(target = on_mi355x(DeviceGaussianMixture(w, m, s)), reference = ScaledPrecisionNormalLogPotential(p, dim))`."""
@@ -169,6 +174,12 @@ function device_family(t::DeviceFunnel, inputs)
     return (TARGET_FUNNEL, t.dim, (ref.precision, 0.0, 0.0, 0.0))
 end
 device_family(t::DeviceIsing, inputs) = (TARGET_ISING, t.base_length^2, (t.beta, 0.0, 0.0, 0.0))
+function device_family(t::DeviceSpinGlass, inputs)
+    L = size(t.bonds_right, 1)
+    size(t.bonds_right) == (L, L) && size(t.bonds_down) == (L, L) && 2 <= L && L^2 <= 65536 ||
+        error("DeviceSpinGlass: bonds_right and bonds_down are L x L with 2 <= L and L^2 <= 65536")
+    return (TARGET_SPIN_GLASS, L^2, (t.beta, 0.0, 0.0, 0.0))
+end
 function device_family(t::DeviceGaussianMixture, inputs)
     K, dim = size(t.means)
     length(t.weights) == K && size(t.std_devs) == (K, dim) || error("DeviceGaussianMixture: weights [K], means and std_devs K x dim")
@@ -335,7 +346,7 @@ function Pigeons.create_replicas(inputs::Inputs{<:OnDevice}, shared::Shared, sou
                     n_chains_variational = inputs.n_chains_variational, rank = t.rank, world_size = t.world_size)
     cfg.struct_size = sizeof(PteConfig)
     ex = shared.explorer
-    if t.target isa DeviceIsing
+    if t.target isa DeviceIsing || t.target isa DeviceSpinGlass
         cfg.explorer = EXPLORER_ISING; cfg.slice_n_passes = t.target.n_sweeps
     elseif ex isa Compose
         cfg.explorer = set_explorer!(cfg, ex.first, 1); cfg.explorer2 = set_explorer!(cfg, ex.second, 2)
@@ -387,6 +398,11 @@ function Pigeons.create_replicas(inputs::Inputs{<:OnDevice}, shared::Shared, sou
         g = t.target
         Q = Matrix{Float64}(permutedims(g.precision))     # row-major for the C ABI (the matrix is symmetric: the same bits)
         check(r, ccall((:pte_set_target_dense, libpte), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}), r.handle, length(g.mean), g.mean, Q))
+    end
+    if t.target isa DeviceSpinGlass                 # the bond planes as pte_set_target_spin_glass reads them
+        g = t.target
+        R = Matrix{Int8}(permutedims(g.bonds_right)); D = Matrix{Int8}(permutedims(g.bonds_down))     # row-major for the C ABI
+        check(r, ccall((:pte_set_target_spin_glass, libpte), Cint, (Ptr{Cvoid}, Int64, Ptr{Int8}, Ptr{Int8}), r.handle, size(R, 1), R, D))
     end
     if t.target isa DevicePoissonChangePoint        # the counts as pte_set_target_changepoint reads them
         check(r, ccall((:pte_set_target_changepoint, libpte), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), r.handle, t.target.y, length(t.target.y)))

@@ -146,6 +146,15 @@ class Engine:
             raise ValueError("set_target_dense: precision must be dim x dim with dim = len(mean) = %d (got shape %s)" % (ma.size, qa.shape))
         self._chk(self.L.pte_set_target_dense(self.h, ma.size, _dp(ma), _dp(qa)))
 
+    def set_target_spin_glass(self, bonds_right, bonds_down):
+        """pte_set_target_spin_glass: the two bond planes [L][L] (row-major, every entry +1 or -1), L^2 = dim"""
+        r = np.ascontiguousarray(bonds_right, dtype=np.int8)
+        dn = np.ascontiguousarray(bonds_down, dtype=np.int8)
+        if r.ndim != 2 or r.shape[0] != r.shape[1] or dn.shape != r.shape:
+            raise ValueError("set_target_spin_glass: bonds_right and bonds_down must be L x L (got shapes %s and %s)" % (r.shape, dn.shape))
+        i8 = C.POINTER(C.c_int8)
+        self._chk(self.L.pte_set_target_spin_glass(self.h, r.shape[0], r.ctypes.data_as(i8), dn.ctypes.data_as(i8)))
+
     # --- hot path
     def explore(self, scan):
         self._chk(self.L.pte_explore(self.h, scan))

@@ -496,6 +496,54 @@ class IsingLogPotential:
     base_length: int = 5
 
 
+class SpinGlassLogPotential:
+    """The +-J Edwards-Anderson spin glass on the L x L periodic lattice: p(state) ∝ exp(beta * S), S = sum_ij s_ij (bonds_right_ij s_i,j+1 +
+    bonds_down_ij s_i+1,j) -- IsingLogPotential with every neighbour product multiplied by a quenched bond in {+1, -1} (at L = 2 the two bonds
+    between the same pair of sites are distinct terms).  The reference is beta = 0; states are 0/1 vectors in row-major order, explored by
+    IsingMetropolis.  Bonds are +-1 only: real-valued or diluted couplings are not available on the device."""
+
+    def __init__(self, beta, bonds_right, bonds_down):
+        planes = []
+        for name, b in (("bonds_right", bonds_right), ("bonds_down", bonds_down)):
+            a = np.asarray(b)
+            if a.ndim != 2 or a.shape[0] != a.shape[1] or a.shape[0] < 2:
+                raise ValueError("SpinGlassLogPotential: %s must be L x L with L >= 2 (got shape %s)" % (name, a.shape))
+            if a.size > 65536:
+                raise ValueError("SpinGlassLogPotential: the device holds lattices of at most 65536 sites (got %s = %d x %d)" % (name, a.shape[0], a.shape[1]))
+            planes.append(a)
+        if planes[0].shape != planes[1].shape:
+            raise ValueError("SpinGlassLogPotential: bonds_right and bonds_down must have the same shape (got %s and %s)" % (planes[0].shape, planes[1].shape))
+        for name, a in zip(("bonds_right", "bonds_down"), planes):
+            bad = np.argwhere(~((a == 1) | (a == -1)))
+            if len(bad):
+                i, j = (int(v) for v in bad[0])
+                raise ValueError("SpinGlassLogPotential: %s[%d][%d] must be +1 or -1 (got %r): ±J is the supported disorder, "
+                                 "real-valued or diluted couplings are out of scope" % (name, i, j, a[i, j].item()))
+        self.beta = float(beta)
+        self.bonds_right = np.ascontiguousarray(planes[0], dtype=np.int8)
+        self.bonds_down = np.ascontiguousarray(planes[1], dtype=np.int8)
+
+    @classmethod
+    def edwards_anderson(cls, beta, base_length, seed=1):
+        """both planes drawn +-1 with probability 1/2 each from np.random.default_rng(seed): bonds_right first, then bonds_down"""
+        rng = np.random.default_rng(seed)
+        L = int(base_length)
+        right = (2 * rng.integers(0, 2, size=(L, L)) - 1).astype(np.int8)
+        down = (2 * rng.integers(0, 2, size=(L, L)) - 1).astype(np.int8)
+        return cls(beta, right, down)
+
+    @property
+    def base_length(self):
+        return int(self.bonds_right.shape[0])
+
+    @property
+    def dim(self):
+        return self.base_length ** 2
+
+    def __repr__(self):
+        return "SpinGlassLogPotential(beta=%r, base_length=%d)" % (self.beta, self.base_length)
+
+
 @dataclass
 class IsingMetropolis:
     """examples/ising.jl:91-93"""
@@ -583,7 +631,7 @@ def default_explorer(target):
         return ToyExplorer()           # src/targets/toy_mvn_target.jl:13
     if isinstance(target, TestSwapper):
         return None                    # src/swap/pair_swapper.jl:139
-    if isinstance(target, IsingLogPotential):
+    if isinstance(target, (IsingLogPotential, SpinGlassLogPotential)):
         return IsingMetropolis()       # examples/ising.jl:94
     return SliceSampler()              # src/targets/target.jl:20
 
@@ -769,6 +817,10 @@ class PT:
             kw.update(target=_lib.TARGET_TEST_SWAPPER, dim=1, target_params=[target.constant_swap_accept_pr])
         elif isinstance(target, IsingLogPotential):
             kw.update(target=_lib.TARGET_ISING, dim=target.base_length ** 2, target_params=[target.beta])
+        elif isinstance(target, SpinGlassLogPotential):
+            if not isinstance(explorer, IsingMetropolis):
+                raise NotImplementedError("the device spin-glass path is explored by IsingMetropolis only (got %r)" % (explorer,))
+            kw.update(target=_lib.TARGET_SPIN_GLASS, dim=target.dim, target_params=[target.beta])
         elif isinstance(target, Funnel):
             ref = inputs.reference
             if not isinstance(ref, ScaledPrecisionNormalLogPotential) or ref.dim != target.dim:
@@ -896,6 +948,9 @@ class PT:
         if isinstance(target, DenseNormal):              # every engine (rank) holds the data
             for eng in (self.shards.engines if hasattr(self.shards, "engines") else [self.replicas]):
                 eng.set_target_dense(target.mean, target.precision)
+        if isinstance(target, SpinGlassLogPotential):    # every engine (rank) holds the bonds
+            for eng in (self.shards.engines if hasattr(self.shards, "engines") else [self.replicas]):
+                eng.set_target_spin_glass(target.bonds_right, target.bonds_down)
         if isinstance(target, SpikeSlabRegression):      # every engine (rank) holds the data
             for eng in (self.shards.engines if hasattr(self.shards, "engines") else [self.replicas]):
                 eng.set_target_varsel(target.likelihood_code, target.X, target.y, target.noise_sd, target.inclusion_prob)

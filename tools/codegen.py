@@ -45,12 +45,13 @@ def _key(g, src, unit_flags, extra):
     return h.hexdigest()[:16]
 
 
-def compile_units(extra=(), force=False):
-    """-> [(source, command, path of the .s, text of the resource remarks)] for the product's translation units, compiled in parallel, cached"""
+def compile_units(extra=(), force=False, units=None):
+    """-> [(source, command, path of the .s, text of the resource remarks)] for the product's translation units (units = None: __graft_entry__.UNITS,
+    the eight whose code tests/test_codegen_frozen.py freezes; or a list such as __graft_entry__.LATTICE_UNITS), compiled in parallel, cached"""
     g = _graft()
     os.makedirs(CACHE, exist_ok=True)
     jobs = []
-    for src, unit_flags in g.UNITS:
+    for src, unit_flags in (g.UNITS if units is None else units):
         key = _key(g, src, unit_flags, extra)
         stem = os.path.join(CACHE, "%s.%s" % (os.path.splitext(src)[0], key))
         cmd = [g.HIPCC, *[f for f in g.FLAGS if f != "-fPIC"], *unit_flags, *extra, "--cuda-device-only", "-S",
@@ -69,7 +70,7 @@ def compile_units(extra=(), force=False):
     with ThreadPoolExecutor(len(jobs)) as ex:
         out = list(ex.map(run, jobs))
     # prune: an assembly file is 15-40 MB (and build/ travels with every gpurun snapshot); keep what this call produced, nothing else
-    keep = set(os.path.basename(stem) for _, _, stem in jobs)
+    keep = set("%s.%s" % (os.path.splitext(src)[0], _key(g, src, unit_flags, extra)) for src, unit_flags in list(g.UNITS) + list(g.LATTICE_UNITS))
     for f in os.listdir(CACHE):
         full = os.path.join(CACHE, f)
         if not extra and f.rsplit(".", 1)[0] not in keep:
