@@ -536,7 +536,7 @@ struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>
     // the latent-AR(1) posterior: x = [mu, a, ls, h_0 .. h_{T-1}], phi = tanh(a), sigma = exp(ls), LIK = AR1_STOCHASTIC_VOLATILITY
     // (y_t ~ N(0, exp(h_t))) or AR1_NORMAL_IDENTITY (y_t ~ N(h_t, obs_sd^2)).  The density is one sum over the fixed tree with the leaves in
     // state order: leaves 0..2 the priors of mu, a and sigma (with the Jacobian of ls), leaf 3 + t = the transition term of h_t + its
-    // observation term.  phi, om = 1 - phi^2, sqrt(om), log(om), isg = exp(-ls) and r = (sigma / sigma_scale)^2 are computed once, on the values
+    // observation term.  phi, om = 1 - phi^2 = sech^2(a), sqrt(om), log(om), 1 - phi, isg = exp(-ls) and r = (sigma / sigma_scale)^2 are computed once, on the values
     // lanes 0..2 of block 0 hold.  The predecessor's h - mu comes from the lane below (lane 0: lane 63 of the block before); coordinate 3 = h_0
     // has the stationary law and reads no neighbour.  GRAD: the h components are elementwise given the successor's residual, which comes from
     // the lane above (lane 63: lane 0 of the block after); those of mu, a and ls are three more sums over the same tree, in lockstep with the
@@ -556,11 +556,15 @@ struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>
         const Ar1Params &ar = this->ar;
         const double LOG2PI = 1.8378770664093453;
         const double mu = readlane_f64(x[0], 0), a = readlane_f64(x[0], 1), ls = readlane_f64(x[0], 2);
+        // om = sech^2(a), its root and its log, and 1 - phi, from e = exp(-2 |a|): 1 - tanh^2 cancels (1e-8 relative at |a| = 10, 0 from 19.07)
+        const double LOG2 = 0.6931471805599453;
         const double phi = tanh(a);
-        const double om = 1.0 - phi * phi, sqom = sqrt(om), lom = log(om);
+        const double ta = fabs(a), e2 = exp(-2.0 * ta), q2 = 1.0 + e2;
+        const double sqom = (2.0 * exp(-ta)) / q2, om = sqom * sqom, lom = 2.0 * ((LOG2 - ta) - log1p(e2));
+        const double omp = a > 0.0 ? (2.0 * e2) / q2 : 2.0 / q2;        // 1 - phi
         const double isg = exp(-ls), sg = exp(ls);
         const double ts = sg * ar.iss, r = ts * ts;
-        const double c0 = isg * sqom, pis = phi * isg, cm = (1.0 - phi) * isg, ca = isg * om;
+        const double c0 = isg * sqom, pis = phi * isg, cm = omp * isg, ca = isg * om;
         constexpr int K = 2 + (GRAD ? 3 : 0) + (WITH_Q ? 1 : 0), KM = 2, KA = 3, KL = 4, KQ = GRAD ? 5 : 2;
         double t[K][E], out[K];
         double hm[E], u[E], ut[E], obd[E];

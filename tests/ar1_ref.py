@@ -6,7 +6,8 @@ sigma = exp(ls), om = 1 - phi^2; mu ~ N(0, mu_sd^2), a ~ N(phi_loc, phi_scale^2)
 (stochastic volatility) or y_t ~ N(h_t, obs_sd^2) (normal).  The state is x = [mu, a, ls, h_0 .. h_{T-1}], d = T + 3.  The density is
 normalised in x (it includes the Jacobian of ls) and is ONE sum over the fixed tree of DESIGN 3 with the leaves in state order; the gradients
 of mu, a and ls are three more sums over the same tree.  The operations and their order are the kernels' (no fused multiply-adds); tanh / exp /
-log / log1p are libm's, the device's differ by an ulp."""
+log / log1p are libm's, the device's differ by an ulp.  om, its root, its log and 1 - phi come from exp(-2 |a|), as in the kernel: 1 - tanh(a)^2
+cancels (tests/test_family_edges_cpu.py holds these leaves to a 60-digit evaluation of the model up to |a| = 25)."""
 import math
 
 import numpy as np
@@ -14,6 +15,7 @@ import numpy as np
 from mixture_ref import tree_sum
 
 LOG2PI = 1.8378770664093453
+LOG2 = 0.6931471805599453
 STOCHASTIC_VOLATILITY, NORMAL_IDENTITY = 0, 1
 
 
@@ -42,12 +44,17 @@ class Ar1:
         with np.errstate(all="ignore"):
             mu, a, ls = np.float64(x[0]), np.float64(x[1]), np.float64(x[2])
             phi = np.tanh(a)
-            om = 1.0 - phi * phi
-            sqom, lom = np.sqrt(om), np.log(om)
+            ta = np.abs(a)                                               # om = sech^2(a) and 1 - phi from exp(-2 |a|): 1 - tanh^2 cancels
+            e2 = np.exp(-2.0 * ta)
+            q2 = 1.0 + e2
+            sqom = (2.0 * np.exp(-ta)) / q2
+            om = sqom * sqom
+            lom = 2.0 * ((LOG2 - ta) - np.log1p(e2))
+            omp = (2.0 * e2) / q2 if a > 0.0 else 2.0 / q2               # 1 - phi
             isg, sg = np.exp(-ls), np.exp(ls)
             ts = sg * self.iss
             r = ts * ts
-            c0, pis, cm, ca = isg * sqom, phi * isg, (1.0 - phi) * isg, isg * om
+            c0, pis, cm, ca = isg * sqom, phi * isg, omp * isg, isg * om
             h = x[3:]
             first = np.arange(self.T) == 0
             hm = h - mu
