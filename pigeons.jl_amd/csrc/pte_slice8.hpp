@@ -157,6 +157,8 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
     // comparing what it returns.
     typedef unsigned mask2_t __attribute__((ext_vector_type(2)));       // a lane mask as the register pair it is: a bit test of its low dword reads the register
     typedef unsigned slow_mask_t __attribute__((ext_vector_type(WIN / 32)));
+    typedef double draws8_t __attribute__((ext_vector_type(8)));        // the shrinkage draws of a hypothesis as the register tuples they are read into (round 9)
+    typedef double draws2_t __attribute__((ext_vector_type(2)));
     slow_mask_t slow_w;
     auto fill_window = [&]() __attribute__((always_inline)) {
         __syncthreads();                               // one wave per block: orders the LDS accesses
@@ -225,9 +227,14 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                 double Vd[S8_BD];
 #pragma unroll
                 for (int it = 0; it < S8_BD; ++it) Vd[it] = s_u[idx0 + 2 + it];
+                // Round 9 (DBL_MODE 2): the LDS byte address of s_u[idx0], which the head's reads use anyway.  The doubling steps advance it
+                // by 8 per step, so that it names the shrinkage draws the moment the doubling block ends (see there).
+                int ua = 0;
+                if constexpr (DBL_MODE == 2) ua = (int)(uintptr_t)(const __attribute__((address_space(3))) double *)&s_u[idx0];
                 int ex0 = 0;
                 int cnt_base = 2;                            // draws of the head: E and u0 (+ lane 0's extra draws of a slow-path exponential)
                 asm volatile("" : "+v"(cnt_base));    // (set here, ahead of the test: otherwise in a block of their own on the likely path)
+                if constexpr (DBL_MODE == 2) asm volatile("" : "+s"(ex0));
                 // bit p of the window's slow-path mask: dword p >> 5 of the register tuple, selected through M0 (one wait state between the
                 // scalar write of M0 and s_movrels), shifted by p (a scalar shift looks at the low five bits of its count)
                 unsigned slow_b;
@@ -246,7 +253,7 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                     const int used = (int)((rs.seed - (wseed + (uint64_t)p * gamma)) * gamma_inv);
                     if (used <= 17) {
                         ex0 = used - 1;
-                        if (lane == 0) { E = Ex; idx0 += ex0; cnt_base = 2 + ex0; }
+                        if (lane == 0) { E = Ex; idx0 += ex0; cnt_base = 2 + ex0; ua += 8 * ex0; }
                         Sest += Ex * inv_abs_nhp;            // not among the window's fast-path exponentials summed into Sest
                         ex_total += ex0;
                         u0 = s_u[idx0 + 1];
@@ -282,6 +289,11 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                 double dmin_lr = 0.0;                    // min(dL, dR) after the budgeted steps (DBL_MODE 2: left by the hand-written block)
                 unsigned need_l0 = 0u;                   // (its low dword, as the statement left it: the bit test then reads the register itself)
                 uint64_t need_m = 0ull;                  // DBL_MODE 2: "still needs doubling" (dmin_lr < 0) as a lane mask, ONE compare at the end of the block
+                // what the shrinkage block and the validity test take over; DBL_MODE 2 computes them at the end of the doubling block (round 9)
+                double thr2 = 0.0, mthr = 0.0, W = 0.0;
+                int n = 0;
+                uint64_t act_m = 0ull;                   // DBL_MODE 2: `active` as a lane mask
+                draws8_t ud8 = 0.0; draws2_t ud2 = 0.0;  // DBL_MODE 2: the shrinkage draws u[0..7], u[8..], in the registers the LDS reads return them into
 #if PTE_S8_BD >= 1 && PTE_S8_BD <= 4 && !defined(PTE_S8_DOUBLING_SELECTS)
                 if constexpr (DBL_MODE == 2) {           // (the launcher picks this instantiation only for sp.p >= S8_BD: no second body in the loop)
                     // Round 4, the one-wave-per-SIMD kernel: a hypothesis that needs no (further) doubling drops out of EXEC by v_cmpx --
@@ -304,6 +316,23 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                     // stand between the VALU write of VCC and its use as a lane mask (a v_cmp under the EXEC of the step before: a lane
                     // that dropped out does not read it).  Fixed registers because the selects address register halves; LL / RR / dmin / Q
                     // sit where the shrinkage block below wants Lbar / Rbar / dmin / Q.
+                    //
+                    // Round 9, the seam to the shrinkage block.  A lone wave used to stand still here twice: for the scalar bit test on the
+                    // block's last compare (~30 cycles from a VALU write of an SGPR to its scalar read, with nothing between them) and then,
+                    // behind the branch, for the LDS round trip of the nine shrinkage draws (88-124 cycles, profiles/r03_lds_latency.txt),
+                    // which hipcc issued BEHIND the instructions meant for its shadow.  Now
+                    //   - every step advances `ua`, the byte address of the hypothesis' draws, by 8 next to kd (under EXEC, like kd), so the
+                    //     address of u[0 .. S8_BS-1] = s_u[idx0 + 2 + kd ...] is ready the moment EXEC is whole again (a masked lane would
+                    //     not load), and the draws are requested THERE, ahead of the compare, its test and the branch;
+                    //   - the last step's two folds into dmin run behind the compare, under the whole EXEC: for a lane the step did not
+                    //     take, dL and dR are the values of its last step (or the head's), folded in there already, and min is idempotent;
+                    //   - behind them comes everything of the round that does not depend on lane 0's out-of-line doubling -- Bq and the margin
+                    //     mthr, thr2 (one v_max_f64 with |.| modifiers: no canonicalising copies), "is this coordinate in the block", the
+                    //     draw count kn0 straight into the shrinkage block's counter, the width the first shrinkage step starts from --
+                    //     so the scalar side reads the compare's mask nine VALU instructions after it was written.
+                    // The compiler does not know that v124-v141 are pending: they are outputs of this statement and inputs of the shrinkage
+                    // block's (pinned in both), nothing between the two names them on the likely path (tests/test_codegen_slice8_seam.py
+                    // holds the generated code to that), and the shrinkage block waits for them itself, read by read.
                     double t_, wd_;
                     int sLh_, sRh_;
                     uint64_t sv_, sx_;
@@ -314,35 +343,65 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                     "v_cmpx_gt_f64_e64 %[sx], 0, v[102:103]\n" \
                     "v_add_f64 v[112:113], v[98:99], -v[96:97]\n" \
                     "v_add_u32 %[kd], 1, %[kd]\n" \
+                    "v_add_u32 %[ua], 8, %[ua]\n" \
                     "v_cndmask_b32 v119, 0, %[one], vcc\n" \
                     "v_cndmask_b32 v121, %[one], v118, vcc\n" \
                     "v_fma_f64 v[96:97], -v[118:119], v[112:113], v[96:97]\n" \
                     "v_fma_f64 v[98:99], v[120:121], v[112:113], v[98:99]\n" \
                     "v_fma_f64 v[114:115], v[96:97], v[96:97], -v[110:111]\n" \
-                    "v_fma_f64 v[116:117], v[98:99], v[98:99], -v[110:111]\n" \
+                    "v_fma_f64 v[116:117], v[98:99], v[98:99], -v[110:111]\n"
+#define PTE_S8_CFOLD \
                     "v_min_f64 v[104:105], v[104:105], |v[114:115]|\n" \
                     "v_min_f64 v[104:105], v[104:105], |v[116:117]|\n"
+                    // u[k] -> v[124 + 2 k : 125 + 2 k]; sm.u[idx0 + 2 + kd + k] is 8 (2 + k) bytes behind `ua`
+#if PTE_S8_BS == 6
+#define PTE_S8_UREADS_TAIL
+#elif PTE_S8_BS == 7
+#define PTE_S8_UREADS_TAIL "ds_read_b64 v[136:137], %[ua] offset:64\n"
+#elif PTE_S8_BS == 8
+#define PTE_S8_UREADS_TAIL "ds_read2_b64 v[136:139], %[ua] offset0:8 offset1:9\n"
+#elif PTE_S8_BS == 9
+#define PTE_S8_UREADS_TAIL "ds_read2_b64 v[136:139], %[ua] offset0:8 offset1:9\n" "ds_read_b64 v[140:141], %[ua] offset:80\n"
+#else
+#define PTE_S8_UREADS_TAIL "ds_read2_b64 v[136:139], %[ua] offset0:8 offset1:9\n" "ds_read2_b64 v[140:143], %[ua] offset0:10 offset1:11\n"
+#endif
                     asm volatile("s_mov_b64 %[sv], exec\n"
-                                 PTE_S8_CSTEP("%[V0]")
 #if PTE_S8_BD >= 2
-                                 PTE_S8_CSTEP("%[V1]")
+                                 PTE_S8_CSTEP("%[V0]") PTE_S8_CFOLD
 #endif
 #if PTE_S8_BD >= 3
-                                 PTE_S8_CSTEP("%[V2]")
+                                 PTE_S8_CSTEP("%[V1]") PTE_S8_CFOLD
 #endif
 #if PTE_S8_BD >= 4
-                                 PTE_S8_CSTEP("%[V3]")
+                                 PTE_S8_CSTEP("%[V2]") PTE_S8_CFOLD
 #endif
+                                 PTE_S8_CSTEP("%[VL]")                                  // (the last step: its folds stand behind the compare)
                                  "s_mov_b64 exec, %[sv]\n"
+                                 "ds_read2_b64 v[124:127], %[ua] offset0:2 offset1:3\n"
+                                 "ds_read2_b64 v[128:131], %[ua] offset0:4 offset1:5\n"
+                                 "ds_read2_b64 v[132:135], %[ua] offset0:6 offset1:7\n"
+                                 PTE_S8_UREADS_TAIL
                                  "v_min_f64 v[102:103], v[114:115], v[116:117]\n"      // (all lanes: what "still needs doubling" is decided on ...
                                  "v_cmp_gt_f64_e64 %[sd], 0, v[102:103]\n"             //  ... here, ONCE: bit 0 sends lane 0 on, the complement is `dbl_ok` of every lane)
-                                 : "+{v[96:97]}"(LL), "+{v[98:99]}"(RR), "+{v[114:115]}"(dL), "+{v[116:117]}"(dR), "+{v[104:105]}"(dmin), [kd] "+v"(kd),
-                                   "=&{v[102:103]}"(t_), "=&{v[112:113]}"(wd_), "=&{v119}"(sLh_), "=&{v121}"(sRh_), [sv] "=&s"(sv_), [sx] "=&s"(sx_), [sd] "=&s"(sd_)
+                                 PTE_S8_CFOLD
+                                 "v_add_f64 %[mthr], %[Sest], |v[110:111]|\n"          // Bq = Sest + |Q|
+                                 "v_max_f64 %[thr], |v[96:97]|, |v[98:99]|\n"
+                                 "v_cmp_gt_i32_e64 %[act], %[nl], %[lg]\n"             // active: l + hg < nl
+                                 "v_add3_u32 v106, %[cb], %[so], %[kd]\n"              // kn0
+                                 "v_mul_f64 %[mthr], %[mthr], %[c_m]\n"
+                                 "v_mul_f64 %[thr], %[thr], %[c_t]\n"
+                                 "v_add_f64 v[112:113], v[98:99], -v[96:97]\n"         // W of the first shrinkage step
+                                 : "+{v[96:97]}"(LL), "+{v[98:99]}"(RR), "+{v[114:115]}"(dL), "+{v[116:117]}"(dR), "+{v[104:105]}"(dmin), [kd] "+v"(kd), [ua] "+v"(ua),
+                                   "=&{v[102:103]}"(t_), "=&{v[112:113]}"(wd_), "=&{v119}"(sLh_), "=&{v121}"(sRh_), [sv] "=&s"(sv_), [sx] "=&s"(sx_), [sd] "=&s"(sd_),
+                                   "=&{v[124:139]}"(ud8), "=&{v[140:143]}"(ud2), [mthr] "=&v"(mthr), [thr] "=&v"(thr2), "=&{v106}"(n), [act] "=&s"(act_m)
                                  : "{v[110:111]}"(Q), "{v118}"(dbl_z0), "{v120}"(dbl_z1), [one] "v"(dbl_one_hi),
-                                   [V0] "v"(Vd[0]), [V1] "v"(Vd[S8_BD > 1 ? 1 : 0]), [V2] "v"(Vd[S8_BD > 2 ? 2 : 0]), [V3] "v"(Vd[S8_BD > 3 ? 3 : 0])
+                                   [V0] "v"(Vd[0]), [V1] "v"(Vd[S8_BD > 2 ? 1 : 0]), [V2] "v"(Vd[S8_BD > 3 ? 2 : 0]), [VL] "v"(Vd[S8_BD - 1]),
+                                   [Sest] "v"(Sest), [nl] "s"(nl), [lg] "v"(l + hg), [cb] "v"(cnt_base), [so] "v"(succ_off), [c_m] "s"(2e-12), [c_t] "s"(1e-6)
                                  : "vcc", "scc");
 #undef PTE_S8_CSTEP
-                    dmin_lr = t_;
+#undef PTE_S8_CFOLD
+#undef PTE_S8_UREADS_TAIL
+                    dmin_lr = t_; W = wd_;
                     need_m = (uint64_t)sd_.x | ((uint64_t)sd_.y << 32); need_l0 = __builtin_amdgcn_readfirstlane(sd_.x);
                 } else
                 if (DBL_MODE == 1 && sp.p >= S8_BD) {    // (uniform; compile-time per kernel)
@@ -454,37 +513,52 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                         dmin_lr = (kd >= sp.p) ? 0.0 : dmin_lr;                   // (the reference's own limit p ended it: not a budget)
                         need_m = ballot64(dmin_lr < 0.0);                         // (the other lanes' bits come out as they were)
                         need_l0 = (unsigned)need_m;
+                        // Lane 0's interval, step count and draws have moved: what the end of the doubling block derived from them, again
+                        // (for the other lanes the same values as there).  The reads the doubling block requested into v124-v141 may still
+                        // be in flight when this path is entered: LDS returns in order, so the lgkmcnt(0) hipcc places in front of the
+                        // first use of THIS path's own reads -- the loop's V above -- retires them as well, before anything here names
+                        // those registers.
+                        thr2 = 1e-6 * fmax(fabs(LL), fabs(RR));
+                        n = cnt_base + kd + succ_off;
+                        W = RR - LL;
+                        const double *un = &s_u[idx0 + 2 + kd];
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) ud8[k] = (k < S8_BS) ? un[k] : 0.0;
+#pragma unroll
+                        for (int k = 8; k < 10; ++k) ud2[k - 8] = (k < S8_BS) ? un[k] : 0.0;
+                        // (a use on THIS path: hipcc then waits for these reads here and not at the head of the shrinkage block, where its
+                        // lgkmcnt(0) would stand on the likely path too, in front of the staged waits)
+                        asm volatile("" : "+{v[124:139]}"(ud8), "+{v[140:143]}"(ud2));
                     }
                 }
                 // ended by itself, not by a budget.  FAST (S8_BD < p <= 20): a speculative lane has kd <= S8_BD < p, and lane 0 leaves
                 // the loop above either satisfied or at kd = p, so "still needs doubling" alone decides
                 const bool dbl_ok = FAST ? !__builtin_amdgcn_inverse_ballot_w64(need_m) : !((kd < sp.p) && (dmin_lr < 0.0));
-                double thr2 = 1e-6 * fmax(fabs(LL), fabs(RR));
-                if constexpr (DBL_MODE == 2) asm volatile("" : "+v"(thr2));       // (taken here: LL / RR then live on only as the shrinkage block's bracket, in place)
+                if constexpr (DBL_MODE != 2) thr2 = 1e-6 * fmax(fabs(LL), fabs(RR));   // (DBL_MODE 2: taken at the end of the doubling block)
 #ifdef PTE_PROFILE_SECTIONS
                 asm volatile("" :: "v"(LL), "v"(RR), "v"(kd), "v"(thr2));
 #endif
                 PROF_T(t1); PROF_ADD(0, t1 - t0);
                 // ---- shrinkage (:141-190) up to the first proposal inside the slice: S8_BS predicated steps,
                 //      their draws loaded up front (consecutive stream positions of this hypothesis)
+                //      (DBL_MODE 2: requested at the end of the doubling block, see there; lane 0's out-of-line doubling has re-read its own)
+                static_assert(DBL_MODE != 2 || HAND_SHRINK, "PTE_S8_DBL_MODE == 2 hands its draws to the hand-written shrinkage block: 6 <= PTE_S8_BS <= 10");
                 const double *us = &s_u[idx0 + 2 + kd];
                 double u[S8_BS];
+                if constexpr (DBL_MODE != 2) {
 #pragma unroll
-                for (int k = 0; k < S8_BS; ++k) u[k] = us[k];
+                    for (int k = 0; k < S8_BS; ++k) u[k] = us[k];
+                }
                 // In the shadow of that LDS round trip (a lone wave has nothing else to put there): everything the validity test and the
                 // chase word need that does not depend on the shrinkage -- the margin, the draws consumed so far relative to the
                 // successor's window, "is this coordinate in the block", "did the doubling end by itself" as lane masks
-                double mthr = 2e-12 * Bq;
+                if constexpr (DBL_MODE != 2) mthr = 2e-12 * Bq;
                 int kn0 = cnt_base + kd + succ_off;          // + n: offset of the successor in the next level's window
                 uint64_t pre_ok;
-                if constexpr (FAST) pre_ok = ballot64(active) & ~need_m;          // (the block's compare serves both: `dbl_ok` is not taken a second time)
+                if constexpr (FAST) pre_ok = 0ull;                                // (act_m & ~need_m, taken by the shrinkage statement: the block's compare serves both, `dbl_ok` is not taken a second time)
                 else pre_ok = ballot64(active && dbl_ok);
-                double Lbar = LL, Rbar = RR, xf = xold, W = 0.0;
-                int n = N_IS_KN ? kn0 : 0;                   // proposals made (+ kn0 where the hand-written tail takes the sum as it stands)
-                if constexpr (FAST) {
-                    if constexpr (N_IS_KN) asm volatile("" : "+v"(mthr), "+v"(n), "+s"(pre_ok));
-                    else asm volatile("" : "+v"(mthr), "+v"(kn0), "+s"(pre_ok));
-                }
+                double Lbar = LL, Rbar = RR, xf = xold;
+                if constexpr (!N_IS_KN) n = 0;               // proposals made (N_IS_KN: + kn0, as the doubling block left it: the hand-written tail takes the sum as it stands)
                 bool fin = false;
                 unsigned unf_l0 = 0u;                        // (its low dword, as the block left it)
                 uint64_t unf_m = 0ull;                       // `!fin` as a lane mask -- the EXEC the block ends with -- for the test below and the hand-written tail (hipcc moves a mask through v_cndmask + v_cmp otherwise)
@@ -496,8 +570,10 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                     double t_;
                     mask2_t unf_mask;
                     uint64_t exec_save;
-#define PTE_S8_STEP(U) \
-                    "v_add_f64 v[112:113], v[98:99], -v[96:97]\n" \
+#define PTE_S8_STEP_W \
+                    "v_add_f64 v[112:113], v[98:99], -v[96:97]\n"
+#define PTE_S8_STEP(U) PTE_S8_STEP_W PTE_S8_STEP_U(U)
+#define PTE_S8_STEP_U(U) \
                     "v_mul_f64 v[102:103], " U ", v[112:113]\n" \
                     "v_add_f64 v[100:101], v[96:97], v[102:103]\n" \
                     "v_cmp_lt_f64 vcc, v[100:101], v[108:109]\n" \
@@ -509,6 +585,65 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                     "v_cndmask_b32 v99, v101, v99, vcc\n" \
                     "v_min_f64 v[104:105], v[104:105], |v[102:103]|\n" \
                     "v_cmpx_ngt_f64 vcc, 0, v[102:103]\n"
+                    if constexpr (DBL_MODE == 2) {
+                    // Round 9: the draws were requested at the end of the doubling block, which has also taken the first step's width.
+                    // LDS returns in order and nothing else on the likely path of the round counts on lgkmcnt (no scalar-memory load, no
+                    // message: tests/test_codegen_slice8_seam.py), so read i of n has landed once lgkmcnt <= n - 1 - i: every odd step
+                    // waits for the pair it starts, behind its v_add_f64.  (After lane 0's out-of-line doubling fewer reads are
+                    // outstanding, hipcc's own, and the same counts hold a fortiori.)  PTE_S8_ONE_WAIT: the A/B build with one wait for all.
+#if defined(PTE_S8_ONE_WAIT) || defined(PTE_PROFILE_SECTIONS)          // (the section timers read s_memtime: out-of-order returns on the same counter)
+#define PTE_S8_WAIT(K) "s_waitcnt lgkmcnt(0)\n"
+#else
+#define PTE_S8_WAIT(K) "s_waitcnt lgkmcnt(" #K ")\n"
+#endif
+#if PTE_S8_BS >= 9
+#define PTE_S8_W1 4
+#define PTE_S8_W3 3
+#define PTE_S8_W5 2
+#define PTE_S8_W7 1
+#elif PTE_S8_BS >= 7
+#define PTE_S8_W1 3
+#define PTE_S8_W3 2
+#define PTE_S8_W5 1
+#define PTE_S8_W7 0
+#else
+#define PTE_S8_W1 2
+#define PTE_S8_W3 1
+#define PTE_S8_W5 0
+#endif
+#define PTE_S8_WAIT_(K) PTE_S8_WAIT(K)
+                    asm volatile(".p2align 3\n"           // hand-written stream at an 8-byte phase (MI355X_MICROARCH.md: the 4 mod 8 phase costs ~1 % here)
+                                 "s_mov_b64 %[sv], exec\n"
+                                 "s_andn2_b64 %[pre], %[act], %[need]\n"               // in the block, doubling ended by itself
+                                 PTE_S8_WAIT_(PTE_S8_W1) PTE_S8_STEP_U("v[124:125]") PTE_S8_STEP("v[126:127]")
+                                 PTE_S8_STEP_W PTE_S8_WAIT_(PTE_S8_W3) PTE_S8_STEP_U("v[128:129]") PTE_S8_STEP("v[130:131]")
+                                 PTE_S8_STEP_W PTE_S8_WAIT_(PTE_S8_W5) PTE_S8_STEP_U("v[132:133]") PTE_S8_STEP("v[134:135]")
+#if PTE_S8_BS >= 7
+                                 PTE_S8_STEP_W PTE_S8_WAIT_(PTE_S8_W7) PTE_S8_STEP_U("v[136:137]")
+#endif
+#if PTE_S8_BS >= 8
+                                 PTE_S8_STEP("v[138:139]")
+#endif
+#if PTE_S8_BS >= 9
+                                 PTE_S8_STEP_W PTE_S8_WAIT_(0) PTE_S8_STEP_U("v[140:141]")
+#endif
+#if PTE_S8_BS >= 10
+                                 PTE_S8_STEP("v[142:143]")
+#endif
+                                 "s_mov_b64 %[unf], exec\n"
+                                 "s_mov_b64 exec, %[sv]\n"
+                                 "s_nop 3\n"
+                                 : "+{v[96:97]}"(Lbar), "+{v[98:99]}"(Rbar), "=&{v[100:101]}"(xf), "=&{v[102:103]}"(t_),
+                                   "+{v[104:105]}"(dmin), "+{v106}"(n), "+{v[112:113]}"(W), [unf] "=&s"(unf_mask), [sv] "=&s"(exec_save), [pre] "=&s"(pre_ok)
+                                 : "{v[108:109]}"(xold), "{v[110:111]}"(Q), "{v[124:139]}"(ud8), "{v[140:143]}"(ud2), [act] "s"(act_m), [need] "s"(need_m)
+                                 : "vcc", "scc");
+#undef PTE_S8_WAIT
+#undef PTE_S8_WAIT_
+#undef PTE_S8_W1
+#undef PTE_S8_W3
+#undef PTE_S8_W5
+#undef PTE_S8_W7
+                    } else
                     asm volatile(".p2align 3\n"           // hand-written stream at an 8-byte phase (MI355X_MICROARCH.md: the 4 mod 8 phase costs ~1 % here)
                                  "s_mov_b64 %[sv], exec\n"
                                  PTE_S8_STEP("%[u0]") PTE_S8_STEP("%[u1]") PTE_S8_STEP("%[u2]") PTE_S8_STEP("%[u3]")
@@ -535,6 +670,8 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                                    [u8] "v"(u[S8_BS > 8 ? 8 : 0]), [u9] "v"(u[S8_BS > 9 ? 9 : 0])
                                  : "vcc");
 #undef PTE_S8_STEP
+#undef PTE_S8_STEP_W
+#undef PTE_S8_STEP_U
                     unf_m = (uint64_t)unf_mask.x | ((uint64_t)unf_mask.y << 32); unf_l0 = __builtin_amdgcn_readfirstlane(unf_mask.x);
                     fin = !__builtin_amdgcn_inverse_ballot_w64(unf_m);
                 } else {

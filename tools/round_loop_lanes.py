@@ -19,7 +19,7 @@ def main():
     hot = C.hot_path(body, header)
     hot_names = set(b["name"] for b in hot)
     for _, cmd, _, _ in units:
-        print("# " + " ".join(cmd[1:]))
+        print("# " + " ".join(cmd[1:]).replace(C.ROOT + os.sep, ""))       # (paths relative to the repository: the listing is committed)
     print("# %s\n# round loop: header %s; its blocks in layout order" % (C.demangle([name])[0], header))
     nl_cold = 0
     for b in C.blocks_of(body):
