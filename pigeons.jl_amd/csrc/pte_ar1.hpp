@@ -14,54 +14,35 @@ namespace pte {
 
 template <int E, int LIK, bool SLICE, bool FULL>
 __global__ __launch_bounds__(64) void k_explore_ar1(EngineDev e, AmParams ap, Ar1Params ar) {
-    automala_body<E, TGT_AR1, SLICE, FULL, false, 1, LIK>(e, ap, blockIdx.x, MixParams{}, GlmParams{}, MixModelParams{}, HierParams{}, ar);
+    automala_body<E, TGT_AR1, SLICE, FULL, false, 1, LIK>(e, ap, blockIdx.x, ar);
 }
 
 // swap statistics of every slot recomputed from the stored states (pte_set_state, pte_set_target_ar1): suff = sum x^2, suff2 = the target's
 // log density
 template <int E, int LIK>
 __global__ __launch_bounds__(64) void k_refresh_ar1_stats(EngineDev e, Ar1Params ar) {
-    const int lane = lane_id();
-    const int64_t slot = blockIdx.x;
-    if (slot >= e.K) return;
-    AmTarget<E, TGT_AR1, false, 1, LIK> T;
-    T.d = e.d; T.lane = lane;
-    T.load_ar1(ar);
-    const double *xrow = e.x + slot * e.ld;
-    double x[E];
-#pragma unroll
-    for (int j = 0; j < E; ++j) x[j] = T.valid(j) ? xrow[64 * j + lane] : 0.0;
-    const double S = sqr_norm_regs<E>(x);
-    const double l2 = T.ar1(x);
-    if (lane == 0) { e.suff[slot] = S; e.suff2[slot] = l2; }
+    PTE_REFRESH_STATS_BODY(E, TGT_AR1, 1, LIK, ar)
 }
 
 int ar1_launch(const Ar1Launch &L, const EngineDev &dev, const AmParams &ap, const Ar1Params &ar) {
-#define AR1_LIK(EE, LL)                                                                                         \
-    if (L.slice) launch_on(L.at, k_explore_ar1<EE, LL, true, false>, 64, 0, dev, ap, ar);                              \
-    else if (L.full) launch_on(L.at, k_explore_ar1<EE, LL, false, true>, 64, 0, dev, ap, ar);                          \
-    else launch_on(L.at, k_explore_ar1<EE, LL, false, false>, 64, 0, dev, ap, ar);
-#define AR1_ONE(EE)                                                                                             \
-    if (L.lik == AR1_NORMAL_IDENTITY) { AR1_LIK(EE, AR1_NORMAL_IDENTITY) } else { AR1_LIK(EE, AR1_STOCHASTIC_VOLATILITY) }
-    switch (L.E) {
-    case 1: AR1_ONE(1) break; case 2: AR1_ONE(2) break; case 4: AR1_ONE(4) break; case 8: AR1_ONE(8) break;
-    default: return 1;
-    }
-#undef AR1_ONE
-#undef AR1_LIK
-    return 0;
+    return with_blocks_per_lane(L.E, [&](auto e_) {
+        auto go = [&](auto p_) {
+            constexpr int E = decltype(e_)::value, LIK = decltype(p_)::value;
+            if (L.slice) launch_on(L.at, k_explore_ar1<E, LIK, true, false>, 64, 0, dev, ap, ar);
+            else if (L.full) launch_on(L.at, k_explore_ar1<E, LIK, false, true>, 64, 0, dev, ap, ar);
+            else launch_on(L.at, k_explore_ar1<E, LIK, false, false>, 64, 0, dev, ap, ar);
+        };
+        if (L.lik == AR1_NORMAL_IDENTITY) go(std::integral_constant<int, AR1_NORMAL_IDENTITY>{});
+        else go(std::integral_constant<int, AR1_STOCHASTIC_VOLATILITY>{});
+    });
 }
 
 int ar1_refresh_stats(int E, int lik, unsigned N, hipStream_t stream, const EngineDev &dev, const Ar1Params &ar) {
-#define AR1_REFRESH(EE)                                                                                                          \
-    if (lik == AR1_NORMAL_IDENTITY) hipLaunchKernelGGL((k_refresh_ar1_stats<EE, AR1_NORMAL_IDENTITY>), dim3(N), dim3(64), 0, stream, dev, ar); \
-    else hipLaunchKernelGGL((k_refresh_ar1_stats<EE, AR1_STOCHASTIC_VOLATILITY>), dim3(N), dim3(64), 0, stream, dev, ar);
-    switch (E) {
-    case 1: AR1_REFRESH(1) break; case 2: AR1_REFRESH(2) break; case 4: AR1_REFRESH(4) break; case 8: AR1_REFRESH(8) break;
-    default: return 1;
-    }
-#undef AR1_REFRESH
-    return 0;
+    return with_blocks_per_lane(E, [&](auto e_) {
+        constexpr int EE = decltype(e_)::value;
+        if (lik == AR1_NORMAL_IDENTITY) hipLaunchKernelGGL((k_refresh_ar1_stats<EE, AR1_NORMAL_IDENTITY>), dim3(N), dim3(64), 0, stream, dev, ar);
+        else hipLaunchKernelGGL((k_refresh_ar1_stats<EE, AR1_STOCHASTIC_VOLATILITY>), dim3(N), dim3(64), 0, stream, dev, ar);
+    });
 }
 
 }  // namespace pte

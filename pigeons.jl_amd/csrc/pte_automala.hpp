@@ -150,6 +150,9 @@ __device__ __forceinline__ double wave_from_above_f64(double v, double edge) {
     return __hiloint2double(hi, lo);
 }
 
+// what a path without data (TGT_MVN, TGT_FUNNEL) hands automala_body in the place of a family's parameter struct
+struct AmNoData {};
+
 template <int E, int TGT, bool FULL = false, int KB = 1, int LIK = 0>
 struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>, AmHierData<TGT == TGT_HIER, E>, AmAr1Data<TGT == TGT_AR1, E>, AmDenseData<TGT == TGT_DENSE, E> {
     int64_t d; int lane;
@@ -243,7 +246,7 @@ struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>
         if (WITH_Q) Q = out[KQ % K];
         return out[1];
     }
-    __device__ __forceinline__ void load_mixture(const MixParams &m) {
+    __device__ __forceinline__ void load(const MixParams &m) {
         mx = m;
 #pragma unroll
         for (int k = 0; k < KB; ++k) mxc[k] = k < m.K ? m.c[k] : 0.0;
@@ -297,10 +300,6 @@ struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>
             }
         }
         return lp;
-    }
-    __device__ __forceinline__ double mixture(const double (&x)[E]) const {
-        double S, Q, dummy[E];
-        return mixture_and_sqr_norm<false, false>(x, dummy, S, x, Q);
     }
     // the GLM's target log density: target = -(p/2) S + c_prior + sum_i l_i(eta_i) + c_obs, eta = X theta.  Two passes through
     // this wave's LDS: theta is broadcast from it to lanes that run over observations (eta_i sequential in j, one fused multiply-add per
@@ -375,10 +374,6 @@ struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>
             for (int j = 0; j < E; ++j) g[j] = valid(j) ? (ref_nprec * x[j]) + acc[j] : 0.0;
         }
         return lp;
-    }
-    __device__ __forceinline__ double glm(const double (&x)[E]) const {
-        double S, Q, dummy[E];
-        return glm_and_sqr_norm<false, false>(x, dummy, S, x, Q);
     }
     // the mixture model's target log density: target = -(p/2) S + c_prior + sum_i l_i + c_obs, l_i = log sum_k exp(a_ik),
     // a_ik = b_k - z_ik^2 / 2, z_ik = (y_i - mu_k) e_k.  The parameters of component k sit in lanes k, K + k, 2 K + k of the one block: they
@@ -468,17 +463,13 @@ struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>
         }
         return lp;
     }
-    __device__ __forceinline__ double mixmodel(const double (&x)[E]) const {
-        double S, Q, dummy[E];
-        return mixmodel_and_sqr_norm<false, false>(x, dummy, S, x, Q);
-    }
     // the hierarchical normal-means posterior: x = [mu, lt = log tau, x_2 .. x_{J+1}], LIK = HIER_CENTERED (x_{2+j} = theta_j) or
     // HIER_NONCENTERED (x_{2+j} = eta_j, theta_j = mu + tau eta_j).  The density is one sum over the fixed tree with the leaves in state order:
     // leaf 0 the prior of mu, leaf 1 the half-Cauchy of tau with the Jacobian of lt, leaf 2 + j = log N(y_j; theta_j, sigma_j^2) + the group
     // coordinate's prior.  tau = exp(lt), 1 / tau = exp(-lt) and log1p((tau / tau_scale)^2) are computed once, on the value lanes 0 and 1 of
     // block 0 hold.  GRAD: the group coordinates' derivatives are elementwise; those of mu and lt are two more sums over the same tree, in
     // lockstep with the density, S = sum x^2 and (WITH_Q) Q = sum q^2.  Lanes past d are masked by index and contribute exactly 0.
-    __device__ __forceinline__ void load_hier(const HierParams &h) {
+    __device__ __forceinline__ void load(const HierParams &h) {
         this->hp = h;
         if constexpr (AmHierData<true, E>::H_IN_REGS) {
 #pragma unroll
@@ -529,10 +520,6 @@ struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>
         if (WITH_Q) Q = out[KQ % K];
         return out[1];
     }
-    __device__ __forceinline__ double hier(const double (&x)[E]) const {
-        double S, Q, dummy[E];
-        return hier_and_sqr_norm<false, false>(x, dummy, S, x, Q);
-    }
     // the latent-AR(1) posterior: x = [mu, a, ls, h_0 .. h_{T-1}], phi = tanh(a), sigma = exp(ls), LIK = AR1_STOCHASTIC_VOLATILITY
     // (y_t ~ N(0, exp(h_t))) or AR1_NORMAL_IDENTITY (y_t ~ N(h_t, obs_sd^2)).  The density is one sum over the fixed tree with the leaves in
     // state order: leaves 0..2 the priors of mu, a and sigma (with the Jacobian of ls), leaf 3 + t = the transition term of h_t + its
@@ -541,7 +528,7 @@ struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>
     // has the stationary law and reads no neighbour.  GRAD: the h components are elementwise given the successor's residual, which comes from
     // the lane above (lane 63: lane 0 of the block after); those of mu, a and ls are three more sums over the same tree, in lockstep with the
     // density, S = sum x^2 and (WITH_Q) Q = sum q^2.  Lanes past d are masked by index and contribute exactly 0.
-    __device__ __forceinline__ void load_ar1(const Ar1Params &a) {
+    __device__ __forceinline__ void load(const Ar1Params &a) {
         this->ar = a;
         if constexpr (AmAr1Data<true, E>::A_IN_REGS) {
             const double *src = LIK == AR1_NORMAL_IDENTITY ? a.y : a.y2;
@@ -624,10 +611,6 @@ struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>
         if constexpr (WITH_Q) Q = out[KQ];
         return out[1];
     }
-    __device__ __forceinline__ double ar1(const double (&x)[E]) const {
-        double S, Q, dummy[E];
-        return ar1_and_sqr_norm<false, false>(x, dummy, S, x, Q);
-    }
     // the dense-precision Gaussian N(m, Q^-1): z = x - m, u = Q z, A = z' u, l2 = c - A / 2, gradient -u.  u_i = sum_k Q[k][i] z_k
     // is accumulated for k = 0 .. d-1 in that order, one fused multiply-add per term from 0.0: row k of the symmetric matrix is E coalesced
     // loads (lane l takes Q[k][64 j + l]), z_k reaches every lane through a read-lane with a uniform index -- no LDS, no memory round trip.
@@ -695,52 +678,39 @@ struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>
         }
         return this->dn.c - 0.5 * A;
     }
-    __device__ __forceinline__ double dense(const double (&x)[E]) const {
-        double S, Q, dummy[E];
-        return dense_and_sqr_norm<false, false>(x, dummy, S, x, Q);
+    // The six data families -- paths (1 - beta) reference + beta target whose target is a <family>_and_sqr_norm member -- are dispatched HERE and
+    // nowhere else: a new family adds its TGT to DATA_FAMILY, a line to the chain below and a load() overload.
+    // (The chain is a macro, not a forwarding member: one more level of inlining reorders the loads of the families' kernels -- DESIGN 4.10)
+    static constexpr bool DATA_FAMILY = TGT == TGT_DENSE || TGT == TGT_AR1 || TGT == TGT_HIER || TGT == TGT_MIXMODEL || TGT == TGT_GLM || TGT == TGT_MIXTURE;
+#define PTE_AM_TARGET_AND_SQR_NORM(l2, GRAD, WITH_Q, ...)                                                    \
+    if constexpr (TGT == TGT_DENSE) l2 = dense_and_sqr_norm<GRAD, WITH_Q>(__VA_ARGS__);                      \
+    else if constexpr (TGT == TGT_AR1) l2 = ar1_and_sqr_norm<GRAD, WITH_Q>(__VA_ARGS__);                     \
+    else if constexpr (TGT == TGT_HIER) l2 = hier_and_sqr_norm<GRAD, WITH_Q>(__VA_ARGS__);                   \
+    else if constexpr (TGT == TGT_MIXMODEL) l2 = mixmodel_and_sqr_norm<GRAD, WITH_Q>(__VA_ARGS__);           \
+    else if constexpr (TGT == TGT_GLM) l2 = glm_and_sqr_norm<GRAD, WITH_Q>(__VA_ARGS__);                     \
+    else l2 = mixture_and_sqr_norm<GRAD, WITH_Q>(__VA_ARGS__)
+    // the target's log density alone: what the swap statistic suff2 holds
+    __device__ __forceinline__ double target(const double (&x)[E]) const {
+        double l2, S, Q, dummy[E];
+        PTE_AM_TARGET_AND_SQR_NORM(l2, false, false, x, dummy, S, x, Q);
+        return l2;
     }
+    // the family's data, as its kernel takes it (d and lane are set): one overload per parameter struct (MixParams, HierParams and Ar1Params: above,
+    // beside their members), an empty one for the paths without data
+    __device__ __forceinline__ void load(const AmNoData &) {}
+    __device__ __forceinline__ void load(const GlmParams &gp) {
+        extern __shared__ __attribute__((aligned(16))) double glm_lds[];      // after automala_body's s_wi / s_ki / s_fi (6 KiB: the base stays 16-B aligned)
+        this->gl = gp; this->glds = glm_lds;
+    }
+    __device__ __forceinline__ void load(const MixModelParams &m) { this->mm = m; this->mk = (int)(d / 3); }
+    __device__ __forceinline__ void load(const DenseParams &n) { this->dn = n; }
     // log_potentials[chain](x) as a plain callable: InterpolatedLogPotential(x) (src/paths/InterpolatedLogPotential.jl:9-16)
     // WITH its beta == 0 / beta == 1 short-circuits -- what SliceSampler evaluates (the AD form below has none)
     __device__ __forceinline__ double path_lp(const double (&x)[E]) const {
-        if constexpr (TGT == TGT_DENSE) {
+        if constexpr (DATA_FAMILY) {
             if (beta == 0.0) return ref_nhp * sqr_norm_regs<E>(x);
-            double S, Q, dummy[E];
-            const double l2 = dense_and_sqr_norm<false, false>(x, dummy, S, x, Q);
-            if (beta == 1.0) return l2;
-            return omb * (ref_nhp * S) + beta * l2;
-        }
-        if constexpr (TGT == TGT_AR1) {
-            if (beta == 0.0) return ref_nhp * sqr_norm_regs<E>(x);
-            double S, Q, dummy[E];
-            const double l2 = ar1_and_sqr_norm<false, false>(x, dummy, S, x, Q);
-            if (beta == 1.0) return l2;
-            return omb * (ref_nhp * S) + beta * l2;
-        }
-        if constexpr (TGT == TGT_HIER) {
-            if (beta == 0.0) return ref_nhp * sqr_norm_regs<E>(x);
-            double S, Q, dummy[E];
-            const double l2 = hier_and_sqr_norm<false, false>(x, dummy, S, x, Q);
-            if (beta == 1.0) return l2;
-            return omb * (ref_nhp * S) + beta * l2;
-        }
-        if constexpr (TGT == TGT_MIXMODEL) {
-            if (beta == 0.0) return ref_nhp * sqr_norm_regs<E>(x);
-            double S, Q, dummy[E];
-            const double l2 = mixmodel_and_sqr_norm<false, false>(x, dummy, S, x, Q);
-            if (beta == 1.0) return l2;
-            return omb * (ref_nhp * S) + beta * l2;
-        }
-        if constexpr (TGT == TGT_GLM) {
-            if (beta == 0.0) return ref_nhp * sqr_norm_regs<E>(x);
-            double S, Q, dummy[E];
-            const double l2 = glm_and_sqr_norm<false, false>(x, dummy, S, x, Q);
-            if (beta == 1.0) return l2;
-            return omb * (ref_nhp * S) + beta * l2;
-        }
-        if (TGT == TGT_MIXTURE) {
-            if (beta == 0.0) return ref_nhp * sqr_norm_regs<E>(x);
-            double S, Q, dummy[E];
-            const double l2 = mixture_and_sqr_norm<false, false>(x, dummy, S, x, Q);
+            double S, Q, dummy[E], l2;
+            PTE_AM_TARGET_AND_SQR_NORM(l2, false, false, x, dummy, S, x, Q);
             if (beta == 1.0) return l2;
             return omb * (ref_nhp * S) + beta * l2;
         }
@@ -756,28 +726,8 @@ struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>
     __device__ __forceinline__ double logdensity(const double (&x)[E]) const {
         if (TGT == TGT_MVN) return nhp * sqr_norm_regs<E>(x);
         double S, l2, dummy[E], dq;
-        if constexpr (TGT == TGT_DENSE) {
-            l2 = dense_and_sqr_norm<false, false>(x, dummy, S, x, dq);
-            return omb * (ref_nhp * S) + beta * l2;
-        }
-        if constexpr (TGT == TGT_AR1) {
-            l2 = ar1_and_sqr_norm<false, false>(x, dummy, S, x, dq);
-            return omb * (ref_nhp * S) + beta * l2;
-        }
-        if constexpr (TGT == TGT_HIER) {
-            l2 = hier_and_sqr_norm<false, false>(x, dummy, S, x, dq);
-            return omb * (ref_nhp * S) + beta * l2;
-        }
-        if constexpr (TGT == TGT_MIXMODEL) {
-            l2 = mixmodel_and_sqr_norm<false, false>(x, dummy, S, x, dq);
-            return omb * (ref_nhp * S) + beta * l2;
-        }
-        if constexpr (TGT == TGT_GLM) {
-            l2 = glm_and_sqr_norm<false, false>(x, dummy, S, x, dq);
-            return omb * (ref_nhp * S) + beta * l2;
-        }
-        if (TGT == TGT_MIXTURE) {
-            l2 = mixture_and_sqr_norm<false, false>(x, dummy, S, x, dq);
+        if constexpr (DATA_FAMILY) {
+            PTE_AM_TARGET_AND_SQR_NORM(l2, false, false, x, dummy, S, x, dq);
             return omb * (ref_nhp * S) + beta * l2;
         }
         if (E <= 4) l2 = funnel_and_sqr_norm<false, false>(x, dummy, S, x, dq);
@@ -804,48 +754,8 @@ struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>
         double logdens = 0.0;
         double g2[E];
         double l2;
-        if constexpr (TGT == TGT_DENSE) {
-            l2 = dense_and_sqr_norm<true, WITH_Q>(x, g2, S, q, Q);
-            logdens += (ref_nhp * S) * omb;
-            logdens += l2 * beta;
-#pragma unroll
-            for (int j = 0; j < E; ++j) g[j] = (ref_nprec * x[j]) * omb + g2[j] * beta;
-            return logdens;
-        }
-        if constexpr (TGT == TGT_AR1) {
-            l2 = ar1_and_sqr_norm<true, WITH_Q>(x, g2, S, q, Q);
-            logdens += (ref_nhp * S) * omb;
-            logdens += l2 * beta;
-#pragma unroll
-            for (int j = 0; j < E; ++j) g[j] = (ref_nprec * x[j]) * omb + g2[j] * beta;
-            return logdens;
-        }
-        if constexpr (TGT == TGT_HIER) {
-            l2 = hier_and_sqr_norm<true, WITH_Q>(x, g2, S, q, Q);
-            logdens += (ref_nhp * S) * omb;
-            logdens += l2 * beta;
-#pragma unroll
-            for (int j = 0; j < E; ++j) g[j] = (ref_nprec * x[j]) * omb + g2[j] * beta;
-            return logdens;
-        }
-        if constexpr (TGT == TGT_MIXMODEL) {
-            l2 = mixmodel_and_sqr_norm<true, WITH_Q>(x, g2, S, q, Q);
-            logdens += (ref_nhp * S) * omb;
-            logdens += l2 * beta;
-#pragma unroll
-            for (int j = 0; j < E; ++j) g[j] = (ref_nprec * x[j]) * omb + g2[j] * beta;
-            return logdens;
-        }
-        if constexpr (TGT == TGT_GLM) {
-            l2 = glm_and_sqr_norm<true, WITH_Q>(x, g2, S, q, Q);
-            logdens += (ref_nhp * S) * omb;
-            logdens += l2 * beta;
-#pragma unroll
-            for (int j = 0; j < E; ++j) g[j] = (ref_nprec * x[j]) * omb + g2[j] * beta;
-            return logdens;
-        }
-        if (TGT == TGT_MIXTURE) {
-            l2 = mixture_and_sqr_norm<true, WITH_Q>(x, g2, S, q, Q);
+        if constexpr (DATA_FAMILY) {
+            PTE_AM_TARGET_AND_SQR_NORM(l2, true, WITH_Q, x, g2, S, q, Q);
             logdens += (ref_nhp * S) * omb;
             logdens += l2 * beta;
 #pragma unroll
@@ -874,6 +784,7 @@ struct AmTarget : AmGlmData<TGT == TGT_GLM>, AmMixModelData<TGT == TGT_MIXMODEL>
     MixParams mx;               // TGT_MIXTURE: the components (K <= KB), their constants c_k in registers
     double mxc[KB];
 };
+#undef PTE_AM_TARGET_AND_SQR_NORM
 
 // SLICE = true instantiates the same prologue (reference-chain refresh, state load) and epilogue (swap statistics, recorders)
 // around the SliceSampler sweep instead of the Langevin refreshes: a separate kernel, so that neither pays for the other's registers.
@@ -888,15 +799,13 @@ __device__ __forceinline__ int64_t am_chain_of_workgroup(int64_t K, int64_t wg) 
 
 // DIRECT (the scan loop with several chains per workgroup, k_scans_automala_wg): `wg` IS the local chain, and the table staging ends in a
 // wave-level wait instead of a workgroup barrier -- every wave writes all the (identical) entries itself, so it only has to see its own stores
-// KB, mp: TGT_MIXTURE only -- the components' bucket (K <= KB) and parameters.  LIK, gp: TGT_GLM only -- the likelihood and the data
-// (the workgroup's dynamic LDS holds theta and r: pte_glm.hpp).  mm: TGT_MIXMODEL only -- the observations (pte_mixture_model.hpp)
-// hp: TGT_HIER only -- the groups' data, LIK its parameterisation (pte_hier.hpp).  ar: TGT_AR1 only -- the observations, LIK the observation
-// model (pte_ar1.hpp).  dn: TGT_DENSE only -- the mean and the precision matrix (pte_dense.hpp)
-template <int E, int TGT, bool SLICE = false, bool FULL = false, bool DIRECT = false, int KB = 1, int LIK = 0>
-__device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const int64_t wg, const MixParams &mp = MixParams{},
-                                              const GlmParams &gp = GlmParams{}, const MixModelParams &mm = MixModelParams{},
-                                              const HierParams &hp = HierParams{}, const Ar1Params &ar = Ar1Params{},
-                                              const DenseParams &dn = DenseParams{}) {      // wg: blockIdx.x
+// fp: the family's data as its kernel takes it (MixParams, GlmParams, ... -- FP is deduced; nothing on the MVN and funnel paths), handed to
+// AmTarget::load; KB (the components' bucket, K <= KB) and LIK (the likelihood / parameterisation / observation model) are the family's
+// compile-time choices.  Which target it is is asked in AmTarget alone (DATA_FAMILY, its chain over the families, target, load): the body below
+// names no family but the funnel, whose path has a reference of its own (the variational leg, suff3).  TGT_GLM's dynamic LDS (theta and r:
+// pte_glm.hpp) lies behind the tables staged here.
+template <int E, int TGT, bool SLICE = false, bool FULL = false, bool DIRECT = false, int KB = 1, int LIK = 0, class FP = AmNoData>
+__device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const int64_t wg, const FP &fp = FP{}) {      // wg: blockIdx.x
     constexpr int NLU = (E == 1 ? 0 : E == 2 ? 1 : E == 4 ? 2 : E == 8 ? 3 : 4);
     const int lane = lane_id();
     // the ziggurat tables of the momentum draws, staged once: a global gather per block of draws costs a memory round trip each time
@@ -914,17 +823,10 @@ __device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const in
     const int slot = e.slot_of_chain[cl];
     const int64_t d = e.d;
     double *xrow = e.x + (int64_t)slot * e.ld;
-    AmTarget<E, TGT, FULL, KB, LIK> T;
+    using Target = AmTarget<E, TGT, FULL, KB, LIK>;
+    Target T;
     T.d = d; T.lane = lane;
-    if (TGT == TGT_MIXTURE) T.load_mixture(mp);
-    if constexpr (TGT == TGT_GLM) {
-        extern __shared__ __attribute__((aligned(16))) double glm_lds[];      // after s_wi / s_ki / s_fi (6 KiB: the base stays 16-B aligned)
-        T.gl = gp; T.glds = glm_lds;
-    }
-    if constexpr (TGT == TGT_MIXMODEL) { T.mm = mm; T.mk = (int)(d / 3); }
-    if constexpr (TGT == TGT_HIER) T.load_hier(hp);
-    if constexpr (TGT == TGT_AR1) T.load_ar1(ar);
-    if constexpr (TGT == TGT_DENSE) T.dn = dn;
+    T.load(fp);
     T.nhp = e.nhp[c]; T.nprec = e.nprec[c];
     T.beta = e.beta[c]; T.omb = 1.0 - T.beta;
     T.ref_nhp = -0.5 * ap.ref_prec; T.ref_nprec = -ap.ref_prec; T.log3 = ap.log3;
@@ -963,28 +865,8 @@ __device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const in
             if (lane == 0) e.suff2[slot] = l20;
             if (v_on) { l30 = T.variational_lp(x); if (lane == 0) e.suff3[slot] = l30; }
         }
-        if (TGT == TGT_MIXTURE) {
-            l20 = T.mixture(x);
-            if (lane == 0) e.suff2[slot] = l20;
-        }
-        if constexpr (TGT == TGT_GLM) {
-            l20 = T.glm(x);
-            if (lane == 0) e.suff2[slot] = l20;
-        }
-        if constexpr (TGT == TGT_MIXMODEL) {
-            l20 = T.mixmodel(x);
-            if (lane == 0) e.suff2[slot] = l20;
-        }
-        if constexpr (TGT == TGT_HIER) {
-            l20 = T.hier(x);
-            if (lane == 0) e.suff2[slot] = l20;
-        }
-        if constexpr (TGT == TGT_AR1) {
-            l20 = T.ar1(x);
-            if (lane == 0) e.suff2[slot] = l20;
-        }
-        if constexpr (TGT == TGT_DENSE) {
-            l20 = T.dense(x);
+        if constexpr (Target::DATA_FAMILY) {
+            l20 = T.target(x);
             if (lane == 0) e.suff2[slot] = l20;
         }
         record_after_explore_impl(e, cl, c, slot, lane, lp0, S0, l20, l30);
@@ -1257,16 +1139,11 @@ __device__ __forceinline__ void automala_body(EngineDev e, AmParams ap, const in
     const double S = sqr_norm_regs<E>(x);
     double l2 = 0.0, l3 = 0.0;
     if (TGT == TGT_FUNNEL) l2 = T.funnel(x, nullptr);
-    if (TGT == TGT_MIXTURE) l2 = T.mixture(x);
-    if constexpr (TGT == TGT_GLM) l2 = T.glm(x);
-    if constexpr (TGT == TGT_MIXMODEL) l2 = T.mixmodel(x);
-    if constexpr (TGT == TGT_HIER) l2 = T.hier(x);
-    if constexpr (TGT == TGT_AR1) l2 = T.ar1(x);
-    if constexpr (TGT == TGT_DENSE) l2 = T.dense(x);
+    if constexpr (Target::DATA_FAMILY) l2 = T.target(x);
     if (v_on) l3 = T.variational_lp(x);
     if (lane == 0) {
         e.suff[slot] = S;
-        if (TGT == TGT_FUNNEL || TGT == TGT_MIXTURE || TGT == TGT_GLM || TGT == TGT_MIXMODEL || TGT == TGT_HIER || TGT == TGT_AR1 || TGT == TGT_DENSE) e.suff2[slot] = l2;
+        if (TGT == TGT_FUNNEL || Target::DATA_FAMILY) e.suff2[slot] = l2;
         if (v_on) e.suff3[slot] = l3;
         e.rng[2 * slot] = r.seed;
         e.expl_steps_sum[cl] += (double)steps_sum; e.expl_steps_n[cl] += steps_n;
@@ -1370,7 +1247,26 @@ __global__ __launch_bounds__(64 * PTE_SCAN_WG) void k_scans_automala_wg(EngineDe
     }
 }
 
-// Swap statistics of every slot recomputed from the stored states (pte_set_state on an interpolated path):
+// Swap statistics of every slot recomputed from the stored states (pte_set_state, pte_set_target_<family>) on a data family's path:
+// suff = sum x^2 with the fixed tree, suff2 = the target's log density.  The body of k_refresh_<family>_stats(EngineDev e, <Family>Params fp),
+// one workgroup of one wave per slot.  (A macro: as a called body, however inlined, it moved the schedule of every kernel made of it --
+// DESIGN 4.10.  The GLM's and the mixture model's kernels, which set their data in the kernel itself, keep their own for the same reason.)
+#define PTE_REFRESH_STATS_BODY(E, TGT, KB, LIK, fp)                                                 \
+    const int lane = lane_id();                                                                    \
+    const int64_t slot = blockIdx.x;                                                               \
+    if (slot >= e.K) return;                                                                       \
+    AmTarget<E, TGT, false, KB, LIK> T;                                                            \
+    T.d = e.d; T.lane = lane;                                                                      \
+    T.load(fp);                                                                                    \
+    const double *xrow = e.x + slot * e.ld;                                                        \
+    double x[E];                                                                                   \
+    _Pragma("unroll")                                                                              \
+    for (int j = 0; j < E; ++j) x[j] = T.valid(j) ? xrow[64 * j + lane] : 0.0;                     \
+    const double S = sqr_norm_regs<E>(x);                                                          \
+    const double l2 = T.target(x);                                                                 \
+    if (lane == 0) { e.suff[slot] = S; e.suff2[slot] = l2; }
+
+// The same on the funnel path (a body of its own: suff3, the variational reference's log density, beside the two):
 // suff = sum x^2 with the fixed tree, suff2 = the funnel's log density.
 template <int E>
 __global__ __launch_bounds__(64) void k_refresh_funnel_stats(EngineDev e, double log3) {

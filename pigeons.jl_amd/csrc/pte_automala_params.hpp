@@ -18,6 +18,7 @@
 // Tools and development builds compile pte.hip alone (no -DPTE_SPLIT_LANGEVIN): it then includes the kernel headers and their entry points itself.
 #pragma once
 #include <hip/hip_ext.h>
+#include <type_traits>
 #include "pte_kernels.hpp"
 
 namespace pte {
@@ -56,6 +57,18 @@ template <typename K, typename... Args>
 static inline void launch_on(const LaunchSite &at, K kernel, dim3 block, size_t lds_bytes, const Args &...args) {
     if (at.ev_a) hipExtLaunchKernelGGL(kernel, at.grid, block, lds_bytes, at.stream, at.ev_a, at.ev_b, 0, args...);
     else hipLaunchKernelGGL(kernel, at.grid, block, lds_bytes, at.stream, args...);
+}
+// The run-time blocks per lane E as a compile-time constant: f(std::integral_constant<int, E>{}) for the E the one-wave kernels are built
+// for -> 0; any other E -> 1 ("this build holds no such kernel") and f is not called.  The one place the family headers spell the list.
+template <typename F>
+static inline int with_blocks_per_lane(int E, F &&f) {
+    switch (E) {
+    case 1: f(std::integral_constant<int, 1>{}); return 0;
+    case 2: f(std::integral_constant<int, 2>{}); return 0;
+    case 4: f(std::integral_constant<int, 4>{}); return 0;
+    case 8: f(std::integral_constant<int, 8>{}); return 0;
+    default: return 1;
+    }
 }
 
 // one launch of k_explore_automala<E, target, slice mode, whole blocks>, one workgroup of one wave per replica

@@ -17,7 +17,7 @@ namespace pte {
 template <int E, bool SLICE, bool FULL>
 __global__ __launch_bounds__(64) void k_explore_dense(EngineDev e, AmParams ap, DenseParams dn) {
     static_assert(!SLICE, "SliceSampler on the dense-normal path is k_explore_dense_slice");
-    automala_body<E, TGT_DENSE, SLICE, FULL, false, 1, 0>(e, ap, blockIdx.x, MixParams{}, GlmParams{}, MixModelParams{}, HierParams{}, Ar1Params{}, dn);
+    automala_body<E, TGT_DENSE, SLICE, FULL>(e, ap, blockIdx.x, dn);
 }
 
 // coordinate idx of v (uniform idx), as a uniform value
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(64) void k_explore_dense_slice(EngineDev e, AmParam
         __threadfence_block();
 #pragma unroll
         for (int j = 0; j < E; ++j) x[j] = T.valid(j) ? xrow[64 * j + lane] : 0.0;
-        const double l20 = T.dense(x);
+        const double l20 = T.target(x);
         if (lane == 0) e.suff2[slot] = l20;
         record_after_explore_impl(e, cl, c, slot, lane, lp0, S0, l20);
         return;
@@ -155,29 +155,20 @@ __global__ __launch_bounds__(64) void k_refresh_dense_stats(EngineDev e, DensePa
 }
 
 int dense_launch(const DenseLaunch &L, const EngineDev &dev, const AmParams &ap, const DenseParams &dn) {
-#define DENSE_ONE(EE)                                                                                                      \
-    if (L.slice) {                                                                                                         \
-        if (L.full) launch_on(L.at, k_explore_dense_slice<EE, true>, 64, 0, dev, ap, dn);                                  \
-        else launch_on(L.at, k_explore_dense_slice<EE, false>, 64, 0, dev, ap, dn);                                        \
-    } else if (L.full) launch_on(L.at, k_explore_dense<EE, false, true>, 64, 0, dev, ap, dn);                              \
-    else launch_on(L.at, k_explore_dense<EE, false, false>, 64, 0, dev, ap, dn);
-    switch (L.E) {
-    case 1: DENSE_ONE(1) break; case 2: DENSE_ONE(2) break; case 4: DENSE_ONE(4) break; case 8: DENSE_ONE(8) break;
-    default: return 1;
-    }
-#undef DENSE_ONE
-    return 0;
+    return with_blocks_per_lane(L.E, [&](auto e_) {
+        constexpr int E = decltype(e_)::value;
+        if (L.slice) {
+            if (L.full) launch_on(L.at, k_explore_dense_slice<E, true>, 64, 0, dev, ap, dn);
+            else launch_on(L.at, k_explore_dense_slice<E, false>, 64, 0, dev, ap, dn);
+        } else if (L.full) launch_on(L.at, k_explore_dense<E, false, true>, 64, 0, dev, ap, dn);
+        else launch_on(L.at, k_explore_dense<E, false, false>, 64, 0, dev, ap, dn);
+    });
 }
 
 int dense_refresh_stats(int E, unsigned N, hipStream_t stream, const EngineDev &dev, const DenseParams &dn) {
-    switch (E) {
-    case 1: hipLaunchKernelGGL((k_refresh_dense_stats<1>), dim3(N), dim3(64), 0, stream, dev, dn); break;
-    case 2: hipLaunchKernelGGL((k_refresh_dense_stats<2>), dim3(N), dim3(64), 0, stream, dev, dn); break;
-    case 4: hipLaunchKernelGGL((k_refresh_dense_stats<4>), dim3(N), dim3(64), 0, stream, dev, dn); break;
-    case 8: hipLaunchKernelGGL((k_refresh_dense_stats<8>), dim3(N), dim3(64), 0, stream, dev, dn); break;
-    default: return 1;
-    }
-    return 0;
+    return with_blocks_per_lane(E, [&](auto e_) {
+        hipLaunchKernelGGL((k_refresh_dense_stats<decltype(e_)::value>), dim3(N), dim3(64), 0, stream, dev, dn);
+    });
 }
 
 }  // namespace pte

@@ -12,11 +12,12 @@ namespace pte {
 
 template <int E, int LIK, bool SLICE, bool FULL>
 __global__ __launch_bounds__(64) void k_explore_glm(EngineDev e, AmParams ap, GlmParams gp) {
-    automala_body<E, TGT_GLM, SLICE, FULL, false, 1, LIK>(e, ap, blockIdx.x, MixParams{}, gp);
+    automala_body<E, TGT_GLM, SLICE, FULL, false, 1, LIK>(e, ap, blockIdx.x, gp);
 }
 
 // swap statistics of every slot recomputed from the stored states (pte_set_state, pte_set_target_glm): suff = sum x^2, suff2 = the GLM's
-// target log density
+// target log density.  (A body of its own: the target holds the reference's precision, and the data and this wave's LDS are set here, in the
+// kernel -- PTE_REFRESH_STATS_BODY's T.load(gp) moved the schedule of these kernels: pte_automala.hpp)
 template <int E, int LIK>
 __global__ __launch_bounds__(64) void k_refresh_glm_stats(EngineDev e, GlmParams gp, double ref_prec) {
     extern __shared__ __attribute__((aligned(16))) double glm_lds[];
@@ -32,38 +33,31 @@ __global__ __launch_bounds__(64) void k_refresh_glm_stats(EngineDev e, GlmParams
 #pragma unroll
     for (int j = 0; j < E; ++j) x[j] = T.valid(j) ? xrow[64 * j + lane] : 0.0;
     const double S = sqr_norm_regs<E>(x);
-    const double l2 = T.glm(x);
+    const double l2 = T.target(x);
     if (lane == 0) { e.suff[slot] = S; e.suff2[slot] = l2; }
 }
 
 int glm_launch(const GlmLaunch &L, const EngineDev &dev, const AmParams &ap, const GlmParams &gp) {
     const size_t lds = glm_lds_bytes(L.E, gp.n_pad);
-#define GLM_LIK(EE, LL)                                                                                         \
-    if (L.slice) launch_on(L.at, k_explore_glm<EE, LL, true, false>, 64, lds, dev, ap, gp);                            \
-    else if (L.full) launch_on(L.at, k_explore_glm<EE, LL, false, true>, 64, lds, dev, ap, gp);                        \
-    else launch_on(L.at, k_explore_glm<EE, LL, false, false>, 64, lds, dev, ap, gp);
-#define GLM_ONE(EE)                                                                                             \
-    if (L.lik == GLM_NORMAL_IDENTITY) { GLM_LIK(EE, GLM_NORMAL_IDENTITY) } else { GLM_LIK(EE, GLM_BERNOULLI_LOGIT) }
-    switch (L.E) {
-    case 1: GLM_ONE(1) break; case 2: GLM_ONE(2) break; case 4: GLM_ONE(4) break; case 8: GLM_ONE(8) break;
-    default: return 1;
-    }
-#undef GLM_ONE
-#undef GLM_LIK
-    return 0;
+    return with_blocks_per_lane(L.E, [&](auto e_) {
+        auto go = [&](auto p_) {
+            constexpr int E = decltype(e_)::value, LIK = decltype(p_)::value;
+            if (L.slice) launch_on(L.at, k_explore_glm<E, LIK, true, false>, 64, lds, dev, ap, gp);
+            else if (L.full) launch_on(L.at, k_explore_glm<E, LIK, false, true>, 64, lds, dev, ap, gp);
+            else launch_on(L.at, k_explore_glm<E, LIK, false, false>, 64, lds, dev, ap, gp);
+        };
+        if (L.lik == GLM_NORMAL_IDENTITY) go(std::integral_constant<int, GLM_NORMAL_IDENTITY>{});
+        else go(std::integral_constant<int, GLM_BERNOULLI_LOGIT>{});
+    });
 }
 
 int glm_refresh_stats(int E, int lik, unsigned N, hipStream_t stream, const EngineDev &dev, const GlmParams &gp, double ref_prec) {
     const size_t lds = glm_lds_bytes(E, gp.n_pad);
-#define GLM_REFRESH(EE)                                                                                                                    \
-    if (lik == GLM_NORMAL_IDENTITY) hipLaunchKernelGGL((k_refresh_glm_stats<EE, GLM_NORMAL_IDENTITY>), dim3(N), dim3(64), lds, stream, dev, gp, ref_prec); \
-    else hipLaunchKernelGGL((k_refresh_glm_stats<EE, GLM_BERNOULLI_LOGIT>), dim3(N), dim3(64), lds, stream, dev, gp, ref_prec);
-    switch (E) {
-    case 1: GLM_REFRESH(1) break; case 2: GLM_REFRESH(2) break; case 4: GLM_REFRESH(4) break; case 8: GLM_REFRESH(8) break;
-    default: return 1;
-    }
-#undef GLM_REFRESH
-    return 0;
+    return with_blocks_per_lane(E, [&](auto e_) {
+        constexpr int EE = decltype(e_)::value;
+        if (lik == GLM_NORMAL_IDENTITY) hipLaunchKernelGGL((k_refresh_glm_stats<EE, GLM_NORMAL_IDENTITY>), dim3(N), dim3(64), lds, stream, dev, gp, ref_prec);
+        else hipLaunchKernelGGL((k_refresh_glm_stats<EE, GLM_BERNOULLI_LOGIT>), dim3(N), dim3(64), lds, stream, dev, gp, ref_prec);
+    });
 }
 
 PTE_DEFINE_RNG_POLICY_SETTER(glm)

@@ -13,54 +13,35 @@ namespace pte {
 
 template <int E, int PARAM, bool SLICE, bool FULL>
 __global__ __launch_bounds__(64) void k_explore_hier(EngineDev e, AmParams ap, HierParams hp) {
-    automala_body<E, TGT_HIER, SLICE, FULL, false, 1, PARAM>(e, ap, blockIdx.x, MixParams{}, GlmParams{}, MixModelParams{}, hp);
+    automala_body<E, TGT_HIER, SLICE, FULL, false, 1, PARAM>(e, ap, blockIdx.x, hp);
 }
 
 // swap statistics of every slot recomputed from the stored states (pte_set_state, pte_set_target_hier): suff = sum x^2, suff2 = the target's
 // log density
 template <int E, int PARAM>
 __global__ __launch_bounds__(64) void k_refresh_hier_stats(EngineDev e, HierParams hp) {
-    const int lane = lane_id();
-    const int64_t slot = blockIdx.x;
-    if (slot >= e.K) return;
-    AmTarget<E, TGT_HIER, false, 1, PARAM> T;
-    T.d = e.d; T.lane = lane;
-    T.load_hier(hp);
-    const double *xrow = e.x + slot * e.ld;
-    double x[E];
-#pragma unroll
-    for (int j = 0; j < E; ++j) x[j] = T.valid(j) ? xrow[64 * j + lane] : 0.0;
-    const double S = sqr_norm_regs<E>(x);
-    const double l2 = T.hier(x);
-    if (lane == 0) { e.suff[slot] = S; e.suff2[slot] = l2; }
+    PTE_REFRESH_STATS_BODY(E, TGT_HIER, 1, PARAM, hp)
 }
 
 int hier_launch(const HierLaunch &L, const EngineDev &dev, const AmParams &ap, const HierParams &hp) {
-#define HIER_PARAM(EE, PP)                                                                                      \
-    if (L.slice) launch_on(L.at, k_explore_hier<EE, PP, true, false>, 64, 0, dev, ap, hp);                             \
-    else if (L.full) launch_on(L.at, k_explore_hier<EE, PP, false, true>, 64, 0, dev, ap, hp);                         \
-    else launch_on(L.at, k_explore_hier<EE, PP, false, false>, 64, 0, dev, ap, hp);
-#define HIER_ONE(EE)                                                                                            \
-    if (L.param == HIER_NONCENTERED) { HIER_PARAM(EE, HIER_NONCENTERED) } else { HIER_PARAM(EE, HIER_CENTERED) }
-    switch (L.E) {
-    case 1: HIER_ONE(1) break; case 2: HIER_ONE(2) break; case 4: HIER_ONE(4) break; case 8: HIER_ONE(8) break;
-    default: return 1;
-    }
-#undef HIER_ONE
-#undef HIER_PARAM
-    return 0;
+    return with_blocks_per_lane(L.E, [&](auto e_) {
+        auto go = [&](auto p_) {
+            constexpr int E = decltype(e_)::value, PARAM = decltype(p_)::value;
+            if (L.slice) launch_on(L.at, k_explore_hier<E, PARAM, true, false>, 64, 0, dev, ap, hp);
+            else if (L.full) launch_on(L.at, k_explore_hier<E, PARAM, false, true>, 64, 0, dev, ap, hp);
+            else launch_on(L.at, k_explore_hier<E, PARAM, false, false>, 64, 0, dev, ap, hp);
+        };
+        if (L.param == HIER_NONCENTERED) go(std::integral_constant<int, HIER_NONCENTERED>{});
+        else go(std::integral_constant<int, HIER_CENTERED>{});
+    });
 }
 
 int hier_refresh_stats(int E, int param, unsigned N, hipStream_t stream, const EngineDev &dev, const HierParams &hp) {
-#define HIER_REFRESH(EE)                                                                                                         \
-    if (param == HIER_NONCENTERED) hipLaunchKernelGGL((k_refresh_hier_stats<EE, HIER_NONCENTERED>), dim3(N), dim3(64), 0, stream, dev, hp); \
-    else hipLaunchKernelGGL((k_refresh_hier_stats<EE, HIER_CENTERED>), dim3(N), dim3(64), 0, stream, dev, hp);
-    switch (E) {
-    case 1: HIER_REFRESH(1) break; case 2: HIER_REFRESH(2) break; case 4: HIER_REFRESH(4) break; case 8: HIER_REFRESH(8) break;
-    default: return 1;
-    }
-#undef HIER_REFRESH
-    return 0;
+    return with_blocks_per_lane(E, [&](auto e_) {
+        constexpr int EE = decltype(e_)::value;
+        if (param == HIER_NONCENTERED) hipLaunchKernelGGL((k_refresh_hier_stats<EE, HIER_NONCENTERED>), dim3(N), dim3(64), 0, stream, dev, hp);
+        else hipLaunchKernelGGL((k_refresh_hier_stats<EE, HIER_CENTERED>), dim3(N), dim3(64), 0, stream, dev, hp);
+    });
 }
 
 }  // namespace pte

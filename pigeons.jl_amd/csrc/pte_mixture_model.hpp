@@ -14,7 +14,7 @@ namespace pte {
 // two waves per SIMD at least: the accumulators of KB = 8 (3 KB sums of the gradient) stay within 256 registers
 template <int KB, bool SLICE>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 8))) void k_explore_mixture_model(EngineDev e, AmParams ap, MixModelParams mm) {
-    automala_body<1, TGT_MIXMODEL, SLICE, false, false, KB, 0>(e, ap, blockIdx.x, MixParams{}, GlmParams{}, mm);
+    automala_body<1, TGT_MIXMODEL, SLICE, false, false, KB>(e, ap, blockIdx.x, mm);
 }
 
 // swap statistics of every slot recomputed from the stored states (pte_set_state, pte_set_target_mixture_model): suff = sum x^2, suff2 = the
@@ -31,7 +31,7 @@ __global__ __launch_bounds__(64) void k_refresh_mixture_model_stats(EngineDev e,
     double x[1];
     x[0] = T.valid(0) ? e.x[slot * e.ld + lane] : 0.0;
     const double S = sqr_norm_regs<1>(x);
-    const double l2 = T.mixmodel(x);
+    const double l2 = T.target(x);
     if (lane == 0) { e.suff[slot] = S; e.suff2[slot] = l2; }
 }
 

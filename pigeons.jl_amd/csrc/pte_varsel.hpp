@@ -253,31 +253,24 @@ __global__ __launch_bounds__(64) void k_refresh_varsel_stats(EngineDev e, Varsel
 
 int varsel_launch(const VarselLaunch &L, const EngineDev &dev, const AmParams &ap, const VarselParams &vp) {
     const size_t lds = varsel_lds_bytes(L.E, vp.n_pad);
-#define VARSEL_LIK(EE, LL)                                                                          \
-    if (L.full) launch_on(L.at, k_explore_varsel<EE, LL, true>, 64, lds, dev, ap, vp);              \
-    else launch_on(L.at, k_explore_varsel<EE, LL, false>, 64, lds, dev, ap, vp);
-#define VARSEL_ONE(EE)                                                                              \
-    if (L.lik == GLM_NORMAL_IDENTITY) { VARSEL_LIK(EE, GLM_NORMAL_IDENTITY) } else { VARSEL_LIK(EE, GLM_BERNOULLI_LOGIT) }
-    switch (L.E) {
-    case 1: VARSEL_ONE(1) break; case 2: VARSEL_ONE(2) break; case 4: VARSEL_ONE(4) break; case 8: VARSEL_ONE(8) break;
-    default: return 1;
-    }
-#undef VARSEL_ONE
-#undef VARSEL_LIK
-    return 0;
+    return with_blocks_per_lane(L.E, [&](auto e_) {
+        auto go = [&](auto lik_) {
+            constexpr int E = decltype(e_)::value, LIK = decltype(lik_)::value;
+            if (L.full) launch_on(L.at, k_explore_varsel<E, LIK, true>, 64, lds, dev, ap, vp);
+            else launch_on(L.at, k_explore_varsel<E, LIK, false>, 64, lds, dev, ap, vp);
+        };
+        if (L.lik == GLM_NORMAL_IDENTITY) go(std::integral_constant<int, GLM_NORMAL_IDENTITY>{});
+        else go(std::integral_constant<int, GLM_BERNOULLI_LOGIT>{});
+    });
 }
 
 int varsel_refresh_stats(int E, int lik, unsigned N, hipStream_t stream, const EngineDev &dev, const VarselParams &vp, double ref_prec) {
     const size_t lds = varsel_lds_bytes(E, vp.n_pad);
-#define VARSEL_REFRESH(EE)                                                                                                                   \
-    if (lik == GLM_NORMAL_IDENTITY) hipLaunchKernelGGL((k_refresh_varsel_stats<EE, GLM_NORMAL_IDENTITY>), dim3(N), dim3(64), lds, stream, dev, vp, ref_prec); \
-    else hipLaunchKernelGGL((k_refresh_varsel_stats<EE, GLM_BERNOULLI_LOGIT>), dim3(N), dim3(64), lds, stream, dev, vp, ref_prec);
-    switch (E) {
-    case 1: VARSEL_REFRESH(1) break; case 2: VARSEL_REFRESH(2) break; case 4: VARSEL_REFRESH(4) break; case 8: VARSEL_REFRESH(8) break;
-    default: return 1;
-    }
-#undef VARSEL_REFRESH
-    return 0;
+    return with_blocks_per_lane(E, [&](auto e_) {
+        constexpr int EE = decltype(e_)::value;
+        if (lik == GLM_NORMAL_IDENTITY) hipLaunchKernelGGL((k_refresh_varsel_stats<EE, GLM_NORMAL_IDENTITY>), dim3(N), dim3(64), lds, stream, dev, vp, ref_prec);
+        else hipLaunchKernelGGL((k_refresh_varsel_stats<EE, GLM_BERNOULLI_LOGIT>), dim3(N), dim3(64), lds, stream, dev, vp, ref_prec);
+    });
 }
 
 PTE_DEFINE_RNG_POLICY_SETTER(varsel)
