@@ -69,7 +69,7 @@ enum {
                                             pte_set_target_dense): dim in 1..512; SliceSampler / AutoMALA / MALA / Compose of them */
     PTE_TARGET_SPIN_GLASS = 12           /* InterpolatingPath(SpinGlass(0), SpinGlass(beta)): the +-J Edwards-Anderson model, PTE_TARGET_ISING with
                                             quenched bonds (pte_set_target_spin_glass): dim = base_length^2, 2 <= base_length, dim <= 65536;
-                                            target_params[0] = beta; PTE_EXPLORER_ISING_METROPOLIS only */
+                                            target_params[0] = beta; PTE_EXPLORER_ISING_METROPOLIS or PTE_EXPLORER_CHECKERBOARD_METROPOLIS */
 };
 /* PTE_TARGET_LATENT_AR1: the observation model */
 enum {
@@ -99,8 +99,11 @@ enum {
     PTE_EXPLORER_AUTOMALA = 3,           /* AutoMALA:     src/explorers/AutoMALA.jl:29-294                 */
     PTE_EXPLORER_ISING_METROPOLIS = 4,   /* IsingMetropolis: examples/ising.jl:91-116 (n_steps in slice_n_passes) */
     PTE_EXPLORER_MALA     = 5,           /* MALA:         src/explorers/MALA.jl:19-105 (am_* fields; step size fixed) */
-    PTE_EXPLORER_AAPS     = 6            /* AAPS:         src/explorers/AAPS.jl (apogee-to-apogee path sampler; am_step_size, am_preconditioner / am_p0 / am_p1,
+    PTE_EXPLORER_AAPS     = 6,           /* AAPS:         src/explorers/AAPS.jl (apogee-to-apogee path sampler; am_step_size, am_preconditioner / am_p0 / am_p1,
                                             aaps_K; step size fixed; MVN and funnel paths, dim <= 512, single explorer)      */
+    PTE_EXPLORER_CHECKERBOARD_METROPOLIS = 7 /* CheckerboardMetropolis: the two-colour Metropolis sweep of the lattice targets (the project's own
+                                            specification, n_steps in slice_n_passes); PTE_TARGET_ISING and PTE_TARGET_SPIN_GLASS with an even
+                                            base_length, single explorer */
 };
 enum {                                   /* Inputs.record (src/pt/Inputs.jl:57-62)                         */
     PTE_RECORD_ROUND_TRIP    = 1u << 0,  /* round_trip     src/recorders/RoundTripRecorder.jl              */
@@ -127,7 +130,8 @@ enum {                                   /* pte_config.debug_kernel: which kerne
     PTE_KERNEL_SLICE_SEQUENTIAL = 1,     /* SliceSampler: the plain sequential kernel (exact fallback of the default one)  */
     /* 2, 5, 7 (and 8 = the default named explicitly): earlier SliceSampler generations, test build libpte_test.so only    */
     PTE_KERNEL_ISING_BITS       = 101,   /* IsingMetropolis: scalar bit-packed sweep, test build only                      */
-    PTE_KERNEL_ISING_BYTES      = 102,   /* IsingMetropolis: scalar byte-lattice sweep (the kernel of base_length % 32 != 0) */
+    PTE_KERNEL_ISING_BYTES      = 102,   /* IsingMetropolis: scalar byte-lattice sweep (the kernel of base_length % 32 != 0);
+                                            CheckerboardMetropolis: its byte-lattice kernel k_explore_checkerboard_sites           */
     /* a FLAG, or-ed to any of the above: pte_run_scans launches explore and swap per scan (the loop of rounds 1-4) even where the whole
      * call could run as ONE kernel with pairwise swap hand-shakes (pte_scan_loop_name); for A/B runs and the parity tests of the two forms */
     PTE_KERNEL_TWO_LAUNCHES     = 0x1000,

@@ -33,6 +33,7 @@
 #include "pte_varsel_params.hpp"
 #include "pte_changepoint_params.hpp"
 #include "pte_spinglass_params.hpp"
+#include "pte_checkerboard_params.hpp"
 #else                              // tools / development builds: one translation unit
 #include "pte_langevin_launch.hpp"
 #include "pte_aaps.hpp"
@@ -45,6 +46,7 @@
 #include "pte_varsel.hpp"
 #include "pte_changepoint.hpp"
 #include "pte_spinglass.hpp"
+#include "pte_checkerboard.hpp"
 #endif
 #include "pte_ising.hpp"
 #if defined(PTE_PROFILE_AM)               // debug builds only (tools/prof_automala.py): 12 words per wave, section times of k_explore_automala
@@ -637,6 +639,14 @@ int launch_explorer_kind(pte_engine *h, int64_t scan, int kind) {
         time_end(h);
         break;
     }
+    case PTE_EXPLORER_CHECKERBOARD_METROPOLIS: {         // the two-colour sweep of either lattice target (pte_checkerboard.hpp); the Ising target has no bonds: null pointers
+        SpinGlassParams gp = h->cfg.target == PTE_TARGET_SPIN_GLASS ? h->spinglass : SpinGlassParams{};
+        gp.L = (int)std::llround(std::sqrt((double)h->d)); gp.n_steps = h->cfg.slice_n_passes; gp.beta_target = h->cfg.target_params[0];
+        time_begin(h, 0, true);
+        if (checkerboard_launch(CheckerboardLaunch{h->ising_impl == 2, launch_site(h, (unsigned)N)}, h->dev, gp)) return fail(h, "this build holds no checkerboard kernel for dim %lld", (long long)h->d);
+        time_end(h);
+        break;
+    }
     default: return fail(h, "explorer %d is not implemented on the device", h->cfg.explorer);
     }
     HIP_OK(h, hipGetLastError());
@@ -1035,6 +1045,7 @@ int validate_config(const pte_config *cfg) {
     const bool funnel = cfg->target == PTE_TARGET_FUNNEL;
     const bool ising = on_lattice(cfg->target), spin_glass = cfg->target == PTE_TARGET_SPIN_GLASS;
     const PathFamily *family = path_family(cfg->target);
+    const bool checkerboard = cfg->explorer == PTE_EXPLORER_CHECKERBOARD_METROPOLIS || cfg->explorer2 == PTE_EXPLORER_CHECKERBOARD_METROPOLIS;
     if (cfg->explorer == PTE_EXPLORER_AAPS || cfg->explorer2 == PTE_EXPLORER_AAPS) {       // AAPS (pte_aaps.hpp): one wave per replica, one explorer
         if (cfg->explorer2 != PTE_EXPLORER_NONE)
             return fail(nullptr, "pte_create: AAPS is not available as half of a Compose on the device");
@@ -1049,6 +1060,7 @@ int validate_config(const pte_config *cfg) {
         if (cfg->debug_kernel != 0)
             return fail(nullptr, "pte_create: AAPS has one kernel; debug_kernel must be 0 (got %d)", cfg->debug_kernel);
     }
+    if (checkerboard && !ising) return fail(nullptr, "pte_create: CheckerboardMetropolis needs the Ising or the spin-glass target");
     if (cfg->target == PTE_TARGET_VARIABLE_SELECTION) {      // Float64 and Bool coordinates, SliceSampler's two methods and nothing else
         if (cfg->explorer != PTE_EXPLORER_SLICE || cfg->explorer2 != PTE_EXPLORER_NONE)
             return fail(nullptr, "pte_create: the variable-selection path is explored by SliceSampler only -- its Bool coordinates have no gradient, "
@@ -1095,7 +1107,13 @@ int validate_config(const pte_config *cfg) {
         if (cfg->explorer == PTE_EXPLORER_SLICE || cfg->explorer2 == PTE_EXPLORER_SLICE)   // spins are Bool coordinates: SliceSampler.jl:65-86 (and :136-142, :189 for Integer ones)
             return fail(nullptr, "pte_create: SliceSampler's Bool / Integer coordinate methods are not available on the device (its Float64 methods are); "
                                  "the %s path is explored by IsingMetropolis only -- use the reference CPU path for Bool / Integer states", spin_glass ? "spin-glass" : "Ising");
-        if (cfg->explorer != PTE_EXPLORER_ISING_METROPOLIS || (spin_glass && cfg->explorer2 != PTE_EXPLORER_NONE))
+        if (checkerboard) {                                  // a single explorer on an even lattice
+            if (cfg->explorer != PTE_EXPLORER_CHECKERBOARD_METROPOLIS || cfg->explorer2 != PTE_EXPLORER_NONE)
+                return fail(nullptr, "pte_create: CheckerboardMetropolis is not available as half of a Compose on the device (got explorers %d, %d)", cfg->explorer, cfg->explorer2);
+            if (L % 2 != 0)
+                return fail(nullptr, "pte_create: CheckerboardMetropolis needs an even base_length (got %lld): on an odd periodic lattice two sites of one colour "
+                                     "would be neighbours", (long long)L);
+        } else if (cfg->explorer != PTE_EXPLORER_ISING_METROPOLIS || (spin_glass && cfg->explorer2 != PTE_EXPLORER_NONE))
             return fail(nullptr, "pte_create: the %s path is explored by IsingMetropolis only", spin_glass ? "spin-glass" : "Ising");
     } else if (cfg->explorer == PTE_EXPLORER_ISING_METROPOLIS) return fail(nullptr, "pte_create: IsingMetropolis needs the Ising target");
     if (!swapper && !family && !ising && cfg->target != PTE_TARGET_MVN_SCALED_PRECISION)
@@ -1138,7 +1156,7 @@ int validate_config(const pte_config *cfg) {
         const bool slice = cfg->explorer == PTE_EXPLORER_SLICE || cfg->explorer2 == PTE_EXPLORER_SLICE;
         bool ok = dk == 0 || (slice && dk == PTE_KERNEL_SLICE_SEQUENTIAL) || (ising && dk == PTE_KERNEL_ISING_BYTES);
 #ifdef PTE_TEST_KERNELS
-        ok = ok || (slice && (dk == 2 || dk == 5 || dk == 7 || dk == 8)) || (ising && !spin_glass && dk == PTE_KERNEL_ISING_BITS);
+        ok = ok || (slice && (dk == 2 || dk == 5 || dk == 7 || dk == 8)) || (ising && !spin_glass && !checkerboard && dk == PTE_KERNEL_ISING_BITS);
 #endif
         if (!ok) return fail(nullptr, "pte_create: debug_kernel %d is not available for this explorer in this build of libpte "
                                       "(0 = default, %d = sequential SliceSampler kernel; the other generations live in the test build libpte_test.so)",
@@ -1209,7 +1227,7 @@ int pte_create(const pte_config *cfg, pte_engine **out) {
     h->fused_wg_allowed = (cfg->debug_kernel & PTE_KERNEL_SCAN_LOOP_ONE_CHAIN) == 0;
     h->test_fault = (cfg->debug_kernel & PTE_KERNEL_TEST_DEAD_CHAIN) ? 1 : ((cfg->debug_kernel & PTE_KERNEL_TEST_LATE_WORKGROUP) ? 2 : 0);
     if (cfg->explorer == PTE_EXPLORER_SLICE || cfg->explorer2 == PTE_EXPLORER_SLICE) h->slice_impl = dk_kernel == 0 ? 8 : dk_kernel;
-    if (cfg->explorer == PTE_EXPLORER_ISING_METROPOLIS) h->ising_impl = dk_kernel == PTE_KERNEL_ISING_BITS ? 1 : (dk_kernel == PTE_KERNEL_ISING_BYTES ? 2 : 0);
+    if (cfg->explorer == PTE_EXPLORER_ISING_METROPOLIS || cfg->explorer == PTE_EXPLORER_CHECKERBOARD_METROPOLIS) h->ising_impl = dk_kernel == PTE_KERNEL_ISING_BITS ? 1 : (dk_kernel == PTE_KERNEL_ISING_BYTES ? 2 : 0);
     if (alloc_engine(h)) return bail(1);
     default_schedule(h);
     if (upload_ladder(h)) return bail(1);
@@ -2065,6 +2083,10 @@ const char *pte_kernel_name(const pte_engine *h) {
         const int64_t L = (int64_t)std::llround(std::sqrt((double)h->d));
         if (h->cfg.target == PTE_TARGET_SPIN_GLASS) return (L % 32 == 0 && h->ising_impl == 0) ? "k_explore_spinglass_spec" : "k_explore_spinglass";
         return (L % 32 == 0 && h->ising_impl == 0) ? "k_explore_ising_spec" : (L % 32 == 0 && h->ising_impl == 1) ? "k_explore_ising_bits" : "k_explore_ising";
+    }
+    case PTE_EXPLORER_CHECKERBOARD_METROPOLIS: {
+        const int64_t L = (int64_t)std::llround(std::sqrt((double)h->d));
+        return (L % 32 == 0 && h->ising_impl == 0) ? "k_explore_checkerboard" : "k_explore_checkerboard_sites";
     }
     default: return "";
     }

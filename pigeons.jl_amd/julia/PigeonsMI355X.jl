@@ -47,6 +47,7 @@ const TARGET_DENSE_NORMAL = Int32(11)
 const TARGET_SPIN_GLASS = Int32(12)
 const GLM_BERNOULLI_LOGIT, GLM_NORMAL_IDENTITY = Int32(0), Int32(1)
 const EXPLORER_NONE, EXPLORER_TOY, EXPLORER_SLICE, EXPLORER_AUTOMALA, EXPLORER_ISING, EXPLORER_MALA, EXPLORER_AAPS = Int32.((0, 1, 2, 3, 4, 5, 6))
+const EXPLORER_CHECKERBOARD_METROPOLIS = Int32(7)      # the two-colour Metropolis sweep of the lattice targets (DESIGN 4.18)
 const RECORD_ROUND_TRIP, RECORD_INDEX_PROCESS, RECORD_ONLINE, RECORD_TRACES, RECORD_ENERGY_AC1, RECORD_TRACES_EXTENDED =
     UInt32.((1, 2, 4, 8, 16, 32))
 const RECORD_REFERENCE_REDUCTION = UInt32(64)   # swap recorders reduced by per-replica Mean / LogSum fits + tree merge, replayed in pte_reduce (include/pte.h)

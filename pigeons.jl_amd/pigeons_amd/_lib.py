@@ -32,6 +32,7 @@ TARGET_SPIN_GLASS = 12
 CHANGEPOINT_FORM_AUTO, CHANGEPOINT_FORM_FULL, CHANGEPOINT_FORM_CACHED = 0, 1, 2      # pte_set_changepoint_form (include/pte.h PTE_CHANGEPOINT_FORM_*)
 GLM_BERNOULLI_LOGIT, GLM_NORMAL_IDENTITY = 0, 1        # pte_set_target_glm's likelihood (include/pte.h PTE_GLM_*)
 EXPLORER_NONE, EXPLORER_TOY, EXPLORER_SLICE, EXPLORER_AUTOMALA, EXPLORER_ISING_METROPOLIS, EXPLORER_MALA, EXPLORER_AAPS = 0, 1, 2, 3, 4, 5, 6
+EXPLORER_CHECKERBOARD_METROPOLIS = 7      # the two-colour Metropolis sweep of the lattice targets
 RECORD_ROUND_TRIP, RECORD_INDEX_PROCESS, RECORD_ONLINE, RECORD_TRACES, RECORD_ENERGY_AC1, RECORD_TRACES_EXTENDED = 1, 2, 4, 8, 16, 32
 RECORD_REFERENCE_REDUCTION = 64      # swap_acceptance_pr / log_sum_ratio by per-replica Mean / LogSum fits and the binary-tree merge, replayed in pte_reduce (include/pte.h)
 ABI_VERSION = 2

@@ -551,6 +551,13 @@ class IsingMetropolis:
 
 
 @dataclass
+class CheckerboardMetropolis:
+    """The two-colour (red / black) Metropolis sweep of IsingLogPotential and SpinGlassLogPotential (the project's own
+    specification): n_steps sweeps of two half-sweeps each, all sites of a colour decided at once.  base_length must be even."""
+    n_steps: int = 3
+
+
+@dataclass
 class TestSwapper:
     """src/swap/pair_swapper.jl:100-149"""
     constant_swap_accept_pr: float = 1.0
@@ -810,6 +817,9 @@ class PT:
             flags |= _lib.RECORD_REFERENCE_REDUCTION | _lib.RECORD_INDEX_PROCESS
         kw = dict(device=inputs.device, n_chains=N, n_chains_variational=n_var, seed=inputs.seed, record_flags=flags,
                   max_scans_per_round=2 ** inputs.n_rounds)
+        if isinstance(explorer, CheckerboardMetropolis) and isinstance(target, (IsingLogPotential, SpinGlassLogPotential)) and target.base_length % 2 != 0:
+            raise ValueError("CheckerboardMetropolis needs an even base_length (got %d): on an odd periodic lattice two sites of one colour "
+                             "would be neighbours" % target.base_length)
         if isinstance(target, ScaledPrecisionNormalPath):
             kw.update(target=_lib.TARGET_MVN_SCALED_PRECISION, dim=target.dim,
                       target_params=[target.precision0, target.precision1])
@@ -818,7 +828,7 @@ class PT:
         elif isinstance(target, IsingLogPotential):
             kw.update(target=_lib.TARGET_ISING, dim=target.base_length ** 2, target_params=[target.beta])
         elif isinstance(target, SpinGlassLogPotential):
-            if not isinstance(explorer, IsingMetropolis):
+            if not isinstance(explorer, (IsingMetropolis, CheckerboardMetropolis)):
                 raise NotImplementedError("the device spin-glass path is explored by IsingMetropolis only (got %r)" % (explorer,))
             kw.update(target=_lib.TARGET_SPIN_GLASS, dim=target.dim, target_params=[target.beta])
         elif isinstance(target, Funnel):
@@ -885,6 +895,8 @@ class PT:
                             slice_max_iter=ex.max_iter)
             if isinstance(ex, IsingMetropolis):
                 return dict(explorer=_lib.EXPLORER_ISING_METROPOLIS, slice_n_passes=ex.n_steps)
+            if isinstance(ex, CheckerboardMetropolis):
+                return dict(explorer=_lib.EXPLORER_CHECKERBOARD_METROPOLIS, slice_n_passes=ex.n_steps)
             if isinstance(ex, AAPS):
                 pc = ex.preconditioner
                 kind = 0 if isinstance(pc, IdentityPreconditioner) else 1 if isinstance(pc, DiagonalPreconditioner) else 2
