@@ -1,0 +1,249 @@
+"""The case table of the families' explore kernels at four and eight 64-coordinate blocks per lane, defined once and used by
+tests/test_family_blocks_cpu.py (the table's own coverage, the restatements' MALA alone) and tests/test_gpu_family_blocks.py (the device
+against the restatements at one transition).
+
+A Case is (family, variant, mode, d, N, explorer parameters): variant the kernel's LIK or PARAM argument, mode "slice" or "mala", d the
+STATE dimension (hier: J + 2, ar1: T + 3, varsel: twice the number of columns), N the number of replicas.  The data, the schedule, the
+states and the chain permutation of a case are made the way the family's own tests/test_gpu_<family>.py makes them for the same mode (its
+_data / _mixture / _target, imported from there; the seeds derived from the dimension by the same expressions; the body of its
+_random_states restated in layout()).  The RNG words are the engine's own, read back through eng.states(); init_rng_words restates them
+(pte.hip, init_zero_state: an engine on the interpolated path starts at the zero state, replica i holding the i-th split of
+SplittableRandom(seed), no draw made), so that the MALA restatement can run before any device does -- the GPU test asserts the two are
+equal.
+
+Dimensions: 129 / 130 (four blocks: block 2 holds one or two coordinates, block 3 none), 256 (four whole blocks), 257 (eight blocks: block
+4 holds one coordinate, blocks 5 to 7 none; varsel's state is even: 258), 512 (eight whole blocks); varsel also 128 (two whole blocks).
+Replicas: 6, but 3 (two off the reference chain) for the SliceSampler cases of dense and glm at 512, where a pass of the restatement
+takes several seconds a replica, against well under a second elsewhere."""
+import math
+
+import numpy as np
+
+import aaps_ref
+import ar1_ref
+import dense_ref
+import glm_ref
+import hier_ref
+import mixture_ref
+import oracle as O
+import varsel_ref
+from test_gpu_ar1 import LIK as AR1_LIK, PRIORS as AR1_PRIORS, _data as ar1_data
+from test_gpu_dense import _target as dense_target
+from test_gpu_glm import _data as glm_data
+from test_gpu_hier import PARAM as HIER_PARAM, _data as hier_data
+from test_gpu_mixture import _mixture as mixture_data
+from test_gpu_varsel import _data as varsel_data
+
+SLICE = dict(w=10.0, p=20, n_passes=1)
+PRECOND_MODE = {"identity": 0, "diagonal": 1, "mix": 2}
+ENGINE_SEED = 1                                      # pigeons_amd.Inputs.seed's default: the tests of the families leave it alone
+HIER_HYPER = dict(mu_sd=2.0, tau_scale=1.5)          # tests/test_gpu_hier.py, _pt
+
+
+class Case:
+    def __init__(self, family, variant, mode, d, N, **kw):
+        self.family, self.variant, self.mode, self.d, self.N, self.kw = family, variant, mode, int(d), int(N), kw
+        self.id = "-".join(str(v) for v in (family, variant, mode, "d%d" % d) if v is not None)
+
+    def __repr__(self):
+        return self.id
+
+
+def _slice(family, variant, d, N=6, **kw):
+    return Case(family, variant, "slice", d, N, **SLICE, **kw)
+
+
+def _mala(family, variant, d, precond, step, seen, **kw):
+    """seen: (proposals accepted, rejected) by the restatement alone on the CPU at this step, over the N - 1 replicas off the reference"""
+    return Case(family, variant, "mala", d, 6, precond=precond, step=step, seen=seen, **kw)
+
+
+# ---- SliceSampler, one pass ------------------------------------------------------------------------------------------------------------
+# glm and varsel: n <= 20 observations (the restatement's cost grows with d, hardly with n)
+SLICE_CASES = [
+    _slice("glm", "bernoulli_logit", 130, n=20), _slice("glm", "normal_identity", 130, n=17),
+    _slice("glm", "bernoulli_logit", 257, n=17), _slice("glm", "normal_identity", 257, n=20),
+    _slice("glm", "bernoulli_logit", 512, N=3, n=20),
+    _slice("hier", "c", 130), _slice("hier", "nc", 130), _slice("hier", "c", 257), _slice("hier", "nc", 257),
+    _slice("hier", "c", 512), _slice("hier", "nc", 512),
+    _slice("ar1", "sv", 130), _slice("ar1", "n", 130), _slice("ar1", "sv", 257), _slice("ar1", "n", 257),
+    _slice("ar1", "sv", 512), _slice("ar1", "n", 512),
+    _slice("mixture", None, 130, K=2), _slice("mixture", None, 257, K=8), _slice("mixture", None, 512, K=4),      # one bucket of K each
+    _slice("dense", None, 130), _slice("dense", None, 256), _slice("dense", None, 257), _slice("dense", None, 512, N=3),
+    _slice("varsel", "bernoulli_logit", 128, n=20, pi=0.5), _slice("varsel", "normal_identity", 128, n=17, pi=0.3),
+    _slice("varsel", "bernoulli_logit", 130, n=17, pi=0.2), _slice("varsel", "normal_identity", 130, n=20, pi=0.5),
+    _slice("varsel", "bernoulli_logit", 256, n=20, pi=0.3), _slice("varsel", "normal_identity", 256, n=17, pi=0.2),
+    _slice("varsel", "bernoulli_logit", 258, n=17, pi=0.5), _slice("varsel", "normal_identity", 258, n=20, pi=0.3),
+    _slice("varsel", "bernoulli_logit", 512, n=20, pi=0.2), _slice("varsel", "normal_identity", 512, n=17, pi=0.5),
+]
+
+# ---- MALA ------------------------------------------------------------------------------------------------------------------------------
+# the steps were chosen on the restatements alone (tests/test_family_blocks_cpu.py repeats the count): each case accepts some proposals
+# and rejects others
+MALA_CASES = [
+    _mala("glm", "bernoulli_logit", 129, "identity", 0.5, (62, 28), n=20), _mala("glm", "bernoulli_logit", 256, "diagonal", 0.3, (70, 35), n=17),
+    _mala("glm", "bernoulli_logit", 257, "mix", 0.5, (33, 72), n=20), _mala("glm", "bernoulli_logit", 512, "diagonal", 0.3, (51, 84), n=17),
+    _mala("glm", "normal_identity", 129, "diagonal", 0.3, (74, 16), n=17), _mala("glm", "normal_identity", 256, "mix", 0.5, (21, 84), n=20),
+    _mala("glm", "normal_identity", 257, "identity", 0.5, (58, 47), n=17), _mala("glm", "normal_identity", 512, "mix", 0.3, (70, 65), n=20),
+    _mala("hier", "c", 129, "mix", 0.1, (39, 51)), _mala("hier", "c", 256, "identity", 0.05, (79, 26)),
+    _mala("hier", "c", 257, "diagonal", 0.05, (27, 78)), _mala("hier", "c", 512, "mix", 0.05, (88, 47)),
+    _mala("hier", "nc", 129, "identity", 0.15, (76, 14)), _mala("hier", "nc", 256, "diagonal", 0.1, (23, 82)),
+    _mala("hier", "nc", 257, "mix", 0.1, (61, 44)), _mala("hier", "nc", 512, "identity", 0.1, (79, 56)),
+    _mala("ar1", "sv", 129, "diagonal", 0.1, (23, 67)), _mala("ar1", "sv", 256, "mix", 0.05, (46, 59)),
+    _mala("ar1", "sv", 257, "identity", 0.1, (25, 80)), _mala("ar1", "sv", 512, "diagonal", 0.1, (55, 80)),
+    _mala("ar1", "n", 129, "mix", 0.1, (38, 52)), _mala("ar1", "n", 256, "identity", 0.1, (16, 89)),
+    _mala("ar1", "n", 257, "diagonal", 0.05, (55, 50)), _mala("ar1", "n", 512, "identity", 0.1, (52, 83)),
+    _mala("mixture", None, 129, "identity", 0.6, (69, 21), K=2), _mala("mixture", None, 256, "diagonal", 0.3, (81, 24), K=4),
+    _mala("mixture", None, 257, "mix", 0.4, (76, 29), K=8), _mala("mixture", None, 512, "diagonal", 0.3, (104, 31), K=3),
+    _mala("dense", None, 129, "diagonal", 0.4, (55, 35)), _mala("dense", None, 256, "mix", 0.4, (35, 70)),
+    _mala("dense", None, 257, "identity", 0.4, (41, 64)), _mala("dense", None, 512, "mix", 0.4, (32, 103)),
+]
+
+CASES = SLICE_CASES + MALA_CASES
+assert len(set(c.id for c in CASES)) == len(CASES)
+
+# ---- the refresh kernels that no family's test_log_density_at_every_beta visits: (family, variant, state dimension, parameters) ---------
+LOG_DENSITY_CASES = [
+    Case("glm", "bernoulli_logit", "lp", 100, 8, n=40),              # k_refresh_glm_stats<2>
+    Case("glm", "normal_identity", "lp", 200, 8, n=30),              # <4>
+    Case("mixture", None, "lp", 200, 8, K=3),                        # k_refresh_mixture_stats<4>
+    Case("varsel", "normal_identity", "lp", 200, 8, n=40, pi=0.3),   # k_refresh_varsel_stats<4>
+    Case("varsel", "bernoulli_logit", "lp", 400, 8, n=30, pi=0.5),   # <8>, ragged
+]
+
+
+# ---- a case's model --------------------------------------------------------------------------------------------------------------------
+class Model:
+    """restatement: the family's target of tests/<family>_ref.py; chain(beta): one chain of it; device(P): the pigeons_amd target and the
+    dimension of its reference; ref_prec; kinds: oracle.COORD_* per coordinate"""
+
+    def __init__(self, restatement, chain_type, ref_prec, device, kinds):
+        self.restatement, self.chain_type, self.ref_prec, self.device, self.kinds = restatement, chain_type, ref_prec, device, kinds
+
+    def chain(self, beta):
+        return self.chain_type(self.restatement, float(beta), self.ref_prec)
+
+
+_MODELS = {}
+
+
+def model(case):
+    """(built once per case) -- data seeds and the reference's precision as the family's own test of this mode: SliceSampler and the log
+    density at precision 0.5 (mixture's log density: 0.25), MALA at 1"""
+    if case.id in _MODELS:
+        return _MODELS[case.id]
+    f, v, d, mala, lp = case.family, case.variant, case.d, case.mode == "mala", case.mode == "lp"
+    prec = 1.0 if mala else 0.5
+    kinds = np.zeros(d, dtype=np.int32)
+    if f == "glm":
+        n = case.kw["n"]
+        sd = 0.8 if lp else 1.0
+        X, y = glm_data(n, d, v, seed=(n + d) if lp else (3 * n + d) if mala else 7 * n + d, noise_sd=sd)
+        m = Model(glm_ref.Glm(X, y, v, sd, prec), glm_ref.GlmChain, prec, lambda P: (P.BayesianGLM(X, y, likelihood=v, noise_sd=sd), d), kinds)
+    elif f == "hier":
+        J = d - 2
+        y, s = hier_data(J, seed=3 * J if mala else 7 * J)
+        m = Model(hier_ref.Hier(y, s, HIER_HYPER["mu_sd"], HIER_HYPER["tau_scale"], HIER_PARAM[v]), hier_ref.HierChain, prec,
+                  lambda P: (P.HierarchicalNormalMeans(y, s, parameterization=HIER_PARAM[v], **HIER_HYPER), d), kinds)
+    elif f == "ar1":
+        y = ar1_data(d - 3, v, seed=3 * d if mala else 7 * d)
+        m = Model(ar1_ref.Ar1(y, AR1_LIK[v], **AR1_PRIORS), ar1_ref.Ar1Chain, prec,
+                  lambda P: (P.LatentAR1(y, likelihood=AR1_LIK[v], **AR1_PRIORS), d), kinds)
+    elif f == "mixture":
+        K = case.kw["K"]
+        prec = 0.25 if lp else prec
+        w, mu, sd = mixture_data(K, d, seed=K + d) if lp else mixture_data(K, d, seed=3 * K + d, spread=1.0) if mala else mixture_data(K, d, seed=7 * K + d)
+        m = Model(mixture_ref.Mixture(w, mu, sd), mixture_ref.MixtureChain, prec, lambda P: (P.GaussianMixture(w, mu, sd), d), kinds)
+    elif f == "dense":
+        mean, Q = dense_target(d, 3 * d if mala else 7 * d)
+        mean = 0.3 * mean if mala else mean
+        m = Model(dense_ref.Dense(mean, Q), dense_ref.DenseChain, prec, lambda P: (P.DenseNormal(mean, Q), d), kinds)
+    elif f == "varsel":
+        n, pi, cols = case.kw["n"], case.kw["pi"], d // 2
+        sd = 0.8 if lp else 1.0
+        X, y = varsel_data(n, cols, v, seed=(n + cols) if lp else 7 * n + cols, noise_sd=sd)
+        kinds = np.array([O.COORD_FLOAT64] * cols + [O.COORD_BOOL] * cols, dtype=np.int32)
+        m = Model(varsel_ref.VarSel(X, y, v, sd, prec, pi), varsel_ref.VarSelChain, prec,
+                  lambda P: (P.SpikeSlabRegression(X, y, likelihood=v, noise_sd=sd, inclusion_prob=pi), cols), kinds)
+    else:
+        raise KeyError(f)
+    _MODELS[case.id] = m
+    return m
+
+
+# the seed and the scale of _random_states in the family's own test of this mode
+_STATE_SEED = {
+    ("glm", "slice"): lambda c: (c.kw["n"], 1.0), ("glm", "mala"): lambda c: (c.d, 0.5), ("glm", "lp"): lambda c: (c.d, 0.5),
+    ("hier", "slice"): lambda c: (c.d - 2, 1.0), ("hier", "mala"): lambda c: (c.d, 0.5),
+    ("ar1", "slice"): lambda c: (c.d, 1.0), ("ar1", "mala"): lambda c: (c.d, 0.5),
+    ("mixture", "slice"): lambda c: (c.kw["K"], 1.5), ("mixture", "mala"): lambda c: (c.d, 1.0), ("mixture", "lp"): lambda c: (c.d, 1.5),
+    ("dense", "slice"): lambda c: (c.d, 1.0), ("dense", "mala"): lambda c: (c.d, 0.5),
+    ("varsel", "slice"): lambda c: (c.kw["n"], 1.0), ("varsel", "lp"): lambda c: (c.d // 2, 0.5),
+}
+
+
+def layout(case):
+    """(betas, x, chain): _random_states of the families' tests -- the schedule 0, sorted uniforms, 1; states N(0, scale^2) (varsel: the
+    thetas, then fair coins); a random chain permutation"""
+    seed, scale = _STATE_SEED[(case.family, case.mode)](case)
+    N, d = case.N, case.d
+    g = np.random.default_rng(seed)
+    betas = np.concatenate([[0.0], np.sort(g.uniform(0.0, 1.0, N - 2)), [1.0]])
+    if case.family == "varsel":
+        x = np.concatenate([g.normal(0.0, scale, (N, d // 2)), (g.uniform(size=(N, d // 2)) < 0.5).astype(float)], axis=1)
+    else:
+        x = g.normal(0.0, scale, (N, d))
+    chain = g.permutation(N).astype(np.int64)
+    return betas, x, chain
+
+
+def init_rng_words(N, seed=ENGINE_SEED):
+    """the RNG words of a new engine's replicas on the interpolated path: the i-th split of SplittableRandom(seed)"""
+    root = O.OracleRng(seed=seed)
+    return np.array([root.split().state for _ in range(N)], dtype=np.uint64)
+
+
+def target_std(case):
+    """set_explorer_adaptation's standard deviations, as the family's MALA test draws them"""
+    lo, hi = (0.7, 1.4) if case.family == "dense" else (0.5, 2.0)
+    return np.random.default_rng(case.d).uniform(lo, hi, case.d)
+
+
+def n_refresh(d, base=3, exponent=0.35):
+    """MALA's defaults (pigeons_amd.MALA.base_n_refresh, exponent_n_refresh)"""
+    return base * int(math.ceil(d ** exponent))
+
+
+def mala_reference(case, betas, x, chain, rng):
+    """the restatement's MALA transition of every replica off the reference chain, refresh by refresh as tests/test_gpu_dense.py runs it
+    -> ({replica: dict(x, words, acc_sum)}, proposals accepted, rejected)"""
+    m, d, step = model(case), case.d, case.kw["step"]
+    std, nr = target_std(case), n_refresh(case.d)
+    out, accepted, rejected = {}, 0, 0
+    for i in range(case.N):
+        c = int(chain[i])
+        if c == 0:
+            continue
+        r = O.OracleRng(state=(int(rng[i, 0]), int(rng[i, 1])))
+        Mv = aaps_ref.build_preconditioner(r, d, PRECOND_MODE[case.kw["precond"]], 1.0 / 3.0, 1.0 / 3.0, std)
+        ch = m.chain(betas[c])
+        xc, acc_sum = x[i].copy(), 0.0
+        for _ in range(nr):                              # (the density and gradient at the start are pure functions of the state: the same bits)
+            res = mixture_ref.mala_transition(xc, r, ch, step, 1, Mv)
+            took = not np.array_equal(res["x"], xc)
+            accepted += int(took)
+            rejected += int(not took)
+            xc, acc_sum = res["x"], acc_sum + res["acc_sum"]
+        out[i] = dict(x=xc, words=r.state, acc_sum=acc_sum)
+    return out, accepted, rejected
+
+
+def slice_reference(case, beta, x, words):
+    """one SliceSampler step of the oracle on the restatement's path_lp -> (state, RNG words, statistics); a new chain per step (varsel's
+    holds the cached predictor)"""
+    m = model(case)
+    r = O.OracleRng(state=(int(words[0]), int(words[1])))
+    sl = O.MixedSliceSampler(m.chain(beta).path_lp, m.kinds, w=case.kw["w"], p=case.kw["p"], n_passes=case.kw["n_passes"])
+    y = np.array(x, dtype=np.float64)
+    sl.step(r, y)
+    return y, r.state, sl.stats
