@@ -344,6 +344,30 @@ __device__ inline double randexp_from_raw(SeqRng &r, uint64_t raw) {
     }
 }
 __device__ inline double randexp_seq(SeqRng &r) { return randexp_from_raw(r, r.next()); }
+// The same procedure for a kernel that enters it from inside a hot loop (pte_slice8.hpp, round 10), where two things about the form above cost a
+// lone wave more than the arithmetic does.  (1) zig_tail_neglog reads g_rng_policy, a loop-invariant global load which hipcc hoists out of the
+// candidate loop to the ENTRY of the path -- an address load, a vector-memory round trip and a wait on every entry, for a word only the tail
+// (idx == 0: ~3e-4 of the draws) looks at.  Here the word comes from `policy()`, called on the tail branch and nowhere else: the caller keeps
+// its own copy (read once per explore step; the host writes the word only between launches) and makes the read one the compiler cannot move.
+// (2) The table words of a candidate were fetched in two dependent trips, ZIG_FE only behind the compare on ZIG_KE.  The layer is known from
+// the raw draw, so all of them are requested together and waited for once (the empty statement pins them in scalar registers at one point:
+// hipcc otherwise sinks the ZIG_FE loads back behind the compare).  Same values, same operations in the same order: bit-identical draws.
+__device__ __forceinline__ double zig_tail_neglog(double u, unsigned policy) { return (policy & PTE_RNG_TAIL_LOG1P) ? -log1p(-u) : -log(u); }
+template <class PolicyFn>
+__device__ __forceinline__ double randexp_from_raw_hot(SeqRng &r, uint64_t raw, PolicyFn policy) {
+    for (;;) {
+        const uint64_t ri = raw & MASK52;
+        const int idx = (int)(ri & 0xFF);
+        double we = ZIG_WE[idx], f1 = ZIG_FE[idx], f0 = ZIG_FE[(idx - 1) & 0xFF];      // (idx == 0 never uses f0: any entry inside the table will do)
+        uint64_t ke = ZIG_KE[idx];
+        asm volatile("" : "+s"(we), "+s"(ke), "+s"(f0), "+s"(f1));
+        const double x = (double)ri * we;
+        if (ri < ke) return x;
+        if (idx == 0) return ZIG_EXP_R + zig_tail_neglog(r.rand(), policy());
+        if ((f0 - f1) * r.rand() + f1 < exp(-x)) return x;
+        raw = r.next();
+    }
+}
 
 // ---- wave-parallel block of normals in the reference's sequential draw order -------------------
 // Produces randn #0..n_valid-1 of the stream (lane l gets output l) and advances `r` exactly as

@@ -75,12 +75,16 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
     // One struct so that the uniforms sit at LDS offset 0: the nine shrinkage draws of a hypothesis (ds_read2_b64: 8-bit offsets in units
     // of 8 bytes) and its head draws then need no address arithmetic beyond the lane's own index -- seven v_add_u32 per round
     // less, five of them between the doubling steps and the shrinkage block (round 4)
+    // (the many-replica twin has no LDS to spare -- its 10240 bytes are what lets a CU hold 16 replicas -- and four waves per SIMD to hide a memory
+    // round trip behind: its slow path reads the policy word as every other kernel does)
+    constexpr bool HOLD_POLICY = (WIN == 512);
     __shared__ struct {
         double u[WIN];
         double e[WIN];                       // randexp fast-path value; NaN <=> slow path needed
         double x[BLK];                       // the current block: start-of-pass values, overwritten as coordinates retire
         double we[256];
         unsigned long long ke[256];
+        unsigned policy[HOLD_POLICY ? 2 : 0];        // round 10: g_rng_policy as it stands at the head of the explore step (8 bytes: 14344 of LDS in all)
     } sm;
     double (&s_u)[WIN] = sm.u; double (&s_e)[WIN] = sm.e; double (&s_x)[BLK] = sm.x; double (&s_we)[256] = sm.we; unsigned long long (&s_ke)[256] = sm.ke;
     const int lane = lane_id();
@@ -88,6 +92,17 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
     const uint64_t wave_t0 = __builtin_amdgcn_s_memrealtime();
 #endif
     for (int i = lane; i < 256; i += 64) { s_we[i] = ZIG_WE[i]; s_ke[i] = ZIG_KE[i]; }
+    // Round 10.  The policy word (ziggurat-tail formula), read here among the prologue's other global loads and kept in LDS: lane 0's slow-path exponential
+    // and the exact sequential procedure consult it on the ziggurat TAIL only, by a read hipcc may not move (volatile) -- the shared helper's
+    // load of g_rng_policy was hoisted to the entry of both paths, a vector-memory round trip on every entry.
+    if constexpr (HOLD_POLICY) sm.policy[0] = g_rng_policy;
+    const auto exp_seq = [&](SeqRng &rs) __attribute__((always_inline)) -> double {
+        if constexpr (HOLD_POLICY)
+            return randexp_from_raw_hot(rs, rs.next(), [&]() __attribute__((always_inline)) -> unsigned {
+                return (unsigned)__builtin_amdgcn_readfirstlane((int)*(const volatile __attribute__((address_space(3))) unsigned *)&sm.policy[0]); });
+        else
+            return randexp_seq(rs);
+    };
     __syncthreads();
     if (cl >= e.K) return;
     const int64_t c = e.c0 + cl;
@@ -170,6 +185,9 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
             const uint64_t ri = r & MASK52;
             const int idx = (int)(ri & 0xFF);
             const bool fast = ri < s_ke[idx];
+            // (Round 10 built the pre-scaled table -- s_we[i] = ZIG_WE[i] * 2^52, ev = u * s_we[idx] with the u of the next line, bit-identical, four
+            // VALU per draw less: 1709 -> 1561 cycles per refill -- and measured 0.6001-0.6037 against 0.6002-0.6040 ms per scan without it: not a
+            // gain that can be told from the noise, so the refill stays as it was.  profiles/r10_slice8_summary.txt)
             const double ev = (double)ri * s_we[idx];
             s_u[i] = u52_to_unit(r);
             s_e[i] = fast ? ev : __longlong_as_double(0x7ff8000000000000LL);
@@ -194,7 +212,7 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
     int steps_n = 0, acc_sum = 0, acc_n = 0, n_fb = 0;
     int err = 0, err_coord = -1;
 #ifdef PTE_PROFILE_SECTIONS
-    long long prof[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    long long prof[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};      // 16-19 (round 10): cycles and entries of the window refill and of lane 0's slow-path head exponential
 #endif
 
     for (int pass = 0; pass < sp.n_passes && !err; ++pass) {
@@ -211,7 +229,7 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
             // branches of the restructured tail cost more than the ~55 exposed cycles of the round trip.)
             do {                                                   // (nl >= 1; one back edge, the refill out of line: a taken branch costs a lone wave ~35 cycles)
                 PROF_T(t0);
-                if (__builtin_expect(p > REFILL_AT, 0)) { wseed += (uint64_t)p * gamma; fill_window(); Sest = Sest * (1.0 + 1e-6) + wsum * inv_abs_nhp; }
+                if (__builtin_expect(p > REFILL_AT, 0)) { PROF_T(tr0); wseed += (uint64_t)p * gamma; fill_window(); Sest = Sest * (1.0 + 1e-6) + wsum * inv_abs_nhp; PROF_T(tr1); PROF_ADD(16, tr1 - tr0); PROF_ADD(17, 1); }
                 // ================= speculative round: lane = hypothesis (l + hg, p + hrel) ==========
                 // Decisions are sign tests of d(v) = v^2 - Q; every tested |d| is folded into dmin and the
                 // hypothesis is valid only if dmin clears the margin at the end (so the loops carry no
@@ -248,8 +266,9 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                 if (__builtin_expect((slow_b & 1u) != 0u, 0)) {
                     // the certain hypothesis needs the ziggurat's slow path for its exponential (2.3 % of the coordinates):
                     // evaluate it exactly at its stream position; its other draws follow `ex0` positions later
+                    PROF_T(ts0);
                     SeqRng rs{wseed + (uint64_t)p * gamma, gamma};
-                    const double Ex = randexp_seq(rs);
+                    const double Ex = exp_seq(rs);
                     const int used = (int)((rs.seed - (wseed + (uint64_t)p * gamma)) * gamma_inv);
                     if (used <= 17) {
                         ex0 = used - 1;
@@ -260,6 +279,10 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
 #pragma unroll
                         for (int it = 0; it < S8_BD; ++it) Vd[it] = s_u[idx0 + 2 + it];
                     }
+#ifdef PTE_PROFILE_SECTIONS
+                    asm volatile("" :: "v"(E), "v"(u0), "v"(Vd[S8_BD - 1]), "v"(Sest));
+#endif
+                    PROF_T(ts1); PROF_ADD(18, ts1 - ts0); PROF_ADD(19, 1);
                 }
                 // Round 7: every slice test of the round is ONE fused operation, d = fma(v, v, -Q) = RN(v^2 - Q), where it used to be
                 // RN(RN(v^2) - Q) in two (the build uses -ffp-contract=off: the fusion is spelled out).  Only the sign of d is used, and only
@@ -881,7 +904,7 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                     }
                     const double X = s_x[64 * ck + lane];
                     const double xo = readlane_f64(X, li);
-                    const double E = randexp_seq(rs);
+                    const double E = exp_seq(rs);
                     const double u0 = rs.rand();
                     const double Q = xo * xo - E * inv_nhp;
                     const double mg = 1e-12 * (Sest + fabs(Q));
@@ -978,7 +1001,7 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
         e.expl_steps_sum[cl] += (double)steps_sum; e.expl_steps_n[cl] += steps_n;
         e.expl_acc_sum[cl] += (double)acc_sum;     e.expl_acc_n[cl] += acc_n;
 #ifdef PTE_PROFILE_SECTIONS
-        for (int i = 0; i < 16; ++i) e.on_m2[16 * cl + i] += (double)prof[i];   // debug builds only (needs d >= 16K)
+        for (int i = 0; i < 20; ++i) e.on_m2[20 * cl + i] += (double)prof[i];   // debug builds only (needs d >= 20 K: tools/prof_sections7.py reads the slots back through the online variance)
 #endif
     }
     record_after_explore(e, cl, c, slot, lane, lp_before, S, 0.0);

@@ -14,7 +14,7 @@ _lib.LIB_PATH = lib
 DK = int(os.environ.get("S_IMPL", "7"))
 import numpy as np
 import pigeons_amd as P
-N, d = (64 if os.environ.get('S_IMPL') == '8' else 128), 1024
+N, d = (48 if os.environ.get('S_IMPL') == '8' else 128), 1024          # (the slots come back through the d online-variance words: 20 x 48 <= 1024)
 pt = P.PT(P.Inputs(target=P.toy_mvn_target(d), n_chains=N, n_rounds=10, explorer=P.SliceSampler(), show_report=False,
                    record=[P.online, P.log_sum_ratio]))
 assert DK in (7, 8)
@@ -24,14 +24,16 @@ scans = 8
 pt.replicas.run_scans(1, scans)
 pt.replicas.reduce()
 m, v, n = pt.replicas.online()
-W_ = 16 if os.environ.get('S_IMPL') == '8' else 8
+W_ = 20 if os.environ.get('S_IMPL') == '8' else 8          # slice8: 16 slots + (round 10) refill cycles / entries, slow-path head exponential cycles / entries
 cnt = (v * (n - 1)).reshape(-1)[:W_ * N].reshape(N, W_) / scans
 names = ["head_dbl", "shrink", "accept", "rounds", "coords_spec", "chase", "fallbacks", "fallback_cyc"]
-for ch in ((1, 16, 32, 48, 63) if N == 64 else (1, 32, 64, 127)):
+for ch in ((1, 12, 24, 36, 47) if N == 48 else (1, 32, 64, 127)):
     c = cnt[ch]
     tot = c[0] + c[1] + c[2] + c[5] + c[7]
     print("chain %3d: total %.2fM | " % (ch, tot / 1e6) + "  ".join("%s %.0f" % (nm, x) for nm, x in zip(names, c)))
     print("   per round: head+doubling %.0f  shrink %.0f  accept %.0f  chase %.0f cyc; coords/round %.2f; fallbacks %.0f at %.0f cyc each"
           % (c[0] / c[3], c[1] / c[3], c[2] / c[3], c[5] / c[3], c[4] / c[3], c[6], c[7] / max(c[6], 1)))
-    if W_ == 16:
+    if W_ == 20:
         print("   rounds ending: all 5 levels %.0f | slow-path E %.0f, doubling over budget / ends inside %.0f, no proposal inside within the budget %.0f, acceptance check %.0f, sliver %.0f, successor outside its window %.0f, end of block %.0f" % tuple(c[8:16]))
+        print("   cold blocks inside the round (their cycles are part of head+doubling): window refill %.0f entries, %.0f cyc each, %.2f %% of the total | lane 0's slow-path head exponential %.0f entries, %.0f cyc each, %.2f %% of the total"
+              % (c[17], c[16] / max(c[17], 1), 100 * c[16] / tot, c[19], c[18] / max(c[19], 1), 100 * c[18] / tot))
