@@ -1,8 +1,9 @@
 """The case table of the families' explore kernels at four and eight 64-coordinate blocks per lane, defined once and used by
-tests/test_family_blocks_cpu.py (the table's own coverage, the restatements' MALA alone) and tests/test_gpu_family_blocks.py (the device
-against the restatements at one transition).
+tests/test_family_blocks_cpu.py (the table's own coverage, the restatements' MALA and AutoMALA alone) and tests/test_gpu_family_blocks.py
+(the device against the restatements at one transition).
 
-A Case is (family, variant, mode, d, N, explorer parameters): variant the kernel's LIK or PARAM argument, mode "slice" or "mala", d the
+A Case is (family, variant, mode, d, N, explorer parameters): variant the kernel's LIK or PARAM argument, mode "slice", "mala" or "automala"
+(which takes the MALA mode's data, states and standard deviations), d the
 STATE dimension (hier: J + 2, ar1: T + 3, varsel: twice the number of columns), N the number of replicas.  The data, the schedule, the
 states and the chain permutation of a case are made the way the family's own tests/test_gpu_<family>.py makes them for the same mode (its
 _data / _mixture / _target, imported from there; the seeds derived from the dimension by the same expressions; the body of its
@@ -21,6 +22,7 @@ import numpy as np
 
 import aaps_ref
 import ar1_ref
+import automala_ref
 import dense_ref
 import glm_ref
 import hier_ref
@@ -99,8 +101,69 @@ MALA_CASES = [
     _mala("dense", None, 257, "identity", 0.4, (41, 64)), _mala("dense", None, 512, "mix", 0.4, (32, 103)),
 ]
 
+# ---- AutoMALA --------------------------------------------------------------------------------------------------------------------------
+# The eight (family, variant) pairs of MALA_CASES at d = 129, 256, 257, 512 with the MALA case's data, states, n, K and standard deviations,
+# base_n_refresh = 1 (6 refreshes at 129, 7 at 256 and 257, 9 at 512), each in one regime:
+#   tuned   the MALA case's step, scan 2        grow    step 2^-12, scan 2: every search grows
+#   shrink  step 2^8, scan 2: every search shrinks (hier-c and both ar1: through non-finite trials)
+#   scan1   the tuned step, scan 1: no reversed search, no MH step -- the chain stays where the proposal ended
+# Every pair meets every regime, every regime every dimension and every preconditioner.  Regime and preconditioner of a cell were chosen on
+# the restatement alone, from the engine's own RNG words, among those in which it meets the conditions of tests/test_family_blocks_cpu.py
+# (at 256 and 257 the hierarchical and AR(1) cases pass or accept nothing under several of the twelve choices): pair k at the j-th
+# dimension takes regime (k + j) mod 4 and the MALA case's preconditioner where that does.
+# seen: what the restatement makes of the case over the 5 replicas off the reference chain -- (proposals accepted, rejected, reversibility
+# checks passed, failed, least and largest exponent of any search, non-finite trials, replicas moved); margin: the least distance of any
+# of its decisions from going the other way (tests/automala_ref.py).  tests/test_family_blocks_cpu.py recomputes both.
+AUTOMALA_REGIMES = ("tuned", "grow", "shrink", "scan1")
+AUTOMALA_DIMS = (129, 256, 257, 512)
+AUTOMALA_BASE_N_REFRESH = 1
+
+
+def _automala(family, variant, d, regime, precond, seen, margin):
+    (m,) = [c for c in MALA_CASES if (c.family, c.variant, c.d) == (family, variant, d)]
+    step = {"grow": 2.0 ** -12, "shrink": 2.0 ** 8}.get(regime, m.kw["step"])
+    kw = {k: v for k, v in m.kw.items() if k not in ("step", "seen", "precond")}
+    return Case(family, variant, "automala", d, 6, regime=regime, precond=precond, step=step, scan=1 if regime == "scan1" else 2, seen=seen,
+                margin=margin, **kw)
+
+
+AUTOMALA_CASES = [
+    _automala("glm", "bernoulli_logit", 129, "tuned", "identity", (14, 16, 23, 7, -1, 1, 0, 4), 8.11e-04),
+    _automala("glm", "bernoulli_logit", 256, "grow", "diagonal", (9, 26, 15, 20, 9, 11, 0, 4), 3.75e-03),
+    _automala("glm", "bernoulli_logit", 257, "shrink", "diagonal", (8, 27, 9, 26, -11, -9, 0, 4), 5.18e-03),
+    _automala("glm", "bernoulli_logit", 512, "scan1", "mix", (0, 0, 0, 0, -1, 0, 0, 5), 6.92e-03),
+    _automala("glm", "normal_identity", 129, "grow", "diagonal", (15, 15, 16, 14, 9, 11, 0, 5), 5.41e-03),
+    _automala("glm", "normal_identity", 256, "shrink", "mix", (8, 27, 17, 18, -11, -8, 0, 5), 2.11e-03),
+    _automala("glm", "normal_identity", 257, "scan1", "identity", (0, 0, 0, 0, -1, 0, 0, 5), 4.32e-03),
+    _automala("glm", "normal_identity", 512, "tuned", "mix", (12, 33, 21, 24, -1, 1, 0, 4), 6.08e-03),
+    _automala("hier", "c", 129, "shrink", "mix", (9, 21, 13, 17, -14, -10, 366, 3), 4.70e-03),
+    _automala("hier", "c", 256, "scan1", "diagonal", (0, 0, 0, 0, -2, 0, 0, 5), 4.13e-02),
+    _automala("hier", "c", 257, "tuned", "identity", (3, 32, 3, 32, -3, 1, 0, 1), 1.67e-02),
+    _automala("hier", "c", 512, "grow", "mix", (4, 41, 4, 41, 4, 10, 0, 2), 4.82e-04),
+    _automala("hier", "nc", 129, "tuned", "identity", (5, 25, 6, 24, -2, 2, 0, 2), 8.43e-04),
+    _automala("hier", "nc", 256, "scan1", "diagonal", (0, 0, 0, 0, -1, 0, 0, 5), 8.06e-02),
+    _automala("hier", "nc", 257, "grow", "mix", (3, 32, 3, 32, 3, 9, 0, 1), 5.07e-04),
+    _automala("hier", "nc", 512, "shrink", "identity", (12, 33, 12, 33, -15, -9, 8, 2), 6.65e-02),
+    _automala("ar1", "sv", 129, "tuned", "diagonal", (5, 25, 6, 24, -3, 1, 0, 2), 1.83e-02),
+    _automala("ar1", "sv", 256, "shrink", "mix", (2, 33, 2, 33, -16, -11, 577, 2), 3.87e-02),
+    _automala("ar1", "sv", 257, "scan1", "identity", (0, 0, 0, 0, -1, 0, 0, 5), 4.72e-02),
+    _automala("ar1", "sv", 512, "grow", "diagonal", (7, 38, 7, 38, 4, 10, 0, 2), 4.74e-04),
+    _automala("ar1", "n", 129, "grow", "mix", (3, 27, 3, 27, 5, 10, 0, 2), 2.57e-03),
+    _automala("ar1", "n", 256, "shrink", "mix", (2, 33, 2, 33, -16, -11, 577, 2), 4.14e-02),
+    _automala("ar1", "n", 257, "scan1", "diagonal", (0, 0, 0, 0, -1, 1, 0, 5), 1.34e-03),
+    _automala("ar1", "n", 512, "tuned", "identity", (7, 38, 7, 38, -4, 2, 0, 2), 3.70e-04),
+    _automala("mixture", None, 129, "shrink", "identity", (7, 23, 8, 22, -9, -8, 0, 3), 4.03e-02),
+    _automala("mixture", None, 256, "scan1", "diagonal", (0, 0, 0, 0, -1, 1, 0, 5), 2.68e-02),
+    _automala("mixture", None, 257, "tuned", "mix", (1, 34, 1, 34, -2, 1, 0, 1), 3.13e-02),
+    _automala("mixture", None, 512, "grow", "diagonal", (16, 29, 17, 28, 6, 11, 0, 4), 8.13e-04),
+    _automala("dense", None, 129, "scan1", "diagonal", (0, 0, 0, 0, -1, 0, 0, 5), 6.22e-03),
+    _automala("dense", None, 256, "tuned", "mix", (8, 27, 12, 23, -3, 0, 0, 3), 4.08e-03),
+    _automala("dense", None, 257, "grow", "identity", (1, 34, 1, 34, 8, 11, 0, 1), 3.20e-03),
+    _automala("dense", None, 512, "shrink", "mix", (20, 25, 21, 24, -12, -9, 0, 5), 1.83e-02),
+]
+
 CASES = SLICE_CASES + MALA_CASES
-assert len(set(c.id for c in CASES)) == len(CASES)
+assert len(set(c.id for c in CASES + AUTOMALA_CASES)) == len(CASES) + len(AUTOMALA_CASES)
 
 # ---- the refresh kernels that no family's test_log_density_at_every_beta visits: (family, variant, state dimension, parameters) ---------
 LOG_DENSITY_CASES = [
@@ -132,7 +195,7 @@ def model(case):
     density at precision 0.5 (mixture's log density: 0.25), MALA at 1"""
     if case.id in _MODELS:
         return _MODELS[case.id]
-    f, v, d, mala, lp = case.family, case.variant, case.d, case.mode == "mala", case.mode == "lp"
+    f, v, d, mala, lp = case.family, case.variant, case.d, case.mode in ("mala", "automala"), case.mode == "lp"
     prec = 1.0 if mala else 0.5
     kinds = np.zeros(d, dtype=np.int32)
     if f == "glm":
@@ -185,7 +248,7 @@ _STATE_SEED = {
 def layout(case):
     """(betas, x, chain): _random_states of the families' tests -- the schedule 0, sorted uniforms, 1; states N(0, scale^2) (varsel: the
     thetas, then fair coins); a random chain permutation"""
-    seed, scale = _STATE_SEED[(case.family, case.mode)](case)
+    seed, scale = _STATE_SEED[(case.family, "mala" if case.mode == "automala" else case.mode)](case)
     N, d = case.N, case.d
     g = np.random.default_rng(seed)
     betas = np.concatenate([[0.0], np.sort(g.uniform(0.0, 1.0, N - 2)), [1.0]])
@@ -236,6 +299,33 @@ def mala_reference(case, betas, x, chain, rng):
             xc, acc_sum = res["x"], acc_sum + res["acc_sum"]
         out[i] = dict(x=xc, words=r.state, acc_sum=acc_sum)
     return out, accepted, rejected
+
+
+def automala_reference(case, betas, x, chain, rng):
+    """the restatement's AutoMALA transition (tests/automala_ref.py) of every replica off the reference chain at the case's step and scan
+    -> {replica: automala_transition's dict + words}"""
+    m, d = model(case), case.d
+    std, nr = target_std(case), n_refresh(d, base=AUTOMALA_BASE_N_REFRESH)
+    out = {}
+    for i in range(case.N):
+        c = int(chain[i])
+        if c == 0:
+            continue
+        r = O.OracleRng(state=(int(rng[i, 0]), int(rng[i, 1])))
+        Mv = aaps_ref.build_preconditioner(r, d, PRECOND_MODE[case.kw["precond"]], 1.0 / 3.0, 1.0 / 3.0, std)
+        out[i] = automala_ref.automala_transition(x[i], r, m.chain(betas[c]), case.kw["step"], nr, Mv, case.kw["scan"] != 1)
+        out[i]["words"] = r.state
+    return out
+
+
+def automala_seen(case, x, res):
+    """(the counts that a case's seen= records, the least margin) of automala_reference's result"""
+    ex = [e for r in res.values() for e in r["exponents"]]
+    acc, n = sum(r["accepted"] for r in res.values()), sum(r["acc_n"] for r in res.values())
+    rs, rn = sum(r["rev_sum"] for r in res.values()), sum(r["rev_n"] for r in res.values())
+    moved = sum(int(not np.array_equal(r["x"], x[i])) for i, r in res.items())
+    nonfinite = sum(r["nonfinite"] for r in res.values())
+    return (acc, n - acc, rs, rn - rs, min(ex), max(ex), nonfinite, moved), min(min(r["margins"]) for r in res.values())
 
 
 def slice_reference(case, beta, x, words):

@@ -1,11 +1,18 @@
 """The case table of tests/family_blocks.py, checked without a device: that it reaches every instantiation it is there for, and that the
 restatement's own MALA, from the table's inputs, accepts some proposals and rejects others in every MALA case -- so that the parity test
-of tests/test_gpu_family_blocks.py sees both branches of the accept / reject step.
+of tests/test_gpu_family_blocks.py sees both branches of the accept / reject step.  The AutoMALA cases likewise: the restatement alone
+(tests/automala_ref.py), from the engine's RNG words, must not raise, must take both outcomes of the MH step and of the reversibility
+check in every case that has them, must only grow, only shrink, or meet non-finite trials where the case's regime says so, and none of its
+decisions may be closer than 1e-6 to going the other way: a device that differs from the restatement in the last bits could otherwise
+rightly decide otherwise.  1e-6 is the floor tests/test_gpu_family_edges.py uses for |u - alpha|; at |lp| + |ke| <= ~1e3 it is 100 x the
+project's log-density tolerance of 1e-11 relative.  The whole AutoMALA part takes about 15 s, half of it dense at d = 512.
 
 A cell is (family, variant, mode, E, whole): E = blocks_per_lane of the state dimension, whole = the state fills its E blocks.  The
 launchers (pte_<family>.hpp, <family>_launch) take the FULL instantiation -- no per-lane validity masks -- at whole for MALA everywhere
 and for SliceSampler on the dense and variable-selection families; the other families' slice mode has the masked instantiation only,
 which eight whole blocks then run with every lane valid."""
+import math
+
 import numpy as np
 import pytest
 
@@ -124,3 +131,54 @@ def test_the_restatement_accepts_and_rejects(case, words):
     assert len(res) == case.N - 1 and accepted + rejected == (case.N - 1) * B.n_refresh(case.d)
     assert accepted > 0 and rejected > 0, (accepted, rejected)
     assert all(np.all(np.isfinite(r["x"])) for r in res.values())
+
+
+# ---- AutoMALA --------------------------------------------------------------------------------------------------------------------------
+PAIRS = [(f, v) for f in ("glm", "hier", "ar1", "mixture", "dense") for v in VARIANTS[f]]
+MARGIN_FLOOR = 1e-6
+
+
+def test_automala_cases_cover_regimes_dimensions_and_preconditioners():
+    A = B.AUTOMALA_CASES
+    assert len(A) == 32 and all(c.N == 6 and c.mode == "automala" for c in A)
+    assert sorted((c.family, c.variant, c.d) for c in A) == sorted((f, v, d) for f, v in PAIRS for d in B.AUTOMALA_DIMS)
+    for f, v in PAIRS:                                   # every (family, variant) meets every regime
+        assert sorted(c.kw["regime"] for c in A if (c.family, c.variant) == (f, v)) == sorted(B.AUTOMALA_REGIMES), (f, v)
+    for regime in B.AUTOMALA_REGIMES:                    # every regime meets every dimension class and every preconditioner
+        mine = [c for c in A if c.kw["regime"] == regime]
+        assert {cell(c)[3:] for c in mine} == set(FOUR_CELLS), regime
+        assert {c.kw["precond"] for c in mine} == {"identity", "diagonal", "mix"}, regime
+    assert B.n_refresh(129, base=1) == 6 and B.n_refresh(512, base=1) == 9
+    for c in A:                                          # the MALA case's inputs, its step where the regime does not set one
+        (m,) = [k for k in B.MALA_CASES if (k.family, k.variant, k.d) == (c.family, c.variant, c.d)]
+        assert c.kw["step"] == {"grow": 2.0 ** -12, "shrink": 2.0 ** 8}.get(c.kw["regime"], m.kw["step"]), c
+        assert c.kw["scan"] == (1 if c.kw["regime"] == "scan1" else 2), c
+        assert B.model(c).ref_prec == 1.0 and all(np.array_equal(a, b) for a, b in zip(B.layout(c), B.layout(m))), c
+        assert {k: c.kw[k] for k in ("n", "K") if k in m.kw} == {k: m.kw[k] for k in ("n", "K") if k in m.kw}, c
+
+
+@pytest.mark.parametrize("case", B.AUTOMALA_CASES, ids=[c.id for c in B.AUTOMALA_CASES])
+def test_the_automala_restatement_meets_the_case_s_conditions(case, words):
+    betas, x, chain = B.layout(case)
+    res = B.automala_reference(case, betas, x, chain, words)          # (raises at a start without density or a step that reaches 0)
+    seen, margin = B.automala_seen(case, x, res)
+    accepted, rejected, passed, failed, lo, hi, nonfinite, moved = seen
+    regime, nr = case.kw["regime"], B.n_refresh(case.d, base=B.AUTOMALA_BASE_N_REFRESH)
+    print("%s %s %s step %g: %s, least margin %.2e (in the table: %s, %.2e)" % (case.id, regime, case.kw["precond"], case.kw["step"], seen, margin,
+                                                                               case.kw["seen"], case.kw["margin"]))
+    assert len(res) == case.N - 1 and all(np.all(np.isfinite(r["x"])) for r in res.values())
+    if regime == "scan1":
+        assert moved == case.N - 1 and accepted + rejected == 0 and passed + failed == 0
+        assert all(len(r["exponents"]) == nr for r in res.values())
+    else:
+        assert accepted + rejected == passed + failed == (case.N - 1) * nr
+        assert all(len(r["exponents"]) == 2 * nr for r in res.values())
+        assert accepted > 0 and rejected > 0 and passed > 0 and failed > 0, seen
+    if regime == "grow":
+        assert lo > 0, seen
+    if regime == "shrink":
+        assert hi < 0, seen
+        if (case.family, case.variant) in (("hier", "c"), ("ar1", "sv"), ("ar1", "n")):
+            assert nonfinite > 0, seen
+    assert margin >= MARGIN_FLOOR, margin
+    assert seen == case.kw["seen"] and math.isclose(margin, case.kw["margin"], rel_tol=0.01), (seen, margin)

@@ -16,7 +16,18 @@ test_the_measured_ratios_hold repeats the measurement on the small shapes.
 
 Before AmTarget::ar1_and_sqr_norm and Ar1.leaves took 1 - phi^2, its root, its log and 1 - phi from exp(-2 |a|), the AR(1) cases failed:
 om = 1 - tanh(a)^2 cancels, the log density was off by 5.5e-9 at |a| = 10, 1.6e-7 at 12, 8.3e-5 at 15, 2.2e-2 at 18 and -inf from
-|a| = 19.07 (19.5, 25), whatever T and the observation model, and d/dmu (through (1 - phi) / sigma) failed from a = 10."""
+|a| = 19.07 (19.5, 25), whatever T and the observation model, and d/dmu (through (1 - phi) / sigma) failed from a = 10.
+
+AutoMALA (part (f) of tests/test_gpu_family_edges.py): the restatement's transition (tests/automala_ref.py) from the battery states, alone:
+it must not raise, no decision of it may be closer than 1e-6 to going the other way (the floor of test_one_swap's |u - alpha|; at
+|lp| + |ke| <= ~1e3 it is 100 x the log-density tolerance above) -- otherwise a device that differs in the last bits could rightly decide
+otherwise --, and over each family it must move some chains and leave others, pass and fail the reversibility check, and on AR(1), the
+hierarchical family and the funnel meet non-finite trials.  Measured (kept states, chains moved / left, checks passed / failed, non-finite
+trials, exponents, least margin):
+    ar1 139 of 150, 47 / 80, 104 / 319, 87, -7 .. 1, 6.7e-5       hier 36 of 60, 19 / 11, 36 / 64, 5, -6 .. 1, 1.2e-3
+    glm 27 of 36, 6 / 15, 15 / 41, 0, -9 .. 1, 1.8e-4             mixture 8 of 14, 2 / 3, 10 / 11, 0, -12 .. -5, 1.1e-2
+    mixture_model 11 of 11, 1 / 7, 6 / 19, 0, -43 .. 1, 3.1e-2    dense 9 of 12, 3 / 3, 9 / 13, 0, -3 .. 1, 3.2e-2
+    funnel 8 of 12, 2 / 4, 5 / 13, 12, -25 .. 2, 2.4e-3"""
 import math
 
 import numpy as np
@@ -24,6 +35,7 @@ import pytest
 from mpmath import mp, mpf
 
 import family_edges as E
+import test_gpu_family_edges as G                   # part (f)'s states, layout and restatement: the very ones the device is compared with
 
 LP_RTOL, LP_ATOL = 1e-11, 1e-11
 G_RTOL = 1e-9
@@ -102,3 +114,54 @@ def test_the_measured_ratios_hold(shape):
     for _ in range(2):
         err, mag = _gradient_error(shape, g.normal(0.0, 1.5, shape.dim))
         assert max(err) <= 10.0 * G_RATIO[shape.family] * max(mag), (shape, float(max(err) / max(mag)))
+
+
+# ---- AutoMALA from the battery states: the restatement alone -----------------------------------------------------------------------------
+MARGIN_FLOOR = 1e-6
+_AUTOMALA = {}
+
+
+def automala_summary(shape):
+    """the restatement's transitions of part (f) of the shape (run once): dict(kept, moved, left, passed, failed, nonfinite, margin)"""
+    if shape.id not in _AUTOMALA:
+        out = dict(kept=0, moved=0, left=0, passed=0, failed=0, nonfinite=0, margin=math.inf)
+        for key, states in G.automala_groups(shape):
+            out["kept"] += len(states)
+            (_, x, chain, _), _, res = G.automala_expected(shape, key, states)           # (raises where a state has no density or no step)
+            assert len(res) == len(states) - 1 and all(np.all(np.isfinite(w["x"])) for w in res.values())
+            for i, w in res.items():
+                same = np.array_equal(w["x"], x[i])
+                out["moved"] += int(not same)
+                out["left"] += int(same)
+                out["passed"] += w["rev_sum"]
+                out["failed"] += w["rev_n"] - w["rev_sum"]
+                out["nonfinite"] += w["nonfinite"]
+                out["margin"] = min(out["margin"], min(w["margins"]))
+        _AUTOMALA[shape.id] = out
+    return _AUTOMALA[shape.id]
+
+
+def test_automala_covers_every_gradient_shape():
+    assert [s.id for s in G.AUTOMALA_SHAPES] == [s.id for s in E.SHAPES if s.family not in ("varsel", "changepoint")]
+    assert sorted(G.AUTOMALA_KEPT) == sorted(s.id for s in G.AUTOMALA_SHAPES) and len(G.AUTOMALA_SHAPES) == 29
+
+
+@pytest.mark.parametrize("shape", G.AUTOMALA_SHAPES, ids=[s.id for s in G.AUTOMALA_SHAPES])
+def test_automala_from_the_battery_states(shape):
+    got = automala_summary(shape)
+    print(shape.id, got)
+    assert (got["kept"], len(shape.states)) == G.AUTOMALA_KEPT[shape.id]
+    assert got["margin"] >= MARGIN_FLOOR, got
+
+
+@pytest.mark.parametrize("family", E.HAS_GRADIENT)
+def test_automala_decides_both_ways_in_every_family(family):
+    tot = {}
+    for s in G.AUTOMALA_SHAPES:
+        if s.family == family:
+            for k, v in automala_summary(s).items():
+                tot[k] = tot.get(k, 0) + v if k != "margin" else min(tot.get(k, math.inf), v)
+    print(family, tot)
+    assert tot["moved"] > 0 and tot["left"] > 0 and tot["passed"] > 0 and tot["failed"] > 0, tot
+    if family in ("ar1", "hier", "funnel"):
+        assert tot["nonfinite"] > 0, tot

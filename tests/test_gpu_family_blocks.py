@@ -1,7 +1,7 @@
 """The families' explore kernels at four and eight blocks per lane (E = 4: d = 129 .. 256, E = 8: 257 .. 512) against the restatements at
 one transition, over the case table of tests/family_blocks.py: k_explore_glm, k_explore_hier, k_explore_ar1, k_explore_mixture,
 k_explore_dense, k_explore_dense_slice and k_explore_varsel, every (E, LIK or PARAM, slice or Langevin, FULL) instantiation that the
-launchers reach from E = 4 on -- the sizes where the hierarchical and AR(1) data leave the registers for L2, the block-sum tree takes its
+launchers reach from E = 4 on (the Langevin ones under MALA and under AutoMALA, whose step-size search visits the huge and non-finite points) -- the sizes where the hierarchical and AR(1) data leave the registers for L2, the block-sum tree takes its
 E >= 4 branch, the dense slice kernel carries its cached u, A and S over up to 512 coordinates and variable selection's Bool coordinate
 d + j lies in block (d + j) / 64.  tests/test_family_blocks_cpu.py holds the table to its coverage.
 
@@ -13,6 +13,7 @@ import math
 import numpy as np
 import pytest
 
+import automala_ref as R
 import family_blocks as B
 import oracle as O
 
@@ -111,6 +112,28 @@ def test_one_mala_transition_parity(P, case):
         np.testing.assert_allclose(am[c], want["acc_sum"] / nr, rtol=RTOL, atol=1e-12, err_msg=what)
     print("MALA %s, step %g: %d proposals accepted, %d rejected" % (case.id, step, accepted, rejected))
     assert accepted > 0 and rejected > 0
+
+
+@pytest.mark.parametrize("case", B.AUTOMALA_CASES, ids=[c.id for c in B.AUTOMALA_CASES])
+def test_one_automala_transition_parity(P, case):
+    """one AutoMALA transition (base_n_refresh = 1: ceil(d^0.35) refreshes) in the case's regime -- its step, with the MH step (scan 2) or
+    without (scan 1) -- against aaps_ref.build_preconditioner + automala_ref.automala_transition: RNG words, the counting recorders, the sum
+    of the step-size factors and the number of reversibility checks passed equal, states and mean acceptance within RTOL.
+    tests/test_family_blocks_cpu.py holds the restatement alone to what makes the comparison meaningful (both outcomes of every decision,
+    none of them closer than 1e-6 to the other)"""
+    d, N, step = case.d, case.N, case.kw["step"]
+    pc = {"identity": P.IdentityPreconditioner, "diagonal": P.DiagonalPreconditioner, "mix": P.MixDiagonalPreconditioner}[case.kw["precond"]]()
+    ex = P.AutoMALA(base_n_refresh=B.AUTOMALA_BASE_N_REFRESH, step_size=step, preconditioner=pc)
+    assert ex.base_n_refresh * int(math.ceil(d ** ex.exponent_n_refresh)) == B.n_refresh(d, base=B.AUTOMALA_BASE_N_REFRESH)
+    pt = _pt(P, case, ex)
+    betas, x, chain, rng = _random_states(pt, case)
+    assert np.array_equal(rng, B.init_rng_words(N))      # the words tests/test_family_blocks_cpu.py held the restatement to its conditions with
+    eng = pt.replicas
+    eng.set_explorer_adaptation(step, B.target_std(case))
+    eng.explore(case.kw["scan"])
+    res = B.automala_reference(case, betas, x, chain, rng)
+    assert len(res) == N - 1
+    R.assert_engine_matches(eng, chain, res, RTOL, lambda i: case.id)
 
 
 @pytest.mark.parametrize("case", B.LOG_DENSITY_CASES, ids=[c.id for c in B.LOG_DENSITY_CASES])

@@ -14,6 +14,9 @@ RNG words made here on the CPU (splits of one oracle stream), so that everything
     and Bool coordinates equal, Float64 ones to 1e-9 relative + 1e-12, explorer statistics equal; (w, p) = (10, 20) and (0.25, 3) -- the
     change point (2, 2), and both of its evaluation forms.  n_passes = 1: the pass that starts at the edge.
 (d) one MALA transition of AR(1) and the hierarchical family from their battery states with |lp| <= 1e6, against mixture_ref.mala_transition.
+(f) one AutoMALA transition of every family that has a gradient (the funnel too) from the same states as (d), against
+    automala_ref.automala_transition: RNG words, the counting recorders, the sum of the step-size factors and the number of reversibility
+    checks passed equal, states and mean acceptance to 1e-9 relative.
 (e) one swap from the battery states: each active pair's two log ratios against family_mp, the acceptance against them, the labels
     afterwards against u < alpha with the lower chain's uniform."""
 import math
@@ -23,6 +26,7 @@ import pytest
 from mpmath import mp, mpf
 
 import aaps_ref as A
+import automala_ref as R
 import family_edges as E
 import mixture_ref as M
 import oracle as O
@@ -226,6 +230,61 @@ def test_one_mala_transition_parity(P, shape):
             moved += int(not same)
             stuck += int(same)
     assert moved > 0 and stuck > 0, (moved, stuck)
+
+
+# ---- (f) -------------------------------------------------------------------------------------------------------------------------------
+# One AutoMALA transition (base_n_refresh = 1, mix preconditioner, scan 2: with the MH step) from the same states as (d), of every family
+# that has a gradient.  The step is 1 unless the shape is listed; KEPT is (states of |lp| <= 1e6 at both ends, states) by shape -- no state
+# is left out silently.  tests/test_family_edges_cpu.py holds the restatement alone to the conditions that make the comparison meaningful.
+AUTOMALA_SHAPES = [s for s in E.SHAPES if s.family in E.HAS_GRADIENT]
+AUTOMALA_STEP = {}
+AUTOMALA_KEPT = {
+    "ar1-T1-sv": (24, 25), "ar1-T1-n": (24, 25), "ar1-T8-sv": (22, 25), "ar1-T8-n": (22, 25), "ar1-T64-sv": (23, 25), "ar1-T64-n": (24, 25),
+    "hier-J1-c": (6, 10), "hier-J1-n": (6, 10), "hier-J8-c": (6, 10), "hier-J8-n": (6, 10), "hier-J64-c": (6, 10), "hier-J64-n": (6, 10),
+    "glm-n1-d1-b": (6, 7), "glm-n1-d1-n": (3, 5), "glm-n65-d3-b": (6, 7), "glm-n65-d3-n": (3, 5), "glm-n130-d67-b": (6, 7), "glm-n130-d67-n": (3, 5),
+    "mixture-K1-d1": (2, 4), "mixture-K3-d65": (3, 5), "mixture-K8-d64": (3, 5),
+    "mixture_model-n1-K1": (3, 3), "mixture_model-n65-K3": (4, 4), "mixture_model-n200-K8": (4, 4),
+    "dense-d1": (3, 4), "dense-d64": (3, 4), "dense-d65": (3, 4), "funnel-d2": (5, 6), "funnel-d65": (3, 6),
+}
+
+
+def automala_n_refresh(d):
+    """AutoMALA's exponent_n_refresh = 0.35 at base_n_refresh = 1"""
+    return int(math.ceil(d ** 0.35))
+
+
+def automala_groups(shape):
+    """[(key of layout(), states)]: mala_groups with a key range of its own"""
+    return [(9000 + 10 * E.SHAPES.index(shape) + k, states) for k, states in enumerate(mala_groups(shape))]
+
+
+def automala_expected(shape, key, states):
+    """(layout, std, {replica off the reference chain: automala_ref.automala_transition's dict + words})"""
+    betas, x, chain, rng = layout(key, shape, states)
+    d, step = shape.dim, AUTOMALA_STEP.get(shape.id, 1.0)
+    std = np.random.default_rng(d).uniform(0.5, 2.0, d)
+    res = {}
+    for i in range(len(states)):
+        c = int(chain[i])
+        if c == 0:
+            continue
+        r = O.OracleRng(state=(int(rng[i, 0]), int(rng[i, 1])))
+        Mv = A.build_preconditioner(r, d, 2, 1.0 / 3.0, 1.0 / 3.0, std)
+        res[i] = R.automala_transition(x[i], r, E.chain(shape, betas[c]), step, automala_n_refresh(d), Mv, True)
+        res[i]["words"] = r.state
+    return (betas, x, chain, rng), std, res
+
+
+@pytest.mark.parametrize("shape", AUTOMALA_SHAPES, ids=[s.id for s in AUTOMALA_SHAPES])
+def test_one_automala_transition_parity(P, shape):
+    step = AUTOMALA_STEP.get(shape.id, 1.0)
+    for key, states in automala_groups(shape):
+        (betas, x, chain, rng), std, res = automala_expected(shape, key, states)
+        ex = P.AutoMALA(base_n_refresh=1, step_size=step, preconditioner=P.MixDiagonalPreconditioner())
+        eng = _engine(P, shape, ex, betas, x, chain, rng)
+        eng.set_explorer_adaptation(step, std)
+        eng.explore(2)
+        R.assert_engine_matches(eng, chain, res, RTOL, lambda i: "%s %s" % (shape.id, states[i][0]))
 
 
 # ---- (e) -------------------------------------------------------------------------------------------------------------------------------
