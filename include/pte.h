@@ -67,9 +67,12 @@ enum {
                                             4..512; SliceSampler / AutoMALA / MALA / Compose of them */
     PTE_TARGET_DENSE_NORMAL = 11,        /* InterpolatingPath(normal ref, N(mean, precision^-1) with a dense precision matrix;
                                             pte_set_target_dense): dim in 1..512; SliceSampler / AutoMALA / MALA / Compose of them */
-    PTE_TARGET_SPIN_GLASS = 12           /* InterpolatingPath(SpinGlass(0), SpinGlass(beta)): the +-J Edwards-Anderson model, PTE_TARGET_ISING with
+    PTE_TARGET_SPIN_GLASS = 12,          /* InterpolatingPath(SpinGlass(0), SpinGlass(beta)): the +-J Edwards-Anderson model, PTE_TARGET_ISING with
                                             quenched bonds (pte_set_target_spin_glass): dim = base_length^2, 2 <= base_length, dim <= 65536;
                                             target_params[0] = beta; PTE_EXPLORER_ISING_METROPOLIS or PTE_EXPLORER_CHECKERBOARD_METROPOLIS */
+    PTE_TARGET_SPIN_GLASS_3D = 13        /* the same model on the base_length^3 periodic cube (pte_set_target_spin_glass_3d; DESIGN 4.19, the project's
+                                            own specification): dim = base_length^3, base_length even and in 2..32 (a row of the lattice is one
+                                            32-bit word); target_params[0] = beta; PTE_EXPLORER_CHECKERBOARD_METROPOLIS only, debug_kernel 0 */
 };
 /* PTE_TARGET_LATENT_AR1: the observation model */
 enum {
@@ -103,7 +106,7 @@ enum {
                                             aaps_K; step size fixed; MVN and funnel paths, dim <= 512, single explorer)      */
     PTE_EXPLORER_CHECKERBOARD_METROPOLIS = 7 /* CheckerboardMetropolis: the two-colour Metropolis sweep of the lattice targets (the project's own
                                             specification, n_steps in slice_n_passes); PTE_TARGET_ISING and PTE_TARGET_SPIN_GLASS with an even
-                                            base_length, single explorer */
+                                            base_length, PTE_TARGET_SPIN_GLASS_3D, single explorer */
 };
 enum {                                   /* Inputs.record (src/pt/Inputs.jl:57-62)                         */
     PTE_RECORD_ROUND_TRIP    = 1u << 0,  /* round_trip     src/recorders/RoundTripRecorder.jl              */
@@ -313,6 +316,16 @@ int pte_set_target_dense(pte_engine *h, int64_t dim, const double *mean /*[dim]*
  * again to replace the bonds.  Until the first call pte_explore, pte_swap, pte_run_scans, pte_group_run_scans and pte_get_state fail.
  * DESIGN 4.17. */
 int pte_set_target_spin_glass(pte_engine *h, int64_t base_length, const int8_t *bonds_right /*[L][L]*/, const int8_t *bonds_down /*[L][L]*/);
+/* PTE_TARGET_SPIN_GLASS_3D: the quenched bonds of the base_length^3 periodic lattice, three planes [L][L][L] in C order [z][y][x], every
+ * entry +1 or -1: bonds_x[z][y][x] couples site (z, y, x) with (z, y, (x + 1) mod L), bonds_y[z][y][x] with (z, (y + 1) mod L, x),
+ * bonds_z[z][y][x] with ((z + 1) mod L, y, x).  Site (z, y, x) is coordinate (z L + y) L + x of the state.  The target is exp(beta S),
+ * S = sum s_zyx (bonds_x s_x+1 + bonds_y s_y+1 + bonds_z s_z+1) (at L = 2 the two bonds between the same pair of sites are distinct terms).
+ * Refuses an engine of another target, a base_length that is not the engine's, a null argument, and the first entry that is not +-1 (by
+ * plane and index).  A refused call leaves the engine as it was.  Otherwise uploads the bonds (one copy shared by all replicas) and recounts
+ * the swap statistic of the current states; may be called again to replace the bonds.  Until the first call pte_explore, pte_swap,
+ * pte_run_scans, pte_group_run_scans and pte_get_state fail.  DESIGN 4.19. */
+int pte_set_target_spin_glass_3d(pte_engine *h, int64_t base_length, const int8_t *bonds_x /*[L][L][L]*/, const int8_t *bonds_y /*[L][L][L]*/,
+                                 const int8_t *bonds_z /*[L][L][L]*/);
 /* PTE_TARGET_VARIABLE_SELECTION: the data of the target N(theta; 0, I / p) prod_j pi^gamma_j (1 - pi)^(1 - gamma_j)
  * prod_i p(y_i | eta_i = sum_j X[i][j] gamma_j theta_j) (p = target_params[0], the reference's precision; pi = inclusion_prob; X row-major
  * [n_obs][d] with d = dim / 2; likelihood PTE_GLM_*, noise_sd read by PTE_GLM_NORMAL_IDENTITY only).  Validates as pte_set_target_glm does

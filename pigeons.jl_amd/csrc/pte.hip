@@ -34,6 +34,7 @@
 #include "pte_changepoint_params.hpp"
 #include "pte_spinglass_params.hpp"
 #include "pte_checkerboard_params.hpp"
+#include "pte_lattice3d_params.hpp"
 #else                              // tools / development builds: one translation unit
 #include "pte_langevin_launch.hpp"
 #include "pte_aaps.hpp"
@@ -47,6 +48,7 @@
 #include "pte_changepoint.hpp"
 #include "pte_spinglass.hpp"
 #include "pte_checkerboard.hpp"
+#include "pte_lattice3d.hpp"
 #endif
 #include "pte_ising.hpp"
 #if defined(PTE_PROFILE_AM)               // debug builds only (tools/prof_automala.py): 12 words per wave, section times of k_explore_automala
@@ -128,6 +130,8 @@ struct pte_engine {
     double *d_dense = nullptr;      // PTE_TARGET_DENSE_NORMAL: the precision matrix [d][ld], its diagonal [ld], the mean [ld], ld = 64 blocks_per_lane(d)
     DenseParams dense{};            // the uploaded data as the kernels read it; dense.n = 0 until pte_set_target_dense
     unsigned char *d_sg_bytes = nullptr; unsigned *d_sg_words = nullptr;   // PTE_TARGET_SPIN_GLASS: the bonds, a byte per site and (L % 32 == 0) two bit-packed planes
+    unsigned *d_sg3_words = nullptr;   // PTE_TARGET_SPIN_GLASS_3D: the bonds, three planes of L * L words
+    SpinGlass3DParams spinglass3d{};   // ... as the kernel reads them; spinglass3d.jw = nullptr until pte_set_target_spin_glass_3d
     SpinGlassParams spinglass{};    // the uploaded bonds as the kernels read them; spinglass.jb = nullptr until pte_set_target_spin_glass
     double step_size = 1.0;
     int am_n_refresh = 0;
@@ -277,8 +281,13 @@ const PathFamily *path_family(int target) {
 }
 bool on_interpolated_path(int target) { return path_family(target) != nullptr; }
 // the lattice targets: Bool states bit-packed in HBM, IsingMetropolis, no k_init; the device sees both as PTE_TARGET_ISING (suff = the pair sum,
-// bond-weighted on the spin glass: DESIGN 4.17)
-bool on_lattice(int target) { return target == PTE_TARGET_ISING || target == PTE_TARGET_SPIN_GLASS; }
+// bond-weighted on the spin glass: DESIGN 4.17; the 3-D spin glass, under CheckerboardMetropolis only: DESIGN 4.19)
+bool on_lattice(int target) { return target == PTE_TARGET_ISING || target == PTE_TARGET_SPIN_GLASS || target == PTE_TARGET_SPIN_GLASS_3D; }
+// base_length of the 3-D lattice of `dim` sites: the even L in 2..32 with L^3 == dim, or 0
+int64_t lattice3d_base_length(int64_t dim) {
+    for (int64_t L = 2; L <= 32; L += 2) if (L * L * L == dim) return L;
+    return 0;
+}
 // the family's data has been uploaded (true for every target that needs none)
 bool family_ready(const pte_engine *h) {
     switch (h->cfg.target) {
@@ -291,6 +300,7 @@ bool family_ready(const pte_engine *h) {
     case PTE_TARGET_LATENT_AR1: return h->ar1.n > 0;
     case PTE_TARGET_DENSE_NORMAL: return h->dense.n > 0;
     case PTE_TARGET_SPIN_GLASS: return h->spinglass.jb != nullptr;
+    case PTE_TARGET_SPIN_GLASS_3D: return h->spinglass3d.jw != nullptr;
     default: return true;
     }
 }
@@ -298,7 +308,8 @@ bool family_ready(const pte_engine *h) {
 int family_missing_error(pte_engine *h, const char *what, const pte_engine *of = nullptr) {
     static const PathFamily spinglass{"spin-glass", "bonds", "pte_set_target_spin_glass", "", "k_explore_spinglass"};       // (a lattice target, on no interpolated normal path)
     const int target = (of ? of : h)->cfg.target;
-    const PathFamily *f = target == PTE_TARGET_SPIN_GLASS ? &spinglass : path_family(target);
+    static const PathFamily spinglass3d{"3-D spin-glass", "bonds", "pte_set_target_spin_glass_3d", "", "k_explore_checkerboard3d"};
+    const PathFamily *f = target == PTE_TARGET_SPIN_GLASS ? &spinglass : target == PTE_TARGET_SPIN_GLASS_3D ? &spinglass3d : path_family(target);
     return fail(h, "%s: the %s target has no %s yet; call %s first", what, f->name, f->data, f->setter);
 }
 int family_no_kernel_error(pte_engine *h) {
@@ -640,6 +651,14 @@ int launch_explorer_kind(pte_engine *h, int64_t scan, int kind) {
         break;
     }
     case PTE_EXPLORER_CHECKERBOARD_METROPOLIS: {         // the two-colour sweep of either lattice target (pte_checkerboard.hpp); the Ising target has no bonds: null pointers
+        if (h->cfg.target == PTE_TARGET_SPIN_GLASS_3D) {     // the 3-D lattice: a kernel of its own (pte_lattice3d.hpp)
+            SpinGlass3DParams gp = h->spinglass3d;
+            gp.n_steps = h->cfg.slice_n_passes;
+            time_begin(h, 0, true);
+            if (lattice3d_launch(launch_site(h, (unsigned)N), h->dev, gp)) return fail(h, "this build holds no 3-D spin-glass kernel for dim %lld", (long long)h->d);
+            time_end(h);
+            break;
+        }
         SpinGlassParams gp = h->cfg.target == PTE_TARGET_SPIN_GLASS ? h->spinglass : SpinGlassParams{};
         gp.L = (int)std::llround(std::sqrt((double)h->d)); gp.n_steps = h->cfg.slice_n_passes; gp.beta_target = h->cfg.target_params[0];
         time_begin(h, 0, true);
@@ -1099,7 +1118,15 @@ int validate_config(const pte_config *cfg) {
         if (cfg->n_chains_variational > 0)
             return fail(nullptr, "pte_create: two-leg tempering (n_chains_variational > 0) is not available on the %s path", family->name);
     }
-    if (ising) {
+    if (cfg->target == PTE_TARGET_SPIN_GLASS_3D) {          // an even cube whose row is one word, CheckerboardMetropolis and nothing else
+        if (lattice3d_base_length(cfg->dim) == 0)
+            return fail(nullptr, "pte_create: the 3-D spin-glass path needs dim = base_length^3 with base_length even and in 2..32 (got %lld): "
+                                 "a row of the lattice is held in one 32-bit word, so 32 is the cap although 34..40 would fit the 65536-site limit", (long long)cfg->dim);
+        if (cfg->explorer != PTE_EXPLORER_CHECKERBOARD_METROPOLIS || cfg->explorer2 != PTE_EXPLORER_NONE)
+            return fail(nullptr, "pte_create: the 3-D spin-glass path is explored by CheckerboardMetropolis only (got explorers %d, %d)", cfg->explorer, cfg->explorer2);
+        if (cfg->debug_kernel != 0)
+            return fail(nullptr, "pte_create: the 3-D spin-glass path has one kernel; debug_kernel must be 0 (got %d)", cfg->debug_kernel);
+    } else if (ising) {
         const int64_t L = (int64_t)std::llround(std::sqrt((double)cfg->dim));
         if (spin_glass && (L < 2 || L * L != cfg->dim || cfg->dim > 65536))
             return fail(nullptr, "pte_create: the spin-glass path needs dim = base_length^2 with 2 <= base_length and dim <= 65536 (got %lld)", (long long)cfg->dim);
@@ -2085,6 +2112,7 @@ const char *pte_kernel_name(const pte_engine *h) {
         return (L % 32 == 0 && h->ising_impl == 0) ? "k_explore_ising_spec" : (L % 32 == 0 && h->ising_impl == 1) ? "k_explore_ising_bits" : "k_explore_ising";
     }
     case PTE_EXPLORER_CHECKERBOARD_METROPOLIS: {
+        if (h->cfg.target == PTE_TARGET_SPIN_GLASS_3D) return "k_explore_checkerboard3d";
         const int64_t L = (int64_t)std::llround(std::sqrt((double)h->d));
         return (L % 32 == 0 && h->ising_impl == 0) ? "k_explore_checkerboard" : "k_explore_checkerboard_sites";
     }
@@ -2405,6 +2433,42 @@ int pte_set_target_spin_glass(pte_engine *h, int64_t base_length, const int8_t *
     return 0;
 }
 
+// The 3-D +-J spin glass.  Host, once per call: the refusals, then the bonds as the kernel reads them -- three planes of L * L
+// words, row r = z L + y of a plane in one word, bit x set where the bond of site (z, y, x) is -1 -- and suff of every slot recounted under the
+// new bonds.  May be called again: the allocation is made once.  A refused call leaves the engine as it was.
+int pte_set_target_spin_glass_3d(pte_engine *h, int64_t base_length, const int8_t *bonds_x, const int8_t *bonds_y, const int8_t *bonds_z) {
+    if (!h) return 1;
+    PTE_ALIVE(h, "pte_set_target_spin_glass_3d");
+    if (h->cfg.target != PTE_TARGET_SPIN_GLASS_3D)
+        return fail(h, "pte_set_target_spin_glass_3d: this engine's target is %d, not PTE_TARGET_SPIN_GLASS_3D", h->cfg.target);
+    const int64_t d = h->d, L = lattice3d_base_length(d), R = L * L;
+    if (base_length != L)
+        return fail(h, "pte_set_target_spin_glass_3d: base_length must be the engine's %lld (dim = %lld) (got %lld)", (long long)L, (long long)d, (long long)base_length);
+    if (!bonds_x || !bonds_y || !bonds_z) return fail(h, "pte_set_target_spin_glass_3d: null argument");
+    const int8_t *const planes[3] = {bonds_x, bonds_y, bonds_z};
+    static const char *const names[3] = {"bonds_x", "bonds_y", "bonds_z"};
+    for (int plane = 0; plane < 3; ++plane)
+        for (int64_t s = 0; s < d; ++s)
+            if (planes[plane][s] != 1 && planes[plane][s] != -1)
+                return fail(h, "pte_set_target_spin_glass_3d: %s[%lld] must be +1 or -1 (got %d): ±J is the supported disorder -- real-valued or diluted "
+                               "couplings break the threshold filter and the bit packing of the sweep", names[plane], (long long)s, (int)planes[plane][s]);
+    HIP_OK(h, hipSetDevice(h->cfg.device));
+    std::vector<unsigned> jw((size_t)(3 * R), 0u);
+    for (int plane = 0; plane < 3; ++plane)
+        for (int64_t s = 0; s < d; ++s)
+            if (planes[plane][s] < 0) jw[(size_t)(plane * R + s / L)] |= 1u << (s % L);
+    if (!h->d_sg3_words && dev_alloc(h, &h->d_sg3_words, (size_t)(3 * R), false)) return 1;
+    HIP_OK(h, hipMemcpyAsync(h->d_sg3_words, jw.data(), sizeof(unsigned) * jw.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    SpinGlass3DParams &p = h->spinglass3d;
+    p.L = (int)L; p.n_steps = h->cfg.slice_n_passes; p.beta_target = h->cfg.target_params[0];
+    p.jw = h->d_sg3_words;
+    lattice3d_refresh_stats((unsigned)h->K, h->stream, h->dev, p);          // suff of the current states
+    HIP_OK(h, hipGetLastError());
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
 // The posterior of a finite mixture model.  Host, once per call: c_prior = -(d/2) log(2 pi / p), c_obs = -(n/2) log(2 pi); y is
 // uploaded zero-padded into one allocation sized once for the largest n.
 int pte_set_target_mixture_model(pte_engine *h, int64_t n_obs, const double *y) {
@@ -2634,6 +2698,12 @@ int pte_set_state(pte_engine *h, const double *state, const int64_t *chain, cons
     if (state && d > 0 && h->cfg.target == PTE_TARGET_SPIN_GLASS) {   // the bond-weighted pair sum of every slot, once the bonds are there (k_refresh_spinglass_stats)
         if (family_ready(h)) {
             spinglass_refresh_stats((unsigned)N, h->stream, h->dev, h->spinglass);
+            HIP_OK(h, hipGetLastError());
+            HIP_OK(h, hipStreamSynchronize(h->stream));
+        }
+    } else if (state && d > 0 && h->cfg.target == PTE_TARGET_SPIN_GLASS_3D) {   // the same in three dimensions (k_refresh_lattice3d_stats)
+        if (family_ready(h)) {
+            lattice3d_refresh_stats((unsigned)N, h->stream, h->dev, h->spinglass3d);
             HIP_OK(h, hipGetLastError());
             HIP_OK(h, hipStreamSynchronize(h->stream));
         }

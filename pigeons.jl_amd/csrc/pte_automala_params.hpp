@@ -1,7 +1,7 @@
 // pte_automala_params.hpp -- what the launcher (pte.hip) and the kernel families share: kernel parameters, where a launch goes (LaunchSite,
 // launch_on) and, per family, the one entry point through which its kernels are launched.
 //
-// The product library is built from EIGHT translation units (UNITS in __graft_entry__.py) and two listed beside them (LATTICE_UNITS, CHECKERBOARD_UNITS):
+// The product library is built from EIGHT translation units (UNITS in __graft_entry__.py) and three listed beside them (LATTICE_UNITS, CHECKERBOARD_UNITS, LATTICE3D_UNITS):
 //   pte.hip           the C ABI, the launcher and every kernel not named below, scheduled with -O2 -amdgpu-sched-strategy=max-ilp: the
 //                     one-wave-per-SIMD slice kernels gain 1.3-2.3 %
 //   pte_langevin.hip  AutoMALA / MALA and SliceSampler on the funnel path (pte_langevin_launch.hpp) with the default scheduler: max-ilp
@@ -15,6 +15,7 @@
 //                     DESIGN 4.16), under the same check
 //   pte_spinglass.hip the spin-glass kernels (pte_spinglass.hpp) with pte.hip's flags: they are the Ising kernels with bonds
 //   pte_checkerboard.hip the CheckerboardMetropolis kernels of both lattice targets (pte_checkerboard.hpp) with pte_spinglass.hip's flags
+//   pte_lattice3d.hip the 3-D spin-glass kernels (pte_lattice3d.hpp) with pte_spinglass.hip's flags
 // Every unit includes pte_kernels.hpp and therefore holds its own copy of the `static __device__` word g_rng_policy: PTE_KERNEL_UNITS below.
 // Tools and development builds compile pte.hip alone (no -DPTE_SPLIT_LANGEVIN): it then includes the kernel headers and their entry points itself.
 #pragma once
@@ -84,7 +85,7 @@ void langevin_refresh_funnel_stats(int E, unsigned N, hipStream_t stream, const 
 
 // The translation units besides pte.hip.  Each defines <unit>_set_rng_policy -- its own copy of g_rng_policy (hipError_t as int) -- with
 // PTE_DEFINE_RNG_POLICY_SETTER(<unit>), and pte_set_rng_policy walks this list: a unit listed here without the setter does not link.
-#define PTE_KERNEL_UNITS(X) X(langevin) X(aaps) X(mixture) X(glm) X(mixture_model) X(varsel) X(changepoint) X(spinglass) X(checkerboard)
+#define PTE_KERNEL_UNITS(X) X(langevin) X(aaps) X(mixture) X(glm) X(mixture_model) X(varsel) X(changepoint) X(spinglass) X(checkerboard) X(lattice3d)
 #define PTE_DECLARE_RNG_POLICY_SETTER(unit) int unit##_set_rng_policy(unsigned policy);
 PTE_KERNEL_UNITS(PTE_DECLARE_RNG_POLICY_SETTER)
 #define PTE_DEFINE_RNG_POLICY_SETTER(unit)                                                                                        \

@@ -25,11 +25,7 @@
 
 namespace pte {
 
-struct CheckerThresholds { uint64_t t4, t8; };
-__device__ __forceinline__ uint64_t checker_threshold(double r) {
-    const double s = r * 4503599627370496.0;                     // r 2^52, exact
-    return s < 4503599627370496.0 ? (uint64_t)s : MASK52;        // (the conversion truncates: floor of a non-negative double)
-}
+struct CheckerThresholds { uint64_t t4, t8; };        // (checker_threshold: pte_checkerboard_params.hpp, shared with pte_lattice3d.hpp)
 __device__ __forceinline__ CheckerThresholds checker_thresholds(double beta, double bt) {
     auto uniform64 = [](uint64_t v) {
         return ((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);

@@ -11,4 +11,11 @@ namespace pte {
 struct CheckerboardLaunch { bool sites; LaunchSite at; };
 int checkerboard_launch(const CheckerboardLaunch &L, const EngineDev &dev, const SpinGlassParams &sp);
 
+// The threshold word T = floor(r 2^52) of `u > r` on integers (pte_checkerboard.hpp derives it), 2^52 - 1 where r >= 1 or r is NaN.  Here, not
+// beside the 2-D kernels, because the 3-D kernel (pte_lattice3d.hpp, a translation unit of its own) decides with the same words.
+__device__ __forceinline__ uint64_t checker_threshold(double r) {
+    const double s = r * 4503599627370496.0;                     // r 2^52, exact
+    return s < 4503599627370496.0 ? (uint64_t)s : MASK52;        // (the conversion truncates: floor of a non-negative double)
+}
+
 }  // namespace pte

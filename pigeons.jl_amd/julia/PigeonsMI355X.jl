@@ -45,6 +45,7 @@ const TARGET_LATENT_AR1 = Int32(10)
 const AR1_STOCHASTIC_VOLATILITY, AR1_NORMAL_IDENTITY = Int32(0), Int32(1)
 const TARGET_DENSE_NORMAL = Int32(11)
 const TARGET_SPIN_GLASS = Int32(12)
+const TARGET_SPIN_GLASS_3D = Int32(13)      # the +-J spin glass on the L^3 cube, CheckerboardMetropolis only (DESIGN 4.19)
 const GLM_BERNOULLI_LOGIT, GLM_NORMAL_IDENTITY = Int32(0), Int32(1)
 const EXPLORER_NONE, EXPLORER_TOY, EXPLORER_SLICE, EXPLORER_AUTOMALA, EXPLORER_ISING, EXPLORER_MALA, EXPLORER_AAPS = Int32.((0, 1, 2, 3, 4, 5, 6))
 const EXPLORER_CHECKERBOARD_METROPOLIS = Int32(7)      # the two-colour Metropolis sweep of the lattice targets (DESIGN 4.18)
@@ -116,6 +117,10 @@ struct DeviceIsing; beta::Float64; base_length::Int; n_sweeps::Int; end
 multiplied by a quenched bond.  `bonds_right[i, j]` couples site (i, j) with (i, j + 1), `bonds_down[i, j]` couples (i, j) with (i + 1, j)
 (periodic), every entry +1 or -1; explorer = the Metropolis sweeps of examples/ising.jl:91-116 (n_sweeps passes)."""
 struct DeviceSpinGlass; beta::Float64; bonds_right::Matrix{Int8}; bonds_down::Matrix{Int8}; n_sweeps::Int; end
+"""The +-J Edwards-Anderson spin glass on the L x L x L periodic lattice, the device family PTE_TARGET_SPIN_GLASS_3D (DESIGN 4.19), L even and
+in 2..32.  `bonds_x[z, y, x]` couples site (z, y, x) with (z, y, x + 1), `bonds_y[z, y, x]` with (z, y + 1, x), `bonds_z[z, y, x]` with
+(z + 1, y, x) (periodic), every entry +1 or -1; explorer = CheckerboardMetropolis, n_sweeps two-colour sweeps per explore step."""
+struct DeviceSpinGlass3D; beta::Float64; bonds_x::Array{Int8, 3}; bonds_y::Array{Int8, 3}; bonds_z::Array{Int8, 3}; n_sweeps::Int; end
 """A normalised mixture of K <= 8 diagonal Gaussians, the device family PTE_TARGET_GAUSSIAN_MIXTURE (DESIGN 4.8): the device form of
 `DistributionLogPotential(MixtureModel([MvNormal(means[k], Diagonal(std_devs[k] .^ 2)) for k in 1:K], weights))`.  `means` and
 `std_devs` are K x dim.  Used as `Inputs(target = on_mi355x(DeviceGaussianMixture(w, m, s)), reference = ScaledPrecisionNormalLogPotential(p, dim))`."""
@@ -180,6 +185,12 @@ function device_family(t::DeviceSpinGlass, inputs)
     size(t.bonds_right) == (L, L) && size(t.bonds_down) == (L, L) && 2 <= L && L^2 <= 65536 ||
         error("DeviceSpinGlass: bonds_right and bonds_down are L x L with 2 <= L and L^2 <= 65536")
     return (TARGET_SPIN_GLASS, L^2, (t.beta, 0.0, 0.0, 0.0))
+end
+function device_family(t::DeviceSpinGlass3D, inputs)
+    L = size(t.bonds_x, 1)
+    size(t.bonds_x) == (L, L, L) && size(t.bonds_y) == (L, L, L) && size(t.bonds_z) == (L, L, L) && 2 <= L <= 32 && iseven(L) ||
+        error("DeviceSpinGlass3D: bonds_x, bonds_y and bonds_z are L x L x L with L even and in 2..32")
+    return (TARGET_SPIN_GLASS_3D, L^3, (t.beta, 0.0, 0.0, 0.0))
 end
 function device_family(t::DeviceGaussianMixture, inputs)
     K, dim = size(t.means)
@@ -349,6 +360,8 @@ function Pigeons.create_replicas(inputs::Inputs{<:OnDevice}, shared::Shared, sou
     ex = shared.explorer
     if t.target isa DeviceIsing || t.target isa DeviceSpinGlass
         cfg.explorer = EXPLORER_ISING; cfg.slice_n_passes = t.target.n_sweeps
+    elseif t.target isa DeviceSpinGlass3D
+        cfg.explorer = EXPLORER_CHECKERBOARD_METROPOLIS; cfg.slice_n_passes = t.target.n_sweeps
     elseif ex isa Compose
         cfg.explorer = set_explorer!(cfg, ex.first, 1); cfg.explorer2 = set_explorer!(cfg, ex.second, 2)
     else
@@ -404,6 +417,12 @@ function Pigeons.create_replicas(inputs::Inputs{<:OnDevice}, shared::Shared, sou
         g = t.target
         R = Matrix{Int8}(permutedims(g.bonds_right)); D = Matrix{Int8}(permutedims(g.bonds_down))     # row-major for the C ABI
         check(r, ccall((:pte_set_target_spin_glass, libpte), Cint, (Ptr{Cvoid}, Int64, Ptr{Int8}, Ptr{Int8}), r.handle, size(R, 1), R, D))
+    end
+    if t.target isa DeviceSpinGlass3D               # the bond planes as pte_set_target_spin_glass_3d reads them
+        g = t.target
+        c_order(A) = Array{Int8, 3}(permutedims(A, (3, 2, 1)))     # [z, y, x] column-major -> [z][y][x] row-major for the C ABI
+        X = c_order(g.bonds_x); Y = c_order(g.bonds_y); Z = c_order(g.bonds_z)
+        check(r, ccall((:pte_set_target_spin_glass_3d, libpte), Cint, (Ptr{Cvoid}, Int64, Ptr{Int8}, Ptr{Int8}, Ptr{Int8}), r.handle, size(X, 1), X, Y, Z))
     end
     if t.target isa DevicePoissonChangePoint        # the counts as pte_set_target_changepoint reads them
         check(r, ccall((:pte_set_target_changepoint, libpte), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), r.handle, t.target.y, length(t.target.y)))

@@ -8,7 +8,7 @@ pigeons.jl_amd/julia/PigeonsMI355X.jl.
 from ._lib import PteError, LIB_PATH
 from .engine import Engine
 from .pt import (Inputs, PT, pigeons, toy_mvn_target, ScaledPrecisionNormalPath, TestSwapper,
-                 SliceSampler, ToyExplorer, AutoMALA, MALA, AAPS, Compose, GaussianReference, InterpolatingPath, Funnel, GaussianMixture, BayesianGLM, MixtureModelPosterior, HierarchicalNormalMeans, LatentAR1, DenseNormal, SpikeSlabRegression, PoissonChangePoint, IsingLogPotential, SpinGlassLogPotential, IsingMetropolis, CheckerboardMetropolis, ScaledPrecisionNormalLogPotential,
+                 SliceSampler, ToyExplorer, AutoMALA, MALA, AAPS, Compose, GaussianReference, InterpolatingPath, Funnel, GaussianMixture, BayesianGLM, MixtureModelPosterior, HierarchicalNormalMeans, LatentAR1, DenseNormal, SpikeSlabRegression, PoissonChangePoint, IsingLogPotential, SpinGlassLogPotential, SpinGlass3DLogPotential, IsingMetropolis, CheckerboardMetropolis, ScaledPrecisionNormalLogPotential,
                  IdentityPreconditioner, DiagonalPreconditioner, MixDiagonalPreconditioner,
                  record_default, record_online,
                  log_sum_ratio, swap_acceptance_pr, round_trip, index_process, online, traces, energy_ac1,

@@ -29,6 +29,7 @@ TARGET_LATENT_AR1 = 10
 AR1_STOCHASTIC_VOLATILITY, AR1_NORMAL_IDENTITY = 0, 1  # pte_set_target_ar1's likelihood (include/pte.h PTE_AR1_*)
 TARGET_DENSE_NORMAL = 11
 TARGET_SPIN_GLASS = 12
+TARGET_SPIN_GLASS_3D = 13                 # the +-J spin glass on the L^3 cube, CheckerboardMetropolis only
 CHANGEPOINT_FORM_AUTO, CHANGEPOINT_FORM_FULL, CHANGEPOINT_FORM_CACHED = 0, 1, 2      # pte_set_changepoint_form (include/pte.h PTE_CHANGEPOINT_FORM_*)
 GLM_BERNOULLI_LOGIT, GLM_NORMAL_IDENTITY = 0, 1        # pte_set_target_glm's likelihood (include/pte.h PTE_GLM_*)
 EXPLORER_NONE, EXPLORER_TOY, EXPLORER_SLICE, EXPLORER_AUTOMALA, EXPLORER_ISING_METROPOLIS, EXPLORER_MALA, EXPLORER_AAPS = 0, 1, 2, 3, 4, 5, 6
@@ -96,6 +97,7 @@ EXPORTS = [
     "pte_set_target_changepoint", "pte_set_changepoint_form", "pte_set_target_hier", "pte_set_target_ar1",
     "pte_set_target_dense",
     "pte_set_target_spin_glass",
+    "pte_set_target_spin_glass_3d",
 ]
 
 _libs = {}
@@ -181,6 +183,7 @@ def load(path=None):
     L.pte_set_target_ar1.argtypes = [vp, C.c_int32, C.c_int64, dp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]
     L.pte_set_target_dense.argtypes = [vp, C.c_int64, dp, dp]
     L.pte_set_target_spin_glass.argtypes = [vp, C.c_int64, C.POINTER(C.c_int8), C.POINTER(C.c_int8)]
+    L.pte_set_target_spin_glass_3d.argtypes = [vp, C.c_int64, C.POINTER(C.c_int8), C.POINTER(C.c_int8), C.POINTER(C.c_int8)]
     L.pte_get_stream.argtypes = [vp]
     L.pte_get_stream.restype = C.c_void_p
     L.pte_shard_message_bytes.argtypes = [vp]

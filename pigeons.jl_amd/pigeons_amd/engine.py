@@ -155,6 +155,15 @@ class Engine:
         i8 = C.POINTER(C.c_int8)
         self._chk(self.L.pte_set_target_spin_glass(self.h, r.shape[0], r.ctypes.data_as(i8), dn.ctypes.data_as(i8)))
 
+    def set_target_spin_glass_3d(self, bonds_x, bonds_y, bonds_z):
+        """pte_set_target_spin_glass_3d: the three bond planes [L][L][L] (C order [z][y][x], every entry +1 or -1), L^3 = dim"""
+        planes = [np.ascontiguousarray(b, dtype=np.int8) for b in (bonds_x, bonds_y, bonds_z)]
+        x = planes[0]
+        if x.ndim != 3 or x.shape[0] != x.shape[1] or x.shape[0] != x.shape[2] or any(p.shape != x.shape for p in planes):
+            raise ValueError("set_target_spin_glass_3d: bonds_x, bonds_y and bonds_z must be L x L x L (got shapes %s, %s and %s)" % tuple(p.shape for p in planes))
+        i8 = C.POINTER(C.c_int8)
+        self._chk(self.L.pte_set_target_spin_glass_3d(self.h, x.shape[0], *(p.ctypes.data_as(i8) for p in planes)))
+
     # --- hot path
     def explore(self, scan):
         self._chk(self.L.pte_explore(self.h, scan))

@@ -544,6 +544,70 @@ class SpinGlassLogPotential:
         return "SpinGlassLogPotential(beta=%r, base_length=%d)" % (self.beta, self.base_length)
 
 
+class SpinGlass3DLogPotential:
+    """The +-J Edwards-Anderson spin glass on the L x L x L periodic lattice, L even and in 2..32 (the project's own
+    specification): p(state) ∝ exp(beta * S), S = sum s_zyx (bonds_x_zyx s_z,y,x+1 + bonds_y_zyx s_z,y+1,x + bonds_z_zyx s_z+1,y,x) (at L = 2
+    the two bonds between the same pair of sites are distinct terms).  The planes are [L][L][L] in the order [z][y][x]; the reference is
+    beta = 0; states are 0/1 vectors in that (C) order, explored by CheckerboardMetropolis.  Bonds are +-1 only."""
+
+    def __init__(self, beta, bonds_x, bonds_y, bonds_z):
+        names = ("bonds_x", "bonds_y", "bonds_z")
+        planes = []
+        for name, b in zip(names, (bonds_x, bonds_y, bonds_z)):
+            a = np.asarray(b)
+            if a.ndim != 3 or a.shape[0] != a.shape[1] or a.shape[0] != a.shape[2] or a.shape[0] < 2:
+                raise ValueError("SpinGlass3DLogPotential: %s must be L x L x L with L >= 2 (got shape %s)" % (name, a.shape))
+            if a.shape[0] % 2 != 0:
+                raise ValueError("SpinGlass3DLogPotential: base_length must be even (got %s of shape %s): on an odd periodic lattice two sites of "
+                                 "one colour would be neighbours" % (name, a.shape))
+            if a.shape[0] > 32:
+                raise ValueError("SpinGlass3DLogPotential: base_length must be at most 32 (got %s of shape %s): the device holds a row of the "
+                                 "lattice in one 32-bit word" % (name, a.shape))
+            planes.append(a)
+        if planes[0].shape != planes[1].shape or planes[0].shape != planes[2].shape:
+            raise ValueError("SpinGlass3DLogPotential: bonds_x, bonds_y and bonds_z must have the same shape (got %s, %s and %s)"
+                             % tuple(a.shape for a in planes))
+        for name, a in zip(names, planes):
+            bad = np.argwhere(~((a == 1) | (a == -1)))
+            if len(bad):
+                z, y, x = (int(v) for v in bad[0])
+                raise ValueError("SpinGlass3DLogPotential: %s[%d][%d][%d] must be +1 or -1 (got %r): ±J is the supported disorder, "
+                                 "real-valued or diluted couplings are out of scope" % (name, z, y, x, a[z, y, x].item()))
+        self.beta = float(beta)
+        self.bonds_x, self.bonds_y, self.bonds_z = (np.ascontiguousarray(a, dtype=np.int8) for a in planes)
+
+    @classmethod
+    def edwards_anderson(cls, beta, base_length, seed=1):
+        """the three planes drawn +-1 with probability 1/2 each from np.random.default_rng(seed): bonds_x first, then bonds_y, then bonds_z"""
+        rng = np.random.default_rng(seed)
+        L = cls._checked_length(base_length)
+        return cls(beta, *[(2 * rng.integers(0, 2, size=(L, L, L)) - 1).astype(np.int8) for _ in range(3)])
+
+    @classmethod
+    def ferromagnet(cls, beta, base_length):
+        """every bond +1: the 3-D Ising model"""
+        L = cls._checked_length(base_length)
+        return cls(beta, *[np.ones((L, L, L), dtype=np.int8) for _ in range(3)])
+
+    @staticmethod
+    def _checked_length(base_length):
+        L = int(base_length)
+        if L < 2 or L % 2 != 0 or L > 32:
+            raise ValueError("SpinGlass3DLogPotential: base_length must be even and in 2..32 (got %d)" % L)
+        return L
+
+    @property
+    def base_length(self):
+        return int(self.bonds_x.shape[0])
+
+    @property
+    def dim(self):
+        return self.base_length ** 3
+
+    def __repr__(self):
+        return "SpinGlass3DLogPotential(beta=%r, base_length=%d)" % (self.beta, self.base_length)
+
+
 @dataclass
 class IsingMetropolis:
     """examples/ising.jl:91-93"""
@@ -640,6 +704,8 @@ def default_explorer(target):
         return None                    # src/swap/pair_swapper.jl:139
     if isinstance(target, (IsingLogPotential, SpinGlassLogPotential)):
         return IsingMetropolis()       # examples/ising.jl:94
+    if isinstance(target, SpinGlass3DLogPotential):
+        return CheckerboardMetropolis()    # the family's one explorer
     return SliceSampler()              # src/targets/target.jl:20
 
 
@@ -831,6 +897,10 @@ class PT:
             if not isinstance(explorer, (IsingMetropolis, CheckerboardMetropolis)):
                 raise NotImplementedError("the device spin-glass path is explored by IsingMetropolis only (got %r)" % (explorer,))
             kw.update(target=_lib.TARGET_SPIN_GLASS, dim=target.dim, target_params=[target.beta])
+        elif isinstance(target, SpinGlass3DLogPotential):
+            if not isinstance(explorer, CheckerboardMetropolis):
+                raise NotImplementedError("the device 3-D spin-glass path is explored by CheckerboardMetropolis only (got %r)" % (explorer,))
+            kw.update(target=_lib.TARGET_SPIN_GLASS_3D, dim=target.dim, target_params=[target.beta])
         elif isinstance(target, Funnel):
             ref = inputs.reference
             if not isinstance(ref, ScaledPrecisionNormalLogPotential) or ref.dim != target.dim:
@@ -963,6 +1033,9 @@ class PT:
         if isinstance(target, SpinGlassLogPotential):    # every engine (rank) holds the bonds
             for eng in (self.shards.engines if hasattr(self.shards, "engines") else [self.replicas]):
                 eng.set_target_spin_glass(target.bonds_right, target.bonds_down)
+        if isinstance(target, SpinGlass3DLogPotential):  # every engine (rank) holds the bonds
+            for eng in (self.shards.engines if hasattr(self.shards, "engines") else [self.replicas]):
+                eng.set_target_spin_glass_3d(target.bonds_x, target.bonds_y, target.bonds_z)
         if isinstance(target, SpikeSlabRegression):      # every engine (rank) holds the data
             for eng in (self.shards.engines if hasattr(self.shards, "engines") else [self.replicas]):
                 eng.set_target_varsel(target.likelihood_code, target.X, target.y, target.noise_sd, target.inclusion_prob)
