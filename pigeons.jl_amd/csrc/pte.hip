@@ -1201,6 +1201,45 @@ int poisoned_error(pte_engine *h, const char *what) {
 }
 #define PTE_ALIVE(h, what) do { if ((h)->poisoned) return poisoned_error(h, what); } while (0)
 
+// ---- what the pte_set_target_* setters share ----
+// How a setter begins: no handle, a poisoned engine, an engine of another target, in that order.  `wrong_target` is the setter's whole message
+// (with the %d of the engine's target): the text of every refusal stands in this file as the caller reads it.
+int setter_entry(pte_engine *h, const char *setter, int32_t target, const char *wrong_target) {
+    if (!h) return 1;
+    PTE_ALIVE(h, setter);
+    if (h->cfg.target != target) return fail(h, wrong_target, h->cfg.target);
+    return 0;
+}
+
+// How a setter ends its refusals: the family's data on the device, in an allocation made at the first call -- `host` has the size of the largest
+// admissible data, so every later call fits -- and the copy waited for, since `host` is the caller's local.
+template <typename T>
+int upload_once(pte_engine *h, T **p, const std::vector<T> &host) {
+    if (!*p && dev_alloc(h, p, host.size(), false)) return 1;
+    HIP_OK(h, hipMemcpyAsync(*p, host.data(), sizeof(T) * host.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// The constants the Bayesian GLM and variable selection take from (likelihood, n, d columns, prior precision p, noise_sd)
+struct DesignConstants { double c_prior, c_obs, w1, w2; };
+DesignConstants design_constants(int32_t likelihood, int64_t n, int64_t d, double p, double noise_sd) {
+    const double LOG2PI = 1.8378770664093453;
+    const bool normal = likelihood == PTE_GLM_NORMAL_IDENTITY;
+    return {-((double)d / 2.0) * std::log(2.0 * M_PI / p), normal ? -(double)n * (std::log(noise_sd) + 0.5 * LOG2PI) : 0.0,
+            normal ? 1.0 / (noise_sd * noise_sd) : 0.0, normal ? 1.0 / (2.0 * (noise_sd * noise_sd)) : 0.0};
+}
+
+// Every bond of the spin glasses' planes ([d] each) is +1 or -1; `filter` is what the setter's sweep would lose otherwise
+int check_bond_planes(pte_engine *h, const char *setter, const char *filter, int n_planes, const int8_t *const *planes, const char *const *names, int64_t d) {
+    for (int plane = 0; plane < n_planes; ++plane)
+        for (int64_t s = 0; s < d; ++s)
+            if (planes[plane][s] != 1 && planes[plane][s] != -1)
+                return fail(h, "%s: %s[%lld] must be +1 or -1 (got %d): ±J is the supported disorder -- real-valued or diluted "
+                               "couplings break the %s and the bit packing of the sweep", setter, names[plane], (long long)s, (int)planes[plane][s], filter);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2156,10 +2195,7 @@ int pte_scan_loop_stats(const pte_engine *h, int64_t *fused_calls, int64_t *gate
 // The Gaussian-mixture target.  Host, once per call: lw_k = log w_k - logsumexp(log w), c_k = lw_k - sum_i log sigma_ki - (d/2) log 2 pi
 // (index order), inv_ki = 1 / sigma_ki; uploaded as [8][ld] means, [8][ld] inverses (zero-padded), [8] constants.
 int pte_set_target_mixture(pte_engine *h, int64_t n_components, const double *weights, const double *means, const double *std_devs) {
-    if (!h) return 1;
-    PTE_ALIVE(h, "pte_set_target_mixture");
-    if (h->cfg.target != PTE_TARGET_GAUSSIAN_MIXTURE)
-        return fail(h, "pte_set_target_mixture: this engine's target is %d, not PTE_TARGET_GAUSSIAN_MIXTURE", h->cfg.target);
+    if (setter_entry(h, "pte_set_target_mixture", PTE_TARGET_GAUSSIAN_MIXTURE, "pte_set_target_mixture: this engine's target is %d, not PTE_TARGET_GAUSSIAN_MIXTURE")) return 1;
     if (n_components < 1 || n_components > 8)
         return fail(h, "pte_set_target_mixture: the device holds 1..8 components (got %lld)", (long long)n_components);
     if (!weights || !means || !std_devs) return fail(h, "pte_set_target_mixture: null argument");
@@ -2193,9 +2229,7 @@ int pte_set_target_mixture(pte_engine *h, int64_t n_components, const double *we
         }
         buf[(size_t)(16 * ld + k)] = (std::log(weights[k]) - lse) - sl - ((double)d / 2.0) * LOG2PI;
     }
-    if (!h->d_mix && dev_alloc(h, &h->d_mix, buf.size(), false)) return 1;
-    HIP_OK(h, hipMemcpyAsync(h->d_mix, buf.data(), sizeof(double) * buf.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_OK(h, hipStreamSynchronize(h->stream));
+    if (upload_once(h, &h->d_mix, buf)) return 1;
     h->mix_K = (int)K;
     return refresh_path_stats(h);                                  // suff / suff2 of the current states
 }
@@ -2204,10 +2238,7 @@ int pte_set_target_mixture(pte_engine *h, int64_t n_components, const double *we
 // (normal), 1 / sigma^2, 1 / (2 sigma^2); uploaded as Xc [d][n_pad] (column-major), Xr [n][ld] (row-major, the state row's stride) and
 // y [n_pad], zero-padded, into one allocation sized once for the largest n this d admits.
 int pte_set_target_glm(pte_engine *h, int32_t likelihood, int64_t n_obs, const double *X, const double *y, double noise_sd) {
-    if (!h) return 1;
-    PTE_ALIVE(h, "pte_set_target_glm");
-    if (h->cfg.target != PTE_TARGET_BAYESIAN_GLM)
-        return fail(h, "pte_set_target_glm: this engine's target is %d, not PTE_TARGET_BAYESIAN_GLM", h->cfg.target);
+    if (setter_entry(h, "pte_set_target_glm", PTE_TARGET_BAYESIAN_GLM, "pte_set_target_glm: this engine's target is %d, not PTE_TARGET_BAYESIAN_GLM")) return 1;
     if (likelihood != PTE_GLM_BERNOULLI_LOGIT && likelihood != PTE_GLM_NORMAL_IDENTITY)
         return fail(h, "pte_set_target_glm: likelihood must be PTE_GLM_BERNOULLI_LOGIT (0) or PTE_GLM_NORMAL_IDENTITY (1) (got %d)", likelihood);
     const int64_t d = h->d, ld = h->dev.ld;
@@ -2236,17 +2267,12 @@ int pte_set_target_glm(pte_engine *h, int32_t likelihood, int64_t n_obs, const d
         for (int64_t j = 0; j < d; ++j) { xc[j * n_pad + i] = X[i * d + j]; xr[i * ld + j] = X[i * d + j]; }
         yy[i] = y[i];
     }
-    const double p = h->cfg.target_params[0], LOG2PI = 1.8378770664093453;
-    if (!h->d_glm && dev_alloc(h, &h->d_glm, buf.size(), false)) return 1;
-    HIP_OK(h, hipMemcpyAsync(h->d_glm, buf.data(), sizeof(double) * buf.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_OK(h, hipStreamSynchronize(h->stream));
+    if (upload_once(h, &h->d_glm, buf)) return 1;
     GlmParams &g = h->glm;
     g.xc = h->d_glm; g.xr = h->d_glm + xc_len; g.y = h->d_glm + xc_len + xr_len;
     g.n = (int)n; g.n_pad = (int)n_pad; g.ld = ld;
-    g.c_prior = -((double)d / 2.0) * std::log(2.0 * M_PI / p);
-    g.c_obs = likelihood == PTE_GLM_NORMAL_IDENTITY ? -(double)n * (std::log(noise_sd) + 0.5 * LOG2PI) : 0.0;
-    g.w1 = likelihood == PTE_GLM_NORMAL_IDENTITY ? 1.0 / (noise_sd * noise_sd) : 0.0;
-    g.w2 = likelihood == PTE_GLM_NORMAL_IDENTITY ? 1.0 / (2.0 * (noise_sd * noise_sd)) : 0.0;
+    const DesignConstants c = design_constants(likelihood, n, d, h->cfg.target_params[0], noise_sd);
+    g.c_prior = c.c_prior; g.c_obs = c.c_obs; g.w1 = c.w1; g.w2 = c.w2;
     h->glm_lik = likelihood;
     return refresh_path_stats(h);                                  // suff / suff2 of the current states
 }
@@ -2255,10 +2281,7 @@ int pte_set_target_glm(pte_engine *h, int32_t likelihood, int64_t n_obs, const d
 // log 2 - log pi - log tau_scale, 1 / tau_scale; y, 1 / sigma and log sigma are uploaded indexed by state coordinate (entries 0, 1 and d.. zero)
 // into one allocation of 3 x 512 doubles.
 int pte_set_target_hier(pte_engine *h, int32_t parameterization, int64_t n_groups, const double *y, const double *sigma, double mu_sd, double tau_scale) {
-    if (!h) return 1;
-    PTE_ALIVE(h, "pte_set_target_hier");
-    if (h->cfg.target != PTE_TARGET_HIERARCHICAL_NORMAL)
-        return fail(h, "pte_set_target_hier: this engine's target is %d, not PTE_TARGET_HIERARCHICAL_NORMAL", h->cfg.target);
+    if (setter_entry(h, "pte_set_target_hier", PTE_TARGET_HIERARCHICAL_NORMAL, "pte_set_target_hier: this engine's target is %d, not PTE_TARGET_HIERARCHICAL_NORMAL")) return 1;
     if (parameterization != PTE_HIER_CENTERED && parameterization != PTE_HIER_NONCENTERED)
         return fail(h, "pte_set_target_hier: parameterization must be PTE_HIER_CENTERED (0) or PTE_HIER_NONCENTERED (1) (got %d)", parameterization);
     const int64_t d = h->d;
@@ -2279,9 +2302,7 @@ int pte_set_target_hier(pte_engine *h, int32_t parameterization, int64_t n_group
         buf[(size_t)(HIER_DATA_LEN + 2 + j)] = 1.0 / sigma[j];
         buf[(size_t)(2 * HIER_DATA_LEN + 2 + j)] = std::log(sigma[j]);
     }
-    if (!h->d_hier && dev_alloc(h, &h->d_hier, buf.size(), false)) return 1;
-    HIP_OK(h, hipMemcpyAsync(h->d_hier, buf.data(), sizeof(double) * buf.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_OK(h, hipStreamSynchronize(h->stream));
+    if (upload_once(h, &h->d_hier, buf)) return 1;
     HierParams &p = h->hier;
     p.y = h->d_hier; p.isig = h->d_hier + HIER_DATA_LEN; p.lsig = h->d_hier + 2 * HIER_DATA_LEN;
     p.n = (int)n_groups;
@@ -2295,10 +2316,7 @@ int pte_set_target_hier(pte_engine *h, int32_t parameterization, int64_t n_group
 // uploaded indexed by state coordinate (entries 0..2 and d.. zero) into one allocation of 2 x 512 doubles.
 int pte_set_target_ar1(pte_engine *h, int32_t likelihood, int64_t n_obs, const double *y, double obs_sd, double mu_sd, double phi_loc,
                        double phi_scale, double sigma_scale) {
-    if (!h) return 1;
-    PTE_ALIVE(h, "pte_set_target_ar1");
-    if (h->cfg.target != PTE_TARGET_LATENT_AR1)
-        return fail(h, "pte_set_target_ar1: this engine's target is %d, not PTE_TARGET_LATENT_AR1", h->cfg.target);
+    if (setter_entry(h, "pte_set_target_ar1", PTE_TARGET_LATENT_AR1, "pte_set_target_ar1: this engine's target is %d, not PTE_TARGET_LATENT_AR1")) return 1;
     if (likelihood != PTE_AR1_STOCHASTIC_VOLATILITY && likelihood != PTE_AR1_NORMAL_IDENTITY)
         return fail(h, "pte_set_target_ar1: likelihood must be PTE_AR1_STOCHASTIC_VOLATILITY (0) or PTE_AR1_NORMAL_IDENTITY (1) (got %d)", likelihood);
     const int64_t d = h->d;
@@ -2319,9 +2337,7 @@ int pte_set_target_ar1(pte_engine *h, int32_t likelihood, int64_t n_obs, const d
         buf[(size_t)(3 + t)] = y[t];
         buf[(size_t)(AR1_DATA_LEN + 3 + t)] = y[t] * y[t];
     }
-    if (!h->d_ar1 && dev_alloc(h, &h->d_ar1, buf.size(), false)) return 1;
-    HIP_OK(h, hipMemcpyAsync(h->d_ar1, buf.data(), sizeof(double) * buf.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_OK(h, hipStreamSynchronize(h->stream));
+    if (upload_once(h, &h->d_ar1, buf)) return 1;
     Ar1Params &p = h->ar1;
     p.y = h->d_ar1; p.y2 = h->d_ar1 + AR1_DATA_LEN;
     p.n = (int)n_obs;
@@ -2380,9 +2396,7 @@ int pte_set_target_dense(pte_engine *h, int64_t dim, const double *mean, const d
         buf[(size_t)(d * ld + i)] = precision[i * d + i];
         buf[(size_t)((d + 1) * ld + i)] = mean[i];
     }
-    if (!h->d_dense && dev_alloc(h, &h->d_dense, buf.size(), false)) return 1;
-    HIP_OK(h, hipMemcpyAsync(h->d_dense, buf.data(), sizeof(double) * buf.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_OK(h, hipStreamSynchronize(h->stream));
+    if (upload_once(h, &h->d_dense, buf)) return 1;
     DenseParams &p = h->dense;
     p.q = h->d_dense; p.diag = h->d_dense + d * ld; p.mean = h->d_dense + (d + 1) * ld;
     p.n = (int)d; p.ld = (int)ld;
@@ -2394,21 +2408,14 @@ int pte_set_target_dense(pte_engine *h, int64_t dim, const double *mean, const d
 // the right bond is -1, bit 2: the down bond is -1) and, where base_length % 32 == 0, the two planes bit-packed like the lattice -- and suff
 // of every slot recounted under the new bonds.  May be called again: the allocation is made once.  A refused call leaves the engine as it was.
 int pte_set_target_spin_glass(pte_engine *h, int64_t base_length, const int8_t *bonds_right, const int8_t *bonds_down) {
-    if (!h) return 1;
-    PTE_ALIVE(h, "pte_set_target_spin_glass");
-    if (h->cfg.target != PTE_TARGET_SPIN_GLASS)
-        return fail(h, "pte_set_target_spin_glass: this engine's target is %d, not PTE_TARGET_SPIN_GLASS", h->cfg.target);
+    if (setter_entry(h, "pte_set_target_spin_glass", PTE_TARGET_SPIN_GLASS, "pte_set_target_spin_glass: this engine's target is %d, not PTE_TARGET_SPIN_GLASS")) return 1;
     const int64_t d = h->d, L = (int64_t)std::llround(std::sqrt((double)d));
     if (base_length != L)
         return fail(h, "pte_set_target_spin_glass: base_length must be the engine's %lld (dim = %lld) (got %lld)", (long long)L, (long long)d, (long long)base_length);
     if (!bonds_right || !bonds_down) return fail(h, "pte_set_target_spin_glass: null argument");
-    for (int plane = 0; plane < 2; ++plane) {
-        const int8_t *b = plane == 0 ? bonds_right : bonds_down;
-        for (int64_t s = 0; s < d; ++s)
-            if (b[s] != 1 && b[s] != -1)
-                return fail(h, "pte_set_target_spin_glass: %s[%lld] must be +1 or -1 (got %d): ±J is the supported disorder -- real-valued or diluted "
-                               "couplings break the two-threshold filter and the bit packing of the sweep", plane == 0 ? "bonds_right" : "bonds_down", (long long)s, (int)b[s]);
-    }
+    const int8_t *const planes[2] = {bonds_right, bonds_down};
+    static const char *const names[2] = {"bonds_right", "bonds_down"};
+    if (check_bond_planes(h, "pte_set_target_spin_glass", "two-threshold filter", 2, planes, names, d)) return 1;
     HIP_OK(h, hipSetDevice(h->cfg.device));
     const int64_t NW = d / 32;
     const bool packed = L % 32 == 0;
@@ -2419,11 +2426,7 @@ int pte_set_target_spin_glass(pte_engine *h, int64_t base_length, const int8_t *
         jb[(size_t)s] = (unsigned char)((r << 1) | (dn << 2));
         if (packed) { jw[(size_t)(s >> 5)] |= r << (s & 31); jw[(size_t)(NW + (s >> 5))] |= dn << (s & 31); }
     }
-    if (!h->d_sg_bytes && dev_alloc(h, &h->d_sg_bytes, (size_t)d, false)) return 1;
-    if (packed && !h->d_sg_words && dev_alloc(h, &h->d_sg_words, (size_t)(2 * NW), false)) return 1;
-    HIP_OK(h, hipMemcpyAsync(h->d_sg_bytes, jb.data(), jb.size(), hipMemcpyHostToDevice, h->stream));
-    if (packed) HIP_OK(h, hipMemcpyAsync(h->d_sg_words, jw.data(), sizeof(unsigned) * jw.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_OK(h, hipStreamSynchronize(h->stream));
+    if (upload_once(h, &h->d_sg_bytes, jb) || (packed && upload_once(h, &h->d_sg_words, jw))) return 1;
     SpinGlassParams &p = h->spinglass;
     p.L = (int)L; p.n_steps = h->cfg.slice_n_passes; p.beta_target = h->cfg.target_params[0];
     p.jb = h->d_sg_bytes; p.jw = packed ? h->d_sg_words : nullptr;
@@ -2437,29 +2440,20 @@ int pte_set_target_spin_glass(pte_engine *h, int64_t base_length, const int8_t *
 // words, row r = z L + y of a plane in one word, bit x set where the bond of site (z, y, x) is -1 -- and suff of every slot recounted under the
 // new bonds.  May be called again: the allocation is made once.  A refused call leaves the engine as it was.
 int pte_set_target_spin_glass_3d(pte_engine *h, int64_t base_length, const int8_t *bonds_x, const int8_t *bonds_y, const int8_t *bonds_z) {
-    if (!h) return 1;
-    PTE_ALIVE(h, "pte_set_target_spin_glass_3d");
-    if (h->cfg.target != PTE_TARGET_SPIN_GLASS_3D)
-        return fail(h, "pte_set_target_spin_glass_3d: this engine's target is %d, not PTE_TARGET_SPIN_GLASS_3D", h->cfg.target);
+    if (setter_entry(h, "pte_set_target_spin_glass_3d", PTE_TARGET_SPIN_GLASS_3D, "pte_set_target_spin_glass_3d: this engine's target is %d, not PTE_TARGET_SPIN_GLASS_3D")) return 1;
     const int64_t d = h->d, L = lattice3d_base_length(d), R = L * L;
     if (base_length != L)
         return fail(h, "pte_set_target_spin_glass_3d: base_length must be the engine's %lld (dim = %lld) (got %lld)", (long long)L, (long long)d, (long long)base_length);
     if (!bonds_x || !bonds_y || !bonds_z) return fail(h, "pte_set_target_spin_glass_3d: null argument");
     const int8_t *const planes[3] = {bonds_x, bonds_y, bonds_z};
     static const char *const names[3] = {"bonds_x", "bonds_y", "bonds_z"};
-    for (int plane = 0; plane < 3; ++plane)
-        for (int64_t s = 0; s < d; ++s)
-            if (planes[plane][s] != 1 && planes[plane][s] != -1)
-                return fail(h, "pte_set_target_spin_glass_3d: %s[%lld] must be +1 or -1 (got %d): ±J is the supported disorder -- real-valued or diluted "
-                               "couplings break the threshold filter and the bit packing of the sweep", names[plane], (long long)s, (int)planes[plane][s]);
+    if (check_bond_planes(h, "pte_set_target_spin_glass_3d", "threshold filter", 3, planes, names, d)) return 1;
     HIP_OK(h, hipSetDevice(h->cfg.device));
     std::vector<unsigned> jw((size_t)(3 * R), 0u);
     for (int plane = 0; plane < 3; ++plane)
         for (int64_t s = 0; s < d; ++s)
             if (planes[plane][s] < 0) jw[(size_t)(plane * R + s / L)] |= 1u << (s % L);
-    if (!h->d_sg3_words && dev_alloc(h, &h->d_sg3_words, (size_t)(3 * R), false)) return 1;
-    HIP_OK(h, hipMemcpyAsync(h->d_sg3_words, jw.data(), sizeof(unsigned) * jw.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_OK(h, hipStreamSynchronize(h->stream));
+    if (upload_once(h, &h->d_sg3_words, jw)) return 1;
     SpinGlass3DParams &p = h->spinglass3d;
     p.L = (int)L; p.n_steps = h->cfg.slice_n_passes; p.beta_target = h->cfg.target_params[0];
     p.jw = h->d_sg3_words;
@@ -2472,10 +2466,7 @@ int pte_set_target_spin_glass_3d(pte_engine *h, int64_t base_length, const int8_
 // The posterior of a finite mixture model.  Host, once per call: c_prior = -(d/2) log(2 pi / p), c_obs = -(n/2) log(2 pi); y is
 // uploaded zero-padded into one allocation sized once for the largest n.
 int pte_set_target_mixture_model(pte_engine *h, int64_t n_obs, const double *y) {
-    if (!h) return 1;
-    PTE_ALIVE(h, "pte_set_target_mixture_model");
-    if (h->cfg.target != PTE_TARGET_MIXTURE_MODEL)
-        return fail(h, "pte_set_target_mixture_model: this engine's target is %d, not PTE_TARGET_MIXTURE_MODEL", h->cfg.target);
+    if (setter_entry(h, "pte_set_target_mixture_model", PTE_TARGET_MIXTURE_MODEL, "pte_set_target_mixture_model: this engine's target is %d, not PTE_TARGET_MIXTURE_MODEL")) return 1;
     const int64_t n_max = 65536;
     if (n_obs < 1 || n_obs > n_max)
         return fail(h, "pte_set_target_mixture_model: the device holds 1..65536 observations (got %lld)", (long long)n_obs);
@@ -2486,9 +2477,7 @@ int pte_set_target_mixture_model(pte_engine *h, int64_t n_obs, const double *y) 
     const int64_t n = n_obs, n_pad = (n + 63) & ~(int64_t)63, d = h->d;
     std::vector<double> buf((size_t)n_max, 0.0);
     for (int64_t i = 0; i < n; ++i) buf[(size_t)i] = y[i];
-    if (!h->d_mixmodel && dev_alloc(h, &h->d_mixmodel, buf.size(), false)) return 1;
-    HIP_OK(h, hipMemcpyAsync(h->d_mixmodel, buf.data(), sizeof(double) * buf.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_OK(h, hipStreamSynchronize(h->stream));
+    if (upload_once(h, &h->d_mixmodel, buf)) return 1;
     const double p = h->cfg.target_params[0];
     MixModelParams &m = h->mixmodel;
     m.y = h->d_mixmodel; m.n = (int)n; m.n_pad = (int)n_pad; m.nd = (double)n;
@@ -2502,10 +2491,7 @@ int pte_set_target_mixture_model(pte_engine *h, int64_t n_obs, const double *y) 
 // (column-major) and y [n_pad], zero-padded, into one allocation sized once for the largest n this d admits.
 int pte_set_target_varsel(pte_engine *h, const double *X, const double *y, int64_t n_obs, int64_t d, int32_t likelihood, double noise_sd,
                           double inclusion_prob) {
-    if (!h) return 1;
-    PTE_ALIVE(h, "pte_set_target_varsel");
-    if (h->cfg.target != PTE_TARGET_VARIABLE_SELECTION)
-        return fail(h, "pte_set_target_varsel: this engine's target is %d, not PTE_TARGET_VARIABLE_SELECTION", h->cfg.target);
+    if (setter_entry(h, "pte_set_target_varsel", PTE_TARGET_VARIABLE_SELECTION, "pte_set_target_varsel: this engine's target is %d, not PTE_TARGET_VARIABLE_SELECTION")) return 1;
     if (likelihood != PTE_GLM_BERNOULLI_LOGIT && likelihood != PTE_GLM_NORMAL_IDENTITY)
         return fail(h, "pte_set_target_varsel: likelihood must be PTE_GLM_BERNOULLI_LOGIT (0) or PTE_GLM_NORMAL_IDENTITY (1) (got %d)", likelihood);
     if (2 * d != h->d)
@@ -2537,16 +2523,12 @@ int pte_set_target_varsel(pte_engine *h, const double *X, const double *y, int64
         for (int64_t j = 0; j < d; ++j) xc[j * n_pad + i] = X[i * d + j];
         yy[i] = y[i];
     }
-    const double p = h->cfg.target_params[0], LOG2PI = 1.8378770664093453;
-    if (!h->d_varsel && dev_alloc(h, &h->d_varsel, buf.size(), false)) return 1;
-    HIP_OK(h, hipMemcpyAsync(h->d_varsel, buf.data(), sizeof(double) * buf.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_OK(h, hipStreamSynchronize(h->stream));
+    if (upload_once(h, &h->d_varsel, buf)) return 1;
     VarselParams &v = h->varsel;
     v.xc = h->d_varsel; v.y = h->d_varsel + xc_len;
     v.n = (int)n; v.n_pad = (int)n_pad; v.d = (int)d;
-    v.c_prior = -((double)d / 2.0) * std::log(2.0 * M_PI / p);
-    v.c_obs = likelihood == PTE_GLM_NORMAL_IDENTITY ? -(double)n * (std::log(noise_sd) + 0.5 * LOG2PI) : 0.0;
-    v.w2 = likelihood == PTE_GLM_NORMAL_IDENTITY ? 1.0 / (2.0 * (noise_sd * noise_sd)) : 0.0;
+    const DesignConstants c = design_constants(likelihood, n, d, h->cfg.target_params[0], noise_sd);
+    v.c_prior = c.c_prior; v.c_obs = c.c_obs; v.w2 = c.w2;
     v.log_pi = std::log(inclusion_prob); v.log_1mpi = std::log(1.0 - inclusion_prob);
     h->varsel_lik = likelihood;
     return refresh_path_stats(h);                                  // suff / suff2 of the current states
@@ -2556,10 +2538,7 @@ int pte_set_target_varsel(pte_engine *h, const double *X, const double *y, int64
 // -((K+1)/2) log(2 pi / p), c_tau = -K log(n + 1) and c_obs = -sum_i lgamma(y_i + 1), sequential in i; the table goes into one allocation
 // sized once for the largest n.
 int pte_set_target_changepoint(pte_engine *h, const double *y, int64_t n_obs) {
-    if (!h) return 1;
-    PTE_ALIVE(h, "pte_set_target_changepoint");
-    if (h->cfg.target != PTE_TARGET_CHANGE_POINT)
-        return fail(h, "pte_set_target_changepoint: this engine's target is %d, not PTE_TARGET_CHANGE_POINT", h->cfg.target);
+    if (setter_entry(h, "pte_set_target_changepoint", PTE_TARGET_CHANGE_POINT, "pte_set_target_changepoint: this engine's target is %d, not PTE_TARGET_CHANGE_POINT")) return 1;
     if (n_obs < 1 || n_obs > 65536)
         return fail(h, "pte_set_target_changepoint: the device holds 1..65536 observations (got %lld)", (long long)n_obs);
     if (!y) return fail(h, "pte_set_target_changepoint: null argument");
@@ -2571,9 +2550,7 @@ int pte_set_target_changepoint(pte_engine *h, const double *y, int64_t n_obs) {
     std::vector<double> C((size_t)65537, 0.0);
     double c_obs = 0.0;
     for (int64_t i = 0; i < n; ++i) { C[i + 1] = C[i] + y[i]; c_obs = c_obs - std::lgamma(y[i] + 1.0); }
-    if (!h->d_changepoint && dev_alloc(h, &h->d_changepoint, C.size(), false)) return 1;
-    HIP_OK(h, hipMemcpyAsync(h->d_changepoint, C.data(), sizeof(double) * C.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_OK(h, hipStreamSynchronize(h->stream));
+    if (upload_once(h, &h->d_changepoint, C)) return 1;
     const double p = h->cfg.target_params[0];
     ChangepointParams &v = h->changepoint;
     v.C = h->d_changepoint; v.n = (int)n; v.K = (int)K;
@@ -2585,10 +2562,7 @@ int pte_set_target_changepoint(pte_engine *h, const double *y, int64_t n_obs) {
 
 // Which evaluation form k_explore_changepoint takes from now on (PTE_CHANGEPOINT_FORM_*); both give the same bits.
 int pte_set_changepoint_form(pte_engine *h, int32_t form) {
-    if (!h) return 1;
-    PTE_ALIVE(h, "pte_set_changepoint_form");
-    if (h->cfg.target != PTE_TARGET_CHANGE_POINT)
-        return fail(h, "pte_set_changepoint_form: this engine's target is %d, not PTE_TARGET_CHANGE_POINT", h->cfg.target);
+    if (setter_entry(h, "pte_set_changepoint_form", PTE_TARGET_CHANGE_POINT, "pte_set_changepoint_form: this engine's target is %d, not PTE_TARGET_CHANGE_POINT")) return 1;
     if (form != CHANGEPOINT_FORM_AUTO && form != CHANGEPOINT_FORM_FULL && form != CHANGEPOINT_FORM_CACHED)
         return fail(h, "pte_set_changepoint_form: form must be PTE_CHANGEPOINT_FORM_AUTO (0), _FULL (1) or _CACHED (2) (got %d)", form);
     h->changepoint_form = form;
