@@ -5,25 +5,22 @@ chain's draw, whole runs against the exact change-point posterior and evidence f
 checkpoint / resume and replacing the data.
 
 RNG words, Integer coordinates and step counts are compared exactly; Float64 coordinates to 1e-12 and log densities to 1e-13 relative: the
-one difference between the device and the restatement is exp (ocml against libm, an ulp), every other operation is the same IEEE one."""
+one difference between the device and the restatement is exp (ocml against libm, an ulp), every other operation is the same IEEE one.
+These are tighter than the figures of tests/family_gpu.py, whose shared checks take them as arguments."""
 import math
 
 import numpy as np
 import pytest
 
+import family_gpu as G
 import oracle as O
 import changepoint_ref as R
+from family_gpu import P  # noqa: F401  (the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
 X_RTOL = 1e-12
 LP_RTOL = 1e-13
-
-
-@pytest.fixture(scope="module")
-def P():
-    import pigeons_amd
-    return pigeons_amd
 
 
 def _data(n, K, seed=1):
@@ -57,16 +54,6 @@ def _random_states(pt, N, K, n, seed, scale=1.0):
     _, _, rng = eng.states()
     eng.set_states(x, chain, rng)
     return betas, x, chain, rng
-
-
-def _log_densities(pt, N, dim):
-    eng = pt.replicas
-    eng.explore(1)
-    eng.swap(1)                                   # (a scan ends at its swap: the traces count it from there)
-    eng.reduce()
-    tr = eng.traces()
-    assert tr.shape == (1, N, dim + 1)
-    return tr[0]
 
 
 def test_state_calls_need_the_data_and_the_setter_validates(P):
@@ -118,17 +105,16 @@ def test_log_density_at_every_beta(P, n, K):
     N, prec, dim = 12, 0.5, 2 * K + 1
     pt = _pt(P, y, K, prec, N, n_passes=0, record=[P.traces], extended_traces=True)
     betas, x, chain, _ = _random_states(pt, N, K, n, seed=K, scale=0.7)
-    tr = _log_densities(pt, N, dim)
+    tr = G.log_densities(pt, N, dim)
     cp = R.ChangePoint(y, K, prec)
     kept = 0
     for c in range(N):
         tau = tr[c, K + 1:dim]
         assert np.all(tau == np.floor(tau)) and tau.min() >= 0 and tau.max() <= n
         kept += int(any(np.array_equal(tr[c, :dim], x[i]) for i in range(N)))
-        want = R.ChangePointChain(cp, betas[c], prec).path_lp(tr[c, :dim])
-        assert math.isfinite(want)
-        assert math.isclose(tr[c, dim], want, rel_tol=LP_RTOL), (c, betas[c], tr[c, dim], want)
-    assert kept >= N - 1                                     # every state but the reference chain's fresh draw is one of those handed in
+    wants = G.assert_log_density_at_every_beta(tr, betas, dim, lambda beta: R.ChangePointChain(cp, beta, prec).path_lp, LP_RTOL, abs_tol=0.0)
+    assert all(math.isfinite(want) for want in wants)
+    assert kept >= N - 1                                    # every state but the reference chain's fresh draw is one of those handed in
     taus = tr[:, K + 1:dim]
     assert np.any(taus == 0.0) and np.any(taus == float(n))
     if K >= 2:
@@ -221,15 +207,9 @@ def test_both_forms_give_the_same_bits(P):
 
 
 # ---- whole runs ------------------------------------------------------------------------------------------------------------------------
-def _run(P, target, prec, seed, n_rounds, checkpoint=False, record=None):
-    """pigeons' round loop by hand: the schedule the last round ran with is kept (adapt replaces it after the round)"""
-    pt = P.PT(P.Inputs(target=target, reference=P.ScaledPrecisionNormalLogPotential(prec, target.n_rates), n_chains=16,
-                       n_rounds=n_rounds, seed=seed, explorer=P.SliceSampler(), checkpoint=checkpoint, extended_traces=True, show_report=False,
-                       record=record or [P.round_trip, P.online, P.traces, P.log_sum_ratio, P.index_process]))
-    while P.next_round(pt):
-        red = P.run_one_round(pt)
-        pt = P.adapt(pt, red)
-    return pt
+def _run(P, target, prec, seed, n_rounds):
+    return G.run_rounds(P, target, prec, seed, n_rounds, P.SliceSampler(), n_chains=16, ref_dim=target.n_rates,
+                        record=["round_trip", "online", "traces", "log_sum_ratio", "index_process"])[0]
 
 
 _RUN = dict(y=[3, 0, 1, 2, 0, 0, 0, 1, 8, 6, 2, 3, 8, 6, 8, 4, 3, 2, 4, 2, 2, 2, 1, 3], K=2, prec=0.25, n_rounds=10, seeds=(1, 2, 3), B=32)
@@ -309,37 +289,16 @@ def _inputs(P, seed=1, n_rounds=5, checkpoint=False):
 
 
 def test_two_runs_are_equal_bit_for_bit(P):
-    a, b = P.pigeons(P.PT(_inputs(P, seed=3))), P.pigeons(P.PT(_inputs(P, seed=3)))
-    xa, ca, ga = a.replicas.states(); xb, cb, gb = b.replicas.states()
-    assert np.array_equal(xa, xb) and np.array_equal(ca, cb) and np.array_equal(ga, gb)
-    assert np.array_equal(a.reduced_recorders.traces, b.reduced_recorders.traces)
-    assert np.array_equal(a.shared.tempering.schedule.grids, b.shared.tempering.schedule.grids)
-    assert P.stepping_stone(a) == P.stepping_stone(b)
+    a = G.assert_two_runs_equal(P, lambda: _inputs(P, seed=3))
     assert np.all(np.isfinite(a.reduced_recorders.traces)) and len(np.unique(a.reduced_recorders.traces[:, 6:11])) > 10
 
 
 def test_sharded_equals_single_engine(P):
-    mk = lambda: _inputs(P, seed=4, n_rounds=4)
-    one, many = P.PT(mk()), P.PT(mk(), n_shards=2)
-    for _ in range(4):
-        assert P.next_round(one) and P.next_round(many)
-        ra = P.run_one_round(one); P.adapt(one, ra)
-        rb = P.run_one_round(many); P.adapt(many, rb)
-        assert np.array_equal(ra.index_process, rb.index_process) and np.array_equal(ra.traces, rb.traces)
-    xa, ca, ga = one.replicas.states(); xb, cb, gb = many.shards.states()
-    assert np.array_equal(xa, xb) and np.array_equal(ca, cb) and np.array_equal(ga, gb)
+    G.assert_sharded_equals_single(P, lambda: _inputs(P, seed=4, n_rounds=4), n_shards=2)
 
 
 def test_checkpoint_resume_equals_uninterrupted(P, tmp_path):
-    straight = P.pigeons(P.PT(_inputs(P, seed=5, n_rounds=6)))
-    folder = str(tmp_path / "exec")
-    P.pigeons(P.PT(_inputs(P, seed=5, n_rounds=3, checkpoint=True)), exec_folder=folder)
-    resumed = P.pigeons(P.load_checkpoint(folder, n_rounds_increment=3))
-    ra, rb = straight.reduced_recorders, resumed.reduced_recorders
-    assert np.array_equal(ra.index_process, rb.index_process) and np.array_equal(ra.traces, rb.traces)
-    assert np.array_equal(straight.shared.tempering.schedule.grids, resumed.shared.tempering.schedule.grids)
-    xa, ca, ga = straight.replicas.states(); xb, cb, gb = resumed.replicas.states()
-    assert np.array_equal(xa, xb) and np.array_equal(ca, cb) and np.array_equal(ga, gb)
+    G.assert_checkpoint_resume(P, lambda **kw: _inputs(P, seed=5, **kw), tmp_path)
 
 
 def test_new_data_replaces_the_old(P):
@@ -350,10 +309,7 @@ def test_new_data_replaces_the_old(P):
     pt = _pt(P, y1, K, prec, N, n_passes=0, record=[P.traces], extended_traces=True)
     betas, _, _, _ = _random_states(pt, N, K, 60, seed=3, scale=0.5)
     pt.replicas.set_target_changepoint(y2)
-    tr = _log_densities(pt, N, 2 * K + 1)
+    tr = G.log_densities(pt, N, 2 * K + 1)
     new, old = R.ChangePoint(y2, K, prec), R.ChangePoint(y1, K, prec)
-    for c in range(N):
-        want = R.ChangePointChain(new, betas[c], prec).path_lp(tr[c, :2 * K + 1])
-        assert math.isclose(tr[c, 2 * K + 1], want, rel_tol=LP_RTOL), (c, tr[c, 2 * K + 1], want)
-        if betas[c] > 0:
-            assert not math.isclose(tr[c, 2 * K + 1], R.ChangePointChain(old, betas[c], prec).path_lp(tr[c, :2 * K + 1]), rel_tol=1e-6)
+    G.assert_log_density_at_every_beta(tr, betas, 2 * K + 1, lambda beta: R.ChangePointChain(new, beta, prec).path_lp, LP_RTOL, abs_tol=0.0)
+    G.assert_log_density_is_not(tr, betas, 2 * K + 1, lambda beta: R.ChangePointChain(old, beta, prec).path_lp)

@@ -3,56 +3,24 @@ NumPy restatement (tests/dense_ref.py), which restates the FULL evaluation only 
 the log density at every chain's beta, one SliceSampler and one MALA transition of every replica from random states, whole runs against the
 closed-form law of every chain, determinism, Compose, the chain-sharded engine and checkpoint / resume.
 
-Tolerances are those of tests/test_gpu_hier.py: RNG words are compared exactly; states and recorders to 1e-9 relative, log densities to 1e-11
-relative with 1e-11 absolute.  The test matrices are Q = U diag(lambda) U' with log-spaced lambda and cond <= 100, for which the
-restatement's own summation-order error is a few 1e-16 relative: the tolerance tests the kernel, not the inputs."""
+The shared checks and their tolerances (RTOL, LP_RTOL, and why) are in tests/family_gpu.py; log densities get 1e-11 absolute with the
+relative figure.  The test matrices are Q = U diag(lambda) U' with log-spaced lambda and cond <= 100, for which the restatement's own
+summation-order error is a few 1e-16 relative: the tolerance tests the kernel, not the inputs."""
 import math
 
 import numpy as np
 import pytest
 
-import aaps_ref as A
 import dense_ref as R
-import mixture_ref as M
-import oracle as O
+import family_gpu as G
+from family_gpu import LP_RTOL, P  # noqa: F401  (P: the module's fixture)
 
 pytestmark = pytest.mark.gpu
-
-RTOL = 1e-9
-LP_RTOL = 1e-11
-
-
-@pytest.fixture(scope="module")
-def P():
-    import pigeons_amd
-    return pigeons_amd
 
 
 def _target(d, seed, cond=100.0):
     """(mean, Q): the mean N(0, 1), the spectrum log-spaced over cond"""
     return np.random.default_rng(1000 + seed).normal(0.0, 1.0, d), R.spectrum_matrix(d, cond, seed)
-
-
-def _random_states(pt, N, d, seed, scale=1.5):
-    eng = pt.replicas
-    g = np.random.default_rng(seed)
-    betas = np.concatenate([[0.0], np.sort(g.uniform(0.0, 1.0, N - 2)), [1.0]])
-    eng.set_schedule(betas)
-    x = g.normal(0.0, scale, (N, d))
-    chain = g.permutation(N).astype(np.int64)
-    _, _, rng = eng.states()
-    eng.set_states(x, chain, rng)
-    return betas, x, chain, rng
-
-
-def _log_densities(P, pt, N, d):
-    eng = pt.replicas
-    eng.explore(1)
-    eng.swap(1)                                   # (a scan ends at its swap: the traces count it from there)
-    eng.reduce()
-    tr = eng.traces()
-    assert tr.shape == (1, N, d + 1)
-    return tr[0]
 
 
 def _pt(P, mean, Q, prec, N, explorer, **kw):
@@ -118,25 +86,22 @@ def test_a_refused_call_changes_nothing_and_new_data_replaces_the_old(P):
     d, N, prec = 7, 8, 0.5
     m1, Q1 = _target(d, 31)
     pt = _pt(P, m1, Q1, prec, N, P.SliceSampler(n_passes=1), record=[P.traces], extended_traces=True)
-    betas, _, _, _ = _random_states(pt, N, d, seed=3, scale=0.5)
+    betas, _, _, _ = G.random_states(pt, N, d, seed=3, scale=0.5)
     with pytest.raises(P.PteError, match="not positive definite"):
         pt.replicas.set_target_dense(m1, -Q1)
     with pytest.raises(P.PteError, match="symmetric bit for bit"):
         pt.replicas.set_target_dense(m1, np.triu(Q1))
-    tr = _log_densities(P, pt, N, d)
+    tr = G.log_densities(pt, N, d)
     old = R.Dense(m1, Q1)
-    for c in range(N):
-        want = R.DenseChain(old, betas[c], prec).path_lp(tr[c, :d])
-        assert math.isclose(tr[c, d], want, rel_tol=LP_RTOL, abs_tol=1e-11), (c, tr[c, d], want)
+    G.assert_log_density_at_every_beta(tr, betas, d, lambda beta: R.DenseChain(old, beta, prec).path_lp, LP_RTOL, abs_tol=1e-11)
     m2, Q2 = _target(d, 32, cond=20.0)
     pt = _pt(P, m1, Q1, prec, N, P.SliceSampler(n_passes=1), record=[P.traces], extended_traces=True)
-    betas, _, _, _ = _random_states(pt, N, d, seed=3, scale=0.5)
+    betas, _, _, _ = G.random_states(pt, N, d, seed=3, scale=0.5)
     pt.replicas.set_target_dense(m2, Q2)
-    tr = _log_densities(P, pt, N, d)
+    tr = G.log_densities(pt, N, d)
     new = R.Dense(m2, Q2)
+    G.assert_log_density_at_every_beta(tr, betas, d, lambda beta: R.DenseChain(new, beta, prec).path_lp, LP_RTOL, abs_tol=1e-11)
     for c in range(N):
-        want = R.DenseChain(new, betas[c], prec).path_lp(tr[c, :d])
-        assert math.isclose(tr[c, d], want, rel_tol=LP_RTOL, abs_tol=1e-11), (c, tr[c, d], want)
         if betas[c] > 0:
             was = R.DenseChain(old, betas[c], prec).path_lp(tr[c, :d])
             assert abs(tr[c, d] - was) > 1e-6 and not math.isclose(tr[c, d], was, rel_tol=1e-6)
@@ -150,15 +115,12 @@ def test_log_density_at_every_beta(P, d):
     mean, Q = _target(d, d)
     N, prec = 8, 0.5
     pt = _pt(P, mean, Q, prec, N, P.SliceSampler(n_passes=1), record=[P.traces], extended_traces=True)
-    betas, x0, _, _ = _random_states(pt, N, d, seed=d, scale=1.5)
-    tr = _log_densities(P, pt, N, d)
+    betas, x0, _, _ = G.random_states(pt, N, d, seed=d, scale=1.5)
+    tr = G.log_densities(pt, N, d)
     dense = R.Dense(mean, Q)
-    moved = 0
-    for c in range(N):
-        want = R.DenseChain(dense, betas[c], prec).path_lp(tr[c, :d])
-        assert math.isclose(tr[c, d], want, rel_tol=LP_RTOL, abs_tol=1e-11), (c, betas[c], tr[c, d], want)
-        moved += int(not any(np.array_equal(tr[c, :d], x0[i]) for i in range(N)))
-    assert moved == N                                              # every chain's state is the pass's, not the one that was set
+    G.assert_log_density_at_every_beta(tr, betas, d, lambda beta: R.DenseChain(dense, beta, prec).path_lp, LP_RTOL, abs_tol=1e-11)
+    moved = sum(int(not any(np.array_equal(tr[c, :d], x0[i]) for i in range(N))) for c in range(N))
+    assert moved == N                                             # every chain's state is the pass's, not the one that was set
 
 
 @pytest.mark.parametrize("d,w,p,n_passes", [(2, 10.0, 20, 1), (11, 10.0, 20, 1), (69, 10.0, 20, 1), (11, 0.25, 3, 1), (65, 10.0, 20, 3)])
@@ -168,26 +130,10 @@ def test_one_slice_transition_parity(P, d, w, p, n_passes):
     mean, Q = _target(d, 7 * d)
     N, prec = 10, 0.5
     pt = _pt(P, mean, Q, prec, N, P.SliceSampler(w=w, p=p, n_passes=n_passes))
-    betas, x, chain, rng = _random_states(pt, N, d, seed=d, scale=1.0)
-    eng = pt.replicas
-    eng.explore(1)
-    x1, c1, r1 = eng.states()
-    eng.reduce()
-    am, an, ss, sn = eng.explorer_stats()
-    assert np.array_equal(c1, chain)
+    betas, x, chain, rng = G.random_states(pt, N, d, seed=d, scale=1.0)
     dense = R.Dense(mean, Q)
-    for i in range(N):
-        c = int(chain[i])
-        if c == 0:
-            continue
-        r = O.OracleRng(state=(int(rng[i, 0]), int(rng[i, 1])))
-        sl = O.MixedSliceSampler(R.DenseChain(dense, betas[c], prec).path_lp, np.zeros(d, dtype=np.int32), w=w, p=p, n_passes=n_passes)
-        yv = x[i].copy()
-        sl.step(r, yv)
-        assert int(r1[i, 0]) == r.state[0] and int(r1[i, 1]) == r.state[1], (i, c)
-        np.testing.assert_allclose(x1[i], yv, rtol=RTOL, atol=1e-12, err_msg="replica %d chain %d" % (i, c))
-        assert an[c] == sl.stats.acc_n and sn[c] == sl.stats.steps_n and ss[c] == sl.stats.steps_sum, (i, c)
-        np.testing.assert_allclose(am[c], sl.stats.acc_mean, rtol=RTOL)
+    G.assert_slice_transition(pt.replicas, betas, x, chain, rng, lambda beta: R.DenseChain(dense, beta, prec).path_lp,
+                              w=w, p=p, n_passes=n_passes)
 
 
 MALA_STEP = {7: 0.5, 64: 0.4, 65: 0.4}        # chosen on the restatement (below the stability limit 2 / sqrt(lambda_max) = 0.63): it accepts about three proposals in four
@@ -198,42 +144,14 @@ MALA_STEP = {7: 0.5, 64: 0.4, 65: 0.4}        # chosen on the restatement (below
 def test_one_mala_transition_parity(P, d, precond):
     """(d = 64: the whole-block instantiation; 65: two blocks, ragged).  The restatement runs refresh by refresh, so the test sees that it
     accepts some proposals and rejects others."""
-    mode, pc = {"identity": (0, P.IdentityPreconditioner()), "diagonal": (1, P.DiagonalPreconditioner()),
-                "mix": (2, P.MixDiagonalPreconditioner())}[precond]
     mean, Q = _target(d, 3 * d)
     N, step, prec = 10, MALA_STEP[d], 1.0
-    ex = P.MALA(step_size=step, preconditioner=pc)
+    ex = G.mala_explorer(P, step, precond)
     pt = _pt(P, 0.3 * mean, Q, prec, N, ex)
-    betas, x, chain, rng = _random_states(pt, N, d, seed=d, scale=0.5)
-    eng = pt.replicas
-    std = np.random.default_rng(d).uniform(0.7, 1.4, d)
-    eng.set_explorer_adaptation(step, std)
-    eng.explore(2)
-    x1, c1, r1 = eng.states()
-    eng.reduce()
-    am, an, ss, sn = eng.explorer_stats()
-    n_refresh = ex.base_n_refresh * int(math.ceil(d ** ex.exponent_n_refresh))
+    betas, x, chain, rng = G.random_states(pt, N, d, seed=d, scale=0.5)
     dense = R.Dense(0.3 * mean, Q)
-    accepted = rejected = 0
-    for i in range(N):
-        c = int(chain[i])
-        if c == 0:
-            continue
-        r = O.OracleRng(state=(int(rng[i, 0]), int(rng[i, 1])))
-        Mv = A.build_preconditioner(r, d, mode, 1.0 / 3.0, 1.0 / 3.0, std)
-        ch = R.DenseChain(dense, betas[c], prec)
-        xc, acc_sum = x[i].copy(), 0.0
-        for _ in range(n_refresh):                                 # (the density and gradient at the start are pure functions of the state: the same bits)
-            res = M.mala_transition(xc, r, ch, step, 1, Mv)
-            took = not np.array_equal(res["x"], xc)
-            accepted += int(took); rejected += int(not took)
-            xc, acc_sum = res["x"], acc_sum + res["acc_sum"]
-        assert int(r1[i, 0]) == r.state[0] and int(r1[i, 1]) == r.state[1], (i, c)
-        np.testing.assert_allclose(x1[i], xc, rtol=RTOL, atol=1e-12, err_msg="replica %d chain %d" % (i, c))
-        assert an[c] == n_refresh and sn[c] == n_refresh and ss[c] == n_refresh, (i, c)
-        np.testing.assert_allclose(am[c], acc_sum / n_refresh, rtol=RTOL, atol=1e-12)
-    print("MALA d = %d, %s: %d proposals accepted, %d rejected" % (d, precond, accepted, rejected))
-    assert accepted > 0 and rejected > 0
+    G.assert_mala_transition(pt.replicas, ex, precond, betas, x, chain, rng, lambda beta: R.DenseChain(dense, beta, prec),
+                             std_range=(0.7, 1.4), form="by_refresh", label="MALA d = %d, %s" % (d, precond))
 
 
 # ---- whole runs ------------------------------------------------------------------------------------------------------------------------
@@ -242,41 +160,16 @@ EXACT_COV = EXACT_D[:, None] * (0.6 * np.ones((6, 6)) + 0.4 * np.eye(6)) * EXACT
 EXACT_MEAN = np.array([2.0, -1.0, 0.5, 3.0, -2.5, 1.0])
 
 
-def _run(P, target, prec, seed, n_rounds, explorer, n_chains=10):
-    """pigeons' round loop by hand: the schedule the last round ran with is kept (adapt replaces it after the round)"""
-    pt = P.PT(P.Inputs(target=target, reference=P.ScaledPrecisionNormalLogPotential(prec, target.dim), n_chains=n_chains,
-                       n_rounds=n_rounds, seed=seed, explorer=explorer, extended_traces=True, show_report=False,
-                       record=[P.round_trip, P.online, P.traces, P.log_sum_ratio, P.index_process]))
-    grids = None
-    while P.next_round(pt):
-        grids = np.array(pt.shared.tempering.schedule.grids)
-        red = P.run_one_round(pt)
-        pt = P.adapt(pt, red)
-    return pt, grids
+def _run(P, target, prec, seed, n_rounds, explorer):
+    return G.run_rounds(P, target, prec, seed, n_rounds, explorer, n_chains=10,
+                        record=["round_trip", "online", "traces", "log_sum_ratio", "index_process"])
 
 
-def _batches(a, B):
-    T = a.shape[0] // B * B
-    return a[:T].reshape(B, T // B, *a.shape[1:])
-
-
-def _stepping_stone_se(tr, betas, dense, prec, B=8):
-    """Monte Carlo standard error of stepping_stone by batch means, the construction of tests/test_gpu_hier.py: the last round's scans
-    (extended traces, every chain) in B consecutive batches, the estimator -- (forward + backward) / 2 of
-    sum_k log mean_t exp(+-(beta_k+1 - beta_k) (target - reference)(x_t)) -- on each, se = sd(batch estimates) / sqrt(B).
-    (Plain sums: this feeds an error estimate, not a parity check.)"""
+def _stepping_stone_se(tr, betas, dense, prec):
+    """G.stepping_stone_se on this family's target - reference (plain sums: this feeds an error estimate, not a parity check)"""
     X = tr[:, :, :dense.d]
     Z = X - dense.mean
-    delta = dense.c - 0.5 * np.einsum("tci,ij,tcj->tc", Z, dense.Q, Z) + 0.5 * prec * (X * X).sum(-1)
-    db = _batches(delta, B)                                       # [B][t][chain]
-    dbeta = np.diff(betas)
-
-    def lme(a):
-        m = a.max(axis=1, keepdims=True)
-        return (m + np.log(np.mean(np.exp(a - m), axis=1, keepdims=True)))[:, 0]
-    fw = lme(db[:, :, :-1] * dbeta).sum(-1)
-    bw = -lme(-db[:, :, 1:] * dbeta).sum(-1)
-    return float(np.std((fw + bw) / 2.0, ddof=1) / math.sqrt(B))
+    return G.stepping_stone_se(dense.c - 0.5 * np.einsum("tci,ij,tcj->tc", Z, dense.Q, Z) + 0.5 * prec * (X * X).sum(-1), betas)
 
 
 @pytest.mark.parametrize("seed", [1, 2])
@@ -300,7 +193,7 @@ def test_run_against_the_closed_forms(P, explorer, seed):
     for c in range(10):                                           # every chain's mean vector
         want, _ = R.DenseChain(dense, grids[c], prec).chain_moments()
         xc = tr_all[:, c, :d]
-        se = _batches(xc, 16).mean(axis=1).std(axis=0, ddof=1) / 4.0
+        se = G.batches(xc, 16).mean(axis=1).std(axis=0, ddof=1) / 4.0
         z = np.abs(xc.mean(axis=0) - want) / se
         zmax = max(zmax, z.max())
         assert np.all(z < 5.0), (c, grids[c], z, xc.mean(axis=0), want, se)
@@ -314,7 +207,7 @@ def test_run_against_the_closed_forms(P, explorer, seed):
     var = [cov[i, i] for i in range(d)] + [m[i] ** 2 * cov[j, j] + m[j] ** 2 * cov[i, i] + 2 * m[i] * m[j] * cov[i, j] + cov[i, i] * cov[j, j] + cov[i, j] ** 2
                                          for i, j in pairs]
     sd = np.sqrt(np.array(var))
-    se = _batches(q, 16).mean(axis=1).std(axis=0, ddof=1) / 4.0
+    se = G.batches(q, 16).mean(axis=1).std(axis=0, ddof=1) / 4.0
     z = np.abs(q.mean(axis=0) - want) / se
     se_ss = _stepping_stone_se(tr_all, grids, dense, prec)
     est = P.stepping_stone(pt) - t.evidence_offset(prec)
@@ -335,47 +228,22 @@ def _inputs(P, seed=1, explorer=None, n_rounds=5, checkpoint=False):
 
 @pytest.mark.parametrize("explorer", ["slice", "automala"])
 def test_two_runs_are_equal_bit_for_bit(P, explorer):
-    mk = lambda: P.pigeons(P.PT(_inputs(P, seed=3, explorer=P.SliceSampler() if explorer == "slice" else P.AutoMALA())))
-    a, b = mk(), mk()
-    xa, ca, ga = a.replicas.states(); xb, cb, gb = b.replicas.states()
-    assert np.array_equal(xa, xb) and np.array_equal(ca, cb) and np.array_equal(ga, gb)
-    assert np.array_equal(a.reduced_recorders.traces, b.reduced_recorders.traces)
-    assert np.array_equal(a.shared.tempering.schedule.grids, b.shared.tempering.schedule.grids)
-    assert P.stepping_stone(a) == P.stepping_stone(b)
+    G.assert_two_runs_equal(P, lambda: _inputs(P, seed=3, explorer=P.SliceSampler() if explorer == "slice" else P.AutoMALA()))
 
 
 def test_compose_slice_automala_runs(P):
-    pt = P.pigeons(P.PT(_inputs(P, seed=2, explorer=P.Compose(P.SliceSampler(), P.AutoMALA()))))
-    assert pt.replicas.kernel_name() == "k_explore_dense_slice"
-    assert np.all(np.isfinite(pt.reduced_recorders.traces)) and np.isfinite(P.stepping_stone(pt))
-    m, n = pt.reduced_recorders.explorer_acceptance_pr
-    assert np.all(n[1:] > 0)                                       # both explorers recorded on every tempered chain
+    G.assert_compose_runs(P, _inputs(P, seed=2, explorer=P.Compose(P.SliceSampler(), P.AutoMALA())), "k_explore_dense_slice")
     # (no round-trip count here: 12 chains need 22 scans for one and the last of the 5 rounds has 32; test_run_against_the_closed_forms asks it of 10 rounds)
 
 
 @pytest.mark.parametrize("explorer", ["slice", "automala"])
 def test_sharded_equals_single_engine(P, explorer):
     mk = lambda: _inputs(P, seed=4, n_rounds=4, explorer=P.SliceSampler() if explorer == "slice" else P.AutoMALA())
-    one, many = P.PT(mk()), P.PT(mk(), n_shards=2)
-    for _ in range(4):
-        assert P.next_round(one) and P.next_round(many)
-        ra = P.run_one_round(one); P.adapt(one, ra)
-        rb = P.run_one_round(many); P.adapt(many, rb)
-        assert np.array_equal(ra.index_process, rb.index_process) and np.array_equal(ra.traces, rb.traces)
-    xa, ca, ga = one.replicas.states(); xb, cb, gb = many.shards.states()
-    assert np.array_equal(xa, xb) and np.array_equal(ca, cb) and np.array_equal(ga, gb)
+    G.assert_sharded_equals_single(P, mk, n_shards=2)
 
 
 @pytest.mark.parametrize("explorer", ["slice", "mala"])
 def test_checkpoint_resume_equals_uninterrupted(P, tmp_path, explorer):
     """(the slice kernel's swap statistics are recomputed in full from the stored state, so a resumed run sees the same bits)"""
     ex = lambda: P.SliceSampler() if explorer == "slice" else P.MALA(step_size=0.2)
-    straight = P.pigeons(P.PT(_inputs(P, seed=5, n_rounds=6, explorer=ex())))
-    folder = str(tmp_path / "exec")
-    P.pigeons(P.PT(_inputs(P, seed=5, n_rounds=3, explorer=ex(), checkpoint=True)), exec_folder=folder)
-    resumed = P.pigeons(P.load_checkpoint(folder, n_rounds_increment=3))
-    ra, rb = straight.reduced_recorders, resumed.reduced_recorders
-    assert np.array_equal(ra.index_process, rb.index_process) and np.array_equal(ra.traces, rb.traces)
-    assert np.array_equal(straight.shared.tempering.schedule.grids, resumed.shared.tempering.schedule.grids)
-    xa, ca, ga = straight.replicas.states(); xb, cb, gb = resumed.replicas.states()
-    assert np.array_equal(xa, xb) and np.array_equal(ca, cb) and np.array_equal(ga, gb)
+    G.assert_checkpoint_resume(P, lambda **kw: _inputs(P, seed=5, explorer=ex(), **kw), tmp_path)

@@ -3,42 +3,22 @@
 invariance where the interpolated densities are Gaussian (K = 1), whole runs on a bimodal mixture, determinism, Compose, the chain-sharded
 engine and checkpoint / resume.
 
-RNG words are compared exactly; states and recorders to 1e-9 relative -- the device's exp / log differ from libm by an ulp."""
+The shared checks and their tolerances (RTOL, and why) are in tests/family_gpu.py; log densities are held to 1e-12 here."""
 import math
 
 import numpy as np
 import pytest
 
-import aaps_ref as A
+import family_gpu as G
 import mixture_ref as R
-import oracle as O
+from family_gpu import P  # noqa: F401  (the module's fixture)
 
 pytestmark = pytest.mark.gpu
-
-RTOL = 1e-9
-
-
-@pytest.fixture(scope="module")
-def P():
-    import pigeons_amd
-    return pigeons_amd
 
 
 def _mixture(K, d, seed=1, spread=2.0):
     g = np.random.default_rng(seed)
     return g.uniform(0.3, 2.0, K), g.normal(0.0, spread, (K, d)), g.uniform(0.5, 1.5, (K, d))
-
-
-def _random_states(P, pt, N, d, seed, scale=1.5):
-    eng = pt.replicas
-    g = np.random.default_rng(seed)
-    betas = np.concatenate([[0.0], np.sort(g.uniform(0.0, 1.0, N - 2)), [1.0]])
-    eng.set_schedule(betas)
-    x = g.normal(0.0, scale, (N, d))
-    chain = g.permutation(N).astype(np.int64)
-    _, _, rng = eng.states()
-    eng.set_states(x, chain, rng)
-    return betas, x, chain, rng
 
 
 def test_state_calls_need_the_mixture(P):
@@ -65,17 +45,10 @@ def test_log_density_at_every_beta(P, K, d):
     t = P.GaussianMixture(w, mu, sd)
     pt = P.PT(P.Inputs(target=t, reference=P.ScaledPrecisionNormalLogPotential(0.25, d), n_chains=N, n_rounds=2, explorer=P.SliceSampler(n_passes=1),
                        record=[P.traces], extended_traces=True, show_report=False))
-    betas, _, _, _ = _random_states(P, pt, N, d, seed=d)
-    eng = pt.replicas
-    eng.explore(1)
-    eng.swap(1)                                   # (a scan ends at its swap: the traces count it from there)
-    eng.reduce()
-    tr = eng.traces()
-    assert tr.shape == (1, N, d + 1)
+    betas, _, _, _ = G.random_states(pt, N, d, seed=d, scale=1.5)
+    tr = G.log_densities(pt, N, d)
     mix = R.Mixture(w, mu, sd)
-    for c in range(N):
-        want = R.MixtureChain(mix, betas[c], 0.25).path_lp(tr[0, c, :d])
-        assert math.isclose(tr[0, c, d], want, rel_tol=1e-12, abs_tol=1e-12), (c, betas[c], tr[0, c, d], want)
+    G.assert_log_density_at_every_beta(tr, betas, d, lambda beta: R.MixtureChain(mix, beta, 0.25).path_lp, 1e-12, abs_tol=1e-12)
 
 
 @pytest.mark.parametrize("K,d", [(2, 3), (4, 40), (8, 70)])
@@ -84,61 +57,22 @@ def test_one_slice_transition_parity(P, K, d):
     N = 10
     pt = P.PT(P.Inputs(target=P.GaussianMixture(w, mu, sd), reference=P.ScaledPrecisionNormalLogPotential(0.5, d), n_chains=N, n_rounds=2,
                        explorer=P.SliceSampler(), show_report=False))
-    betas, x, chain, rng = _random_states(P, pt, N, d, seed=K)
-    eng = pt.replicas
-    eng.explore(1)
-    x1, c1, r1 = eng.states()
-    eng.reduce()
-    am, an, ss, sn = eng.explorer_stats()
-    assert np.array_equal(c1, chain)
+    betas, x, chain, rng = G.random_states(pt, N, d, seed=K, scale=1.5)
     mix = R.Mixture(w, mu, sd)
-    for i in range(N):
-        c = int(chain[i])
-        if c == 0:
-            continue
-        r = O.OracleRng(state=(int(rng[i, 0]), int(rng[i, 1])))
-        s = O.MixedSliceSampler(R.MixtureChain(mix, betas[c], 0.5).path_lp, np.zeros(d, dtype=np.int32))
-        y = x[i].copy()
-        s.step(r, y)
-        assert int(r1[i, 0]) == r.state[0] and int(r1[i, 1]) == r.state[1], (i, c)
-        np.testing.assert_allclose(x1[i], y, rtol=RTOL, atol=1e-12, err_msg="replica %d chain %d" % (i, c))
-        assert an[c] == s.stats.acc_n and sn[c] == s.stats.steps_n and ss[c] == s.stats.steps_sum, (i, c)
-        np.testing.assert_allclose(am[c], s.stats.acc_mean, rtol=RTOL)
+    G.assert_slice_transition(pt.replicas, betas, x, chain, rng, lambda beta: R.MixtureChain(mix, beta, 0.5).path_lp)
 
 
 @pytest.mark.parametrize("K,d,precond", [(2, 6, "mix"), (3, 64, "diagonal"), (8, 128, "identity"), (4, 300, "mix")])
 def test_one_mala_transition_parity(P, K, d, precond):
-    mode, pc = {"identity": (0, P.IdentityPreconditioner()), "diagonal": (1, P.DiagonalPreconditioner()),
-                "mix": (2, P.MixDiagonalPreconditioner())}[precond]
     w, mu, sd = _mixture(K, d, seed=3 * K + d, spread=1.0)
     N, step = 10, 0.3
-    ex = P.MALA(step_size=step, preconditioner=pc)
+    ex = G.mala_explorer(P, step, precond)
     pt = P.PT(P.Inputs(target=P.GaussianMixture(w, mu, sd), reference=P.ScaledPrecisionNormalLogPotential(1.0, d), n_chains=N, n_rounds=2,
                        explorer=ex, show_report=False))
-    betas, x, chain, rng = _random_states(P, pt, N, d, seed=d, scale=1.0)
-    eng = pt.replicas
-    std = np.random.default_rng(d).uniform(0.5, 2.0, d)
-    eng.set_explorer_adaptation(step, std)
-    eng.explore(2)
-    x1, c1, r1 = eng.states()
-    eng.reduce()
-    am, an, ss, sn = eng.explorer_stats()
-    n_refresh = ex.base_n_refresh * int(math.ceil(d ** ex.exponent_n_refresh))
+    betas, x, chain, rng = G.random_states(pt, N, d, seed=d, scale=1.0)
     mix = R.Mixture(w, mu, sd)
-    moved = 0
-    for i in range(N):
-        c = int(chain[i])
-        if c == 0:
-            continue
-        r = O.OracleRng(state=(int(rng[i, 0]), int(rng[i, 1])))
-        M = A.build_preconditioner(r, d, mode, 1.0 / 3.0, 1.0 / 3.0, std)
-        res = R.mala_transition(x[i], r, R.MixtureChain(mix, betas[c], 1.0), step, n_refresh, M)
-        assert int(r1[i, 0]) == r.state[0] and int(r1[i, 1]) == r.state[1], (i, c)
-        np.testing.assert_allclose(x1[i], res["x"], rtol=RTOL, atol=1e-12, err_msg="replica %d chain %d" % (i, c))
-        assert an[c] == res["acc_n"] and sn[c] == n_refresh and ss[c] == res["steps"], (i, c)
-        np.testing.assert_allclose(am[c], res["acc_sum"] / res["acc_n"], rtol=RTOL, atol=1e-12)
-        moved += int(not np.array_equal(res["x"], x[i]))
-    assert moved > 0
+    G.assert_mala_transition(pt.replicas, ex, precond, betas, x, chain, rng, lambda beta: R.MixtureChain(mix, beta, 1.0),
+                             std_range=(0.5, 2.0), form="whole")
 
 
 @pytest.mark.parametrize("explorer", ["slice", "mala", "automala"])
@@ -197,44 +131,20 @@ def test_whole_run_on_a_bimodal_mixture(P):
 
 
 def test_two_runs_are_equal_bit_for_bit(P):
-    a, b = P.pigeons(P.PT(_bimodal(P, seed=3, n_rounds=6))), P.pigeons(P.PT(_bimodal(P, seed=3, n_rounds=6)))
-    xa, ca, ga = a.replicas.states(); xb, cb, gb = b.replicas.states()
-    assert np.array_equal(xa, xb) and np.array_equal(ca, cb) and np.array_equal(ga, gb)
-    assert np.array_equal(a.reduced_recorders.traces, b.reduced_recorders.traces)
-    assert np.array_equal(a.shared.tempering.schedule.grids, b.shared.tempering.schedule.grids)
-    assert P.stepping_stone(a) == P.stepping_stone(b)
+    G.assert_two_runs_equal(P, lambda: _bimodal(P, seed=3, n_rounds=6))
 
 
 def test_compose_slice_automala_runs(P):
-    pt = P.pigeons(P.PT(_bimodal(P, seed=2, n_rounds=6, explorer=P.Compose(P.SliceSampler(), P.AutoMALA()))))
-    assert pt.replicas.kernel_name() == "k_explore_mixture"
-    assert np.all(np.isfinite(pt.reduced_recorders.traces)) and np.isfinite(P.stepping_stone(pt))
-    m, n = pt.reduced_recorders.explorer_acceptance_pr
-    assert np.all(n[1:] > 0)
+    G.assert_compose_runs(P, _bimodal(P, seed=2, n_rounds=6, explorer=P.Compose(P.SliceSampler(), P.AutoMALA())), "k_explore_mixture")
 
 
 @pytest.mark.parametrize("explorer", ["slice", "automala"])
 def test_sharded_equals_single_engine(P, explorer):
     mk = lambda: _bimodal(P, seed=4, n_rounds=4, explorer=P.SliceSampler() if explorer == "slice" else P.AutoMALA())
-    one, many = P.PT(mk()), P.PT(mk(), n_shards=2)
-    for _ in range(4):
-        assert P.next_round(one) and P.next_round(many)
-        ra = P.run_one_round(one); P.adapt(one, ra)
-        rb = P.run_one_round(many); P.adapt(many, rb)
-        assert np.array_equal(ra.index_process, rb.index_process) and np.array_equal(ra.traces, rb.traces)
-    xa, ca, ga = one.replicas.states(); xb, cb, gb = many.shards.states()
-    assert np.array_equal(xa, xb) and np.array_equal(ca, cb) and np.array_equal(ga, gb)
+    G.assert_sharded_equals_single(P, mk, n_shards=2)
 
 
 def test_checkpoint_resume_equals_uninterrupted(P, tmp_path):
     import dataclasses
-    straight = P.pigeons(P.PT(_bimodal(P, seed=5, n_rounds=6, explorer=P.MALA(step_size=0.5))))
-    folder = str(tmp_path / "exec")
-    P.pigeons(P.PT(_bimodal(P, seed=5, n_rounds=3, explorer=P.MALA(step_size=0.5), checkpoint=True)), exec_folder=folder)
-    resumed = P.pigeons(P.load_checkpoint(folder, n_rounds_increment=3))
-    ra, rb = straight.reduced_recorders, resumed.reduced_recorders
-    assert np.array_equal(ra.index_process, rb.index_process) and np.array_equal(ra.traces, rb.traces)
-    assert np.array_equal(straight.shared.tempering.schedule.grids, resumed.shared.tempering.schedule.grids)
-    xa, ca, ga = straight.replicas.states(); xb, cb, gb = resumed.replicas.states()
-    assert np.array_equal(xa, xb) and np.array_equal(ca, cb) and np.array_equal(ga, gb)
+    resumed = G.assert_checkpoint_resume(P, lambda **kw: _bimodal(P, seed=5, explorer=P.MALA(step_size=0.5), **kw), tmp_path)
     assert dataclasses.is_dataclass(resumed.inputs)

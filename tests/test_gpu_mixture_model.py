@@ -3,29 +3,19 @@ restatement (tests/mixture_model_ref.py): the log density at every chain's beta,
 from random states, the evidence of a small data set against prior Monte Carlo, label switching on two well-separated clusters,
 determinism, Compose, the chain-sharded engine, checkpoint / resume and replacing the data.
 
-RNG words are compared exactly; states and recorders to 1e-9 relative, log densities to 1e-11 relative -- the device's exp / log differ
-from libm by an ulp."""
+The shared checks and their tolerances (RTOL, LP_RTOL, and why) are in tests/family_gpu.py."""
 import math
 
 import numpy as np
 import pytest
 
-import aaps_ref as A
+import family_gpu as G
 import mixture_model_ref as R
-import mixture_ref as M
-import oracle as O
+from family_gpu import LP_RTOL, P  # noqa: F401  (P: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
-RTOL = 1e-9
-LP_RTOL = 1e-11
 Y8 = [-1.6, -1.3, -1.0, -0.9, 0.8, 1.1, 1.3, 1.7]
-
-
-@pytest.fixture(scope="module")
-def P():
-    import pigeons_amd
-    return pigeons_amd
 
 
 def _data(n, seed=1):
@@ -33,28 +23,6 @@ def _data(n, seed=1):
     g = np.random.default_rng(seed)
     y = np.where(g.uniform(size=n) < 0.4, g.normal(-1.0, 0.4, n), g.normal(0.8, 0.7, n))
     return (y - y.mean()) / (y.std() if n > 1 else 1.0)
-
-
-def _random_states(pt, N, d, seed, scale=1.0):
-    eng = pt.replicas
-    g = np.random.default_rng(seed)
-    betas = np.concatenate([[0.0], np.sort(g.uniform(0.0, 1.0, N - 2)), [1.0]])
-    eng.set_schedule(betas)
-    x = g.normal(0.0, scale, (N, d))
-    chain = g.permutation(N).astype(np.int64)
-    _, _, rng = eng.states()
-    eng.set_states(x, chain, rng)
-    return betas, x, chain, rng
-
-
-def _log_densities(P, pt, N, d):
-    eng = pt.replicas
-    eng.explore(1)
-    eng.swap(1)                                   # (a scan ends at its swap: the traces count it from there)
-    eng.reduce()
-    tr = eng.traces()
-    assert tr.shape == (1, N, d + 1)
-    return tr[0]
 
 
 def test_state_calls_need_the_data_and_the_setter_validates(P):
@@ -96,12 +64,10 @@ def test_log_density_at_every_beta(P, n, K):
     d, N, prec = 3 * K, 12, 0.5
     pt = P.PT(P.Inputs(target=P.MixtureModelPosterior(y, K), reference=P.ScaledPrecisionNormalLogPotential(prec, d),
                        n_chains=N, n_rounds=2, explorer=P.SliceSampler(n_passes=1), record=[P.traces], extended_traces=True, show_report=False))
-    betas, _, _, _ = _random_states(pt, N, d, seed=d, scale=0.5)
-    tr = _log_densities(P, pt, N, d)
+    betas, _, _, _ = G.random_states(pt, N, d, seed=d, scale=0.5)
+    tr = G.log_densities(pt, N, d)
     model = R.MixtureModel(y, K, prec)
-    for c in range(N):
-        want = R.MixtureModelChain(model, betas[c], prec).path_lp(tr[c, :d])
-        assert math.isclose(tr[c, d], want, rel_tol=LP_RTOL, abs_tol=1e-11), (c, betas[c], tr[c, d], want)
+    G.assert_log_density_at_every_beta(tr, betas, d, lambda beta: R.MixtureModelChain(model, beta, prec).path_lp, LP_RTOL, abs_tol=1e-11)
 
 
 @pytest.mark.parametrize("n,K", [(50, 1), (70, 2), (130, 3), (200, 8)])
@@ -110,96 +76,33 @@ def test_one_slice_transition_parity(P, n, K):
     d, N, prec = 3 * K, 10, 0.5
     pt = P.PT(P.Inputs(target=P.MixtureModelPosterior(y, K), reference=P.ScaledPrecisionNormalLogPotential(prec, d), n_chains=N,
                        n_rounds=2, explorer=P.SliceSampler(), show_report=False))
-    betas, x, chain, rng = _random_states(pt, N, d, seed=n, scale=1.0)
-    eng = pt.replicas
-    eng.explore(1)
-    x1, c1, r1 = eng.states()
-    eng.reduce()
-    am, an, ss, sn = eng.explorer_stats()
-    assert np.array_equal(c1, chain)
+    betas, x, chain, rng = G.random_states(pt, N, d, seed=n, scale=1.0)
     model = R.MixtureModel(y, K, prec)
-    for i in range(N):
-        c = int(chain[i])
-        if c == 0:
-            continue
-        r = O.OracleRng(state=(int(rng[i, 0]), int(rng[i, 1])))
-        s = O.MixedSliceSampler(R.MixtureModelChain(model, betas[c], prec).path_lp, np.zeros(d, dtype=np.int32))
-        yv = x[i].copy()
-        s.step(r, yv)
-        assert int(r1[i, 0]) == r.state[0] and int(r1[i, 1]) == r.state[1], (i, c)
-        np.testing.assert_allclose(x1[i], yv, rtol=RTOL, atol=1e-12, err_msg="replica %d chain %d" % (i, c))
-        assert an[c] == s.stats.acc_n and sn[c] == s.stats.steps_n and ss[c] == s.stats.steps_sum, (i, c)
-        np.testing.assert_allclose(am[c], s.stats.acc_mean, rtol=RTOL)
+    G.assert_slice_transition(pt.replicas, betas, x, chain, rng, lambda beta: R.MixtureModelChain(model, beta, prec).path_lp)
 
 
 @pytest.mark.parametrize("n,K,precond", [(40, 2, "mix"), (64, 3, "diagonal"), (100, 1, "identity"), (90, 8, "mix"), (200, 4, "diagonal")])
 def test_one_mala_transition_parity(P, n, K, precond):
-    mode, pc = {"identity": (0, P.IdentityPreconditioner()), "diagonal": (1, P.DiagonalPreconditioner()),
-                "mix": (2, P.MixDiagonalPreconditioner())}[precond]
     y = _data(n, seed=3 * n + K)
     d, N, step, prec = 3 * K, 10, 0.05, 1.0
-    ex = P.MALA(step_size=step, preconditioner=pc)
+    ex = G.mala_explorer(P, step, precond)
     pt = P.PT(P.Inputs(target=P.MixtureModelPosterior(y, K), reference=P.ScaledPrecisionNormalLogPotential(prec, d), n_chains=N,
                        n_rounds=2, explorer=ex, show_report=False))
-    betas, x, chain, rng = _random_states(pt, N, d, seed=d, scale=0.5)
-    eng = pt.replicas
-    std = np.random.default_rng(d).uniform(0.5, 2.0, d)
-    eng.set_explorer_adaptation(step, std)
-    eng.explore(2)
-    x1, c1, r1 = eng.states()
-    eng.reduce()
-    am, an, ss, sn = eng.explorer_stats()
-    n_refresh = ex.base_n_refresh * int(math.ceil(d ** ex.exponent_n_refresh))
+    betas, x, chain, rng = G.random_states(pt, N, d, seed=d, scale=0.5)
     model = R.MixtureModel(y, K, prec)
-    moved = 0
-    for i in range(N):
-        c = int(chain[i])
-        if c == 0:
-            continue
-        r = O.OracleRng(state=(int(rng[i, 0]), int(rng[i, 1])))
-        Mv = A.build_preconditioner(r, d, mode, 1.0 / 3.0, 1.0 / 3.0, std)
-        res = M.mala_transition(x[i], r, R.MixtureModelChain(model, betas[c], prec), step, n_refresh, Mv)
-        assert int(r1[i, 0]) == r.state[0] and int(r1[i, 1]) == r.state[1], (i, c)
-        np.testing.assert_allclose(x1[i], res["x"], rtol=RTOL, atol=1e-12, err_msg="replica %d chain %d" % (i, c))
-        assert an[c] == res["acc_n"] and sn[c] == n_refresh and ss[c] == res["steps"], (i, c)
-        np.testing.assert_allclose(am[c], res["acc_sum"] / res["acc_n"], rtol=RTOL, atol=1e-12)
-        moved += int(not np.array_equal(res["x"], x[i]))
-    assert moved > 0
+    G.assert_mala_transition(pt.replicas, ex, precond, betas, x, chain, rng, lambda beta: R.MixtureModelChain(model, beta, prec),
+                             std_range=(0.5, 2.0), form="whole")
 
 
 # ---- whole runs ------------------------------------------------------------------------------------------------------------------------
-def _run(P, target, prec, seed, n_rounds, explorer, n_chains=16, record=None):
-    """pigeons' round loop by hand: the schedule the last round ran with is kept (adapt replaces it after the round)"""
-    pt = P.PT(P.Inputs(target=target, reference=P.ScaledPrecisionNormalLogPotential(prec, target.dim), n_chains=n_chains,
-                       n_rounds=n_rounds, seed=seed, explorer=explorer, extended_traces=True, show_report=False,
-                       record=record or [P.round_trip, P.traces, P.log_sum_ratio, P.index_process]))
-    grids = None
-    while P.next_round(pt):
-        grids = np.array(pt.shared.tempering.schedule.grids)
-        red = P.run_one_round(pt)
-        pt = P.adapt(pt, red)
-    return pt, grids
+def _run(P, target, prec, seed, n_rounds, explorer, n_chains=16):
+    return G.run_rounds(P, target, prec, seed, n_rounds, explorer, n_chains=n_chains,
+                        record=["round_trip", "traces", "log_sum_ratio", "index_process"])
 
 
-def _batches(a, B):
-    T = a.shape[0] // B * B
-    return a[:T].reshape(B, T // B, *a.shape[1:])
-
-
-def _stepping_stone_se(tr, betas, model, B=8):
-    """Monte Carlo standard error of stepping_stone by batch means, as tests/test_gpu_glm.py takes it: the last round's scans (extended
-    traces, every chain) in B consecutive batches, the estimator -- (forward + backward) / 2 of sum_k log mean_t exp(+-(beta_k+1 - beta_k)
-    (target - reference)(x_t)) -- on each, se = sd(batch estimates) / sqrt(B)."""
-    delta = model.log_likelihood(tr[:, :, :model.d]) + model.c_prior          # target - reference = log likelihood + the constants
-    db = _batches(delta, B)                                                  # [B][t][chain]
-    dbeta = np.diff(betas)
-
-    def lme(a):
-        m = a.max(axis=1, keepdims=True)
-        return (m + np.log(np.mean(np.exp(a - m), axis=1, keepdims=True)))[:, 0]
-    fw = lme(db[:, :, :-1] * dbeta).sum(-1)
-    bw = -lme(-db[:, :, 1:] * dbeta).sum(-1)
-    return float(np.std((fw + bw) / 2.0, ddof=1) / math.sqrt(B))
+def _stepping_stone_se(tr, betas, model):
+    """G.stepping_stone_se on this family's target - reference = log likelihood + the constants"""
+    return G.stepping_stone_se(model.log_likelihood(tr[:, :, :model.d]) + model.c_prior, betas)
 
 
 @pytest.fixture(scope="module")
@@ -237,7 +140,7 @@ def test_label_switching_on_two_separated_clusters(P):
     tr = pt.reduced_recorders.traces[:, -1, :6]                    # the target chain
     ind = (tr[:, 0] < tr[:, 1]).astype(float)
     frac = ind.mean()
-    se = float(_batches(ind, 16).mean(axis=1).std(ddof=1) / 4.0)
+    se = float(G.batches(ind, 16).mean(axis=1).std(ddof=1) / 4.0)
     print("label switching: fraction %.4f, se %.4f, scans %d, round trips %d" % (frac, se, ind.size, P.n_round_trips(pt)))
     assert se <= 0.1, (frac, se)
     assert abs(frac - 0.5) <= 4 * se, (frac, se)
@@ -253,45 +156,21 @@ def _inputs(P, seed=1, explorer=None, n_rounds=5, checkpoint=False):
 
 
 def test_two_runs_are_equal_bit_for_bit(P):
-    a, b = P.pigeons(P.PT(_inputs(P, seed=3, explorer=P.AutoMALA()))), P.pigeons(P.PT(_inputs(P, seed=3, explorer=P.AutoMALA())))
-    xa, ca, ga = a.replicas.states(); xb, cb, gb = b.replicas.states()
-    assert np.array_equal(xa, xb) and np.array_equal(ca, cb) and np.array_equal(ga, gb)
-    assert np.array_equal(a.reduced_recorders.traces, b.reduced_recorders.traces)
-    assert np.array_equal(a.shared.tempering.schedule.grids, b.shared.tempering.schedule.grids)
-    assert P.stepping_stone(a) == P.stepping_stone(b)
+    G.assert_two_runs_equal(P, lambda: _inputs(P, seed=3, explorer=P.AutoMALA()))
 
 
 def test_compose_slice_automala_runs(P):
-    pt = P.pigeons(P.PT(_inputs(P, seed=2, explorer=P.Compose(P.SliceSampler(), P.AutoMALA()))))
-    assert pt.replicas.kernel_name() == "k_explore_mixture_model"
-    assert np.all(np.isfinite(pt.reduced_recorders.traces)) and np.isfinite(P.stepping_stone(pt))
-    m, n = pt.reduced_recorders.explorer_acceptance_pr
-    assert np.all(n[1:] > 0)
+    G.assert_compose_runs(P, _inputs(P, seed=2, explorer=P.Compose(P.SliceSampler(), P.AutoMALA())), "k_explore_mixture_model")
 
 
 @pytest.mark.parametrize("explorer", ["slice", "automala"])
 def test_sharded_equals_single_engine(P, explorer):
     mk = lambda: _inputs(P, seed=4, n_rounds=4, explorer=P.SliceSampler() if explorer == "slice" else P.AutoMALA())
-    one, many = P.PT(mk()), P.PT(mk(), n_shards=2)
-    for _ in range(4):
-        assert P.next_round(one) and P.next_round(many)
-        ra = P.run_one_round(one); P.adapt(one, ra)
-        rb = P.run_one_round(many); P.adapt(many, rb)
-        assert np.array_equal(ra.index_process, rb.index_process) and np.array_equal(ra.traces, rb.traces)
-    xa, ca, ga = one.replicas.states(); xb, cb, gb = many.shards.states()
-    assert np.array_equal(xa, xb) and np.array_equal(ca, cb) and np.array_equal(ga, gb)
+    G.assert_sharded_equals_single(P, mk, n_shards=2)
 
 
 def test_checkpoint_resume_equals_uninterrupted(P, tmp_path):
-    straight = P.pigeons(P.PT(_inputs(P, seed=5, n_rounds=6, explorer=P.MALA(step_size=0.1))))
-    folder = str(tmp_path / "exec")
-    P.pigeons(P.PT(_inputs(P, seed=5, n_rounds=3, explorer=P.MALA(step_size=0.1), checkpoint=True)), exec_folder=folder)
-    resumed = P.pigeons(P.load_checkpoint(folder, n_rounds_increment=3))
-    ra, rb = straight.reduced_recorders, resumed.reduced_recorders
-    assert np.array_equal(ra.index_process, rb.index_process) and np.array_equal(ra.traces, rb.traces)
-    assert np.array_equal(straight.shared.tempering.schedule.grids, resumed.shared.tempering.schedule.grids)
-    xa, ca, ga = straight.replicas.states(); xb, cb, gb = resumed.replicas.states()
-    assert np.array_equal(xa, xb) and np.array_equal(ca, cb) and np.array_equal(ga, gb)
+    G.assert_checkpoint_resume(P, lambda **kw: _inputs(P, seed=5, explorer=P.MALA(step_size=0.1), **kw), tmp_path)
 
 
 def test_new_data_replaces_the_old(P):
@@ -302,13 +181,10 @@ def test_new_data_replaces_the_old(P):
     y1 = _data(90, seed=31)
     pt = P.PT(P.Inputs(target=P.MixtureModelPosterior(y1, K), reference=P.ScaledPrecisionNormalLogPotential(prec, d),
                        n_chains=N, n_rounds=2, explorer=P.SliceSampler(n_passes=1), record=[P.traces], extended_traces=True, show_report=False))
-    betas, _, _, _ = _random_states(pt, N, d, seed=3, scale=0.5)
+    betas, _, _, _ = G.random_states(pt, N, d, seed=3, scale=0.5)
     y2 = 1.5 * _data(200, seed=32)
     pt.replicas.set_target_mixture_model(y2)
-    tr = _log_densities(P, pt, N, d)
+    tr = G.log_densities(pt, N, d)
     new, old = R.MixtureModel(y2, K, prec), R.MixtureModel(y1, K, prec)
-    for c in range(N):
-        want = R.MixtureModelChain(new, betas[c], prec).path_lp(tr[c, :d])
-        assert math.isclose(tr[c, d], want, rel_tol=LP_RTOL, abs_tol=1e-11), (c, tr[c, d], want)
-        if betas[c] > 0:
-            assert not math.isclose(tr[c, d], R.MixtureModelChain(old, betas[c], prec).path_lp(tr[c, :d]), rel_tol=1e-6)
+    G.assert_log_density_at_every_beta(tr, betas, d, lambda beta: R.MixtureModelChain(new, beta, prec).path_lp, LP_RTOL, abs_tol=1e-11)
+    G.assert_log_density_is_not(tr, betas, d, lambda beta: R.MixtureModelChain(old, beta, prec).path_lp)

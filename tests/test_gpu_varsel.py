@@ -4,27 +4,19 @@ Bool coordinates, draw for draw against oracle.MixedSliceSampler -- and the refe
 probabilities, coefficient means and evidence of the conjugate normal-identity model, determinism, the chain-sharded engine, checkpoint /
 resume and replacing the data.
 
-RNG words and Bool coordinates are compared exactly; Float64 coordinates and recorders to 1e-9 relative, log densities to 1e-11 relative --
-the tolerances of tests/test_gpu_glm.py, the same arithmetic class: the device's exp / log1p differ from libm by an ulp, and its fused
-multiply-adds from the restatement's twice-rounded ones in rare ties."""
+RNG words and Bool coordinates are compared exactly; Float64 coordinates, recorders and log densities to the RTOL and LP_RTOL of
+tests/family_gpu.py, which holds the shared checks and says why: this family is of the GLM's arithmetic class."""
 import math
 
 import numpy as np
 import pytest
 
+import family_gpu as G
 import oracle as O
 import varsel_ref as R
+from family_gpu import LP_RTOL, RTOL, P  # noqa: F401  (P: the module's fixture)
 
 pytestmark = pytest.mark.gpu
-
-RTOL = 1e-9
-LP_RTOL = 1e-11
-
-
-@pytest.fixture(scope="module")
-def P():
-    import pigeons_amd
-    return pigeons_amd
 
 
 def _data(n, d, lik, seed=1, noise_sd=1.0):
@@ -53,16 +45,6 @@ def _random_states(pt, N, d, seed, scale=1.5):
     _, _, rng = eng.states()
     eng.set_states(x, chain, rng)
     return betas, x, chain, rng
-
-
-def _log_densities(pt, N, dim):
-    eng = pt.replicas
-    eng.explore(1)
-    eng.swap(1)                                   # (a scan ends at its swap: the traces count it from there)
-    eng.reduce()
-    tr = eng.traces()
-    assert tr.shape == (1, N, dim + 1)
-    return tr[0]
 
 
 def test_state_calls_need_the_data_and_the_setter_validates(P):
@@ -112,12 +94,11 @@ def test_log_density_at_every_beta(P, lik, n, d, pi):
     N, prec = 12, 0.5
     pt = _pt(P, X, y, lik, prec, N, pi=pi, noise_sd=0.8, n_passes=1, record=[P.traces], extended_traces=True)
     betas, _, _, _ = _random_states(pt, N, d, seed=d, scale=0.5)
-    tr = _log_densities(pt, N, 2 * d)
+    tr = G.log_densities(pt, N, 2 * d)
     vs = R.VarSel(X, y, lik, 0.8, prec, pi)
     for c in range(N):
         assert set(np.unique(tr[c, d:2 * d])) <= {0.0, 1.0}
-        want = R.VarSelChain(vs, betas[c], prec).lp_full(tr[c, :2 * d])
-        assert math.isclose(tr[c, 2 * d], want, rel_tol=LP_RTOL, abs_tol=1e-11), (c, betas[c], tr[c, 2 * d], want)
+    G.assert_log_density_at_every_beta(tr, betas, 2 * d, lambda beta: R.VarSelChain(vs, beta, prec).lp_full, LP_RTOL, abs_tol=1e-11)
 
 
 _NARROW = dict(w=0.25, p=3)          # a first interval that the doubling cap p keeps from covering the slice (the default w = 10, p = 20 never binds)
@@ -189,22 +170,9 @@ def test_the_shrink_cap_is_an_error_with_the_coordinate(P):
 
 
 # ---- whole runs ------------------------------------------------------------------------------------------------------------------------
-def _run(P, target, prec, seed, n_rounds, checkpoint=False, record=None):
-    """pigeons' round loop by hand: the schedule the last round ran with is kept (adapt replaces it after the round)"""
-    pt = P.PT(P.Inputs(target=target, reference=P.ScaledPrecisionNormalLogPotential(prec, target.n_columns), n_chains=16,
-                       n_rounds=n_rounds, seed=seed, explorer=P.SliceSampler(), checkpoint=checkpoint, extended_traces=True, show_report=False,
-                       record=record or [P.round_trip, P.online, P.traces, P.log_sum_ratio, P.index_process]))
-    grids = None
-    while P.next_round(pt):
-        grids = np.array(pt.shared.tempering.schedule.grids)
-        red = P.run_one_round(pt)
-        pt = P.adapt(pt, red)
-    return pt, grids
-
-
-def _batches(a, B):
-    T = a.shape[0] // B * B
-    return a[:T].reshape(B, T // B, *a.shape[1:])
+def _run(P, target, prec, seed, n_rounds):
+    return G.run_rounds(P, target, prec, seed, n_rounds, P.SliceSampler(), n_chains=16, ref_dim=target.n_columns,
+                        record=["round_trip", "online", "traces", "log_sum_ratio", "index_process"])
 
 
 _RUN = dict(d=4, n=30, prec=1.0, sd=1.0, pi=0.5, n_rounds=10, seeds=(1, 2, 3), B=32)
@@ -256,10 +224,10 @@ def test_run_against_the_exact_inclusion_probabilities_and_coefficients(P, runs,
     assert cnt == 2 ** _RUN["n_rounds"]
     tr = pt.reduced_recorders.traces[:, -1, :2 * d]                 # the target chain
     assert tr.shape[0] == cnt and set(np.unique(tr[:, d:])) <= {0.0, 1.0}
-    gb = _batches(tr[:, d:], B)
+    gb = G.batches(tr[:, d:], B)
     se_g = gb.mean(axis=1).std(axis=0, ddof=1) / math.sqrt(B)
     dev_g = (np.asarray(m)[d:2 * d] - incl) / se_g
-    bb = _batches(tr[:, :d] * tr[:, d:], B)
+    bb = G.batches(tr[:, :d] * tr[:, d:], B)
     se_b = bb.mean(axis=1).std(axis=0, ddof=1) / math.sqrt(B)
     dev_b = ((tr[:, :d] * tr[:, d:]).mean(axis=0) - b) / se_b
     print("seed %d: inclusion deviations / se %s, coefficient deviations / se %s" % (seed, np.round(dev_g, 2), np.round(dev_b, 2)))
@@ -290,37 +258,16 @@ def _inputs(P, seed=1, n_rounds=5, checkpoint=False):
 
 
 def test_two_runs_are_equal_bit_for_bit(P):
-    a, b = P.pigeons(P.PT(_inputs(P, seed=3))), P.pigeons(P.PT(_inputs(P, seed=3)))
-    xa, ca, ga = a.replicas.states(); xb, cb, gb = b.replicas.states()
-    assert np.array_equal(xa, xb) and np.array_equal(ca, cb) and np.array_equal(ga, gb)
-    assert np.array_equal(a.reduced_recorders.traces, b.reduced_recorders.traces)
-    assert np.array_equal(a.shared.tempering.schedule.grids, b.shared.tempering.schedule.grids)
-    assert P.stepping_stone(a) == P.stepping_stone(b)
+    a = G.assert_two_runs_equal(P, lambda: _inputs(P, seed=3))
     assert np.all(np.isfinite(a.reduced_recorders.traces)) and len(np.unique(a.reduced_recorders.traces[:, 6:12])) == 2
 
 
 def test_sharded_equals_single_engine(P):
-    mk = lambda: _inputs(P, seed=4, n_rounds=4)
-    one, many = P.PT(mk()), P.PT(mk(), n_shards=2)
-    for _ in range(4):
-        assert P.next_round(one) and P.next_round(many)
-        ra = P.run_one_round(one); P.adapt(one, ra)
-        rb = P.run_one_round(many); P.adapt(many, rb)
-        assert np.array_equal(ra.index_process, rb.index_process) and np.array_equal(ra.traces, rb.traces)
-    xa, ca, ga = one.replicas.states(); xb, cb, gb = many.shards.states()
-    assert np.array_equal(xa, xb) and np.array_equal(ca, cb) and np.array_equal(ga, gb)
+    G.assert_sharded_equals_single(P, lambda: _inputs(P, seed=4, n_rounds=4), n_shards=2)
 
 
 def test_checkpoint_resume_equals_uninterrupted(P, tmp_path):
-    straight = P.pigeons(P.PT(_inputs(P, seed=5, n_rounds=6)))
-    folder = str(tmp_path / "exec")
-    P.pigeons(P.PT(_inputs(P, seed=5, n_rounds=3, checkpoint=True)), exec_folder=folder)
-    resumed = P.pigeons(P.load_checkpoint(folder, n_rounds_increment=3))
-    ra, rb = straight.reduced_recorders, resumed.reduced_recorders
-    assert np.array_equal(ra.index_process, rb.index_process) and np.array_equal(ra.traces, rb.traces)
-    assert np.array_equal(straight.shared.tempering.schedule.grids, resumed.shared.tempering.schedule.grids)
-    xa, ca, ga = straight.replicas.states(); xb, cb, gb = resumed.replicas.states()
-    assert np.array_equal(xa, xb) and np.array_equal(ca, cb) and np.array_equal(ga, gb)
+    G.assert_checkpoint_resume(P, lambda **kw: _inputs(P, seed=5, **kw), tmp_path)
 
 
 def test_new_data_replaces_the_old(P):
@@ -332,10 +279,7 @@ def test_new_data_replaces_the_old(P):
     betas, _, _, _ = _random_states(pt, N, d, seed=3, scale=0.5)
     X2, y2 = _data(200, d, "normal_identity", seed=32, noise_sd=2.0)
     pt.replicas.set_target_varsel(P._lib.GLM_NORMAL_IDENTITY, X2, y2, 2.0, 0.25)
-    tr = _log_densities(pt, N, 2 * d)
+    tr = G.log_densities(pt, N, 2 * d)
     new, old = R.VarSel(X2, y2, "normal_identity", 2.0, prec, 0.25), R.VarSel(X1, y1, "normal_identity", 1.0, prec, 0.5)
-    for c in range(N):
-        want = R.VarSelChain(new, betas[c], prec).lp_full(tr[c, :2 * d])
-        assert math.isclose(tr[c, 2 * d], want, rel_tol=LP_RTOL, abs_tol=1e-11), (c, tr[c, 2 * d], want)
-        if betas[c] > 0:
-            assert not math.isclose(tr[c, 2 * d], R.VarSelChain(old, betas[c], prec).lp_full(tr[c, :2 * d]), rel_tol=1e-6)
+    G.assert_log_density_at_every_beta(tr, betas, 2 * d, lambda beta: R.VarSelChain(new, beta, prec).lp_full, LP_RTOL, abs_tol=1e-11)
+    G.assert_log_density_is_not(tr, betas, 2 * d, lambda beta: R.VarSelChain(old, beta, prec).lp_full)
