@@ -85,6 +85,10 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
         double we[256];
         unsigned long long ke[256];
         unsigned policy[HOLD_POLICY ? 2 : 0];        // round 10: g_rng_policy as it stands at the head of the explore step (8 bytes: 14344 of LDS in all)
+        // round 11: the slow-path exponentials the fill could decide, one record per LANE of the fill (768 bytes: 15112 of LDS in all).  rmeta[j] =
+        // window position | draws consumed << 16 (2 or 3) of the record lane j wrote, S8_UNRESOLVED (no position) if it has none; rex[j] its value
+        double rex[HOLD_POLICY ? 64 : 0];
+        unsigned rmeta[HOLD_POLICY ? 64 : 0];
     } sm;
     double (&s_u)[WIN] = sm.u; double (&s_e)[WIN] = sm.e; double (&s_x)[BLK] = sm.x; double (&s_we)[256] = sm.we; unsigned long long (&s_ke)[256] = sm.ke;
     const int lane = lane_id();
@@ -175,9 +179,30 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
     typedef double draws8_t __attribute__((ext_vector_type(8)));        // the shrinkage draws of a hypothesis as the register tuples they are read into (round 9)
     typedef double draws2_t __attribute__((ext_vector_type(2)));
     slow_mask_t slow_w;
+    // Round 11.  The slow-path exponentials of a window (2.3 % of its draws, NaN in s_e) used to be decided where the chase met one as the HEAD of
+    // a coordinate: by lane 0 alone, on the round's dependency chain -- a scalar mix64 pair, four table words behind a scalar-memory wait, the 37
+    // dependent VALU of exp(-x) and five taken branches, ~1255 cycles, 65-71 times per scan (profiles/r10_slice8_summary.txt).  Everything that
+    // decision needs is in the window once it is filled, so the fill now decides them side by side.  Every lane keeps the LAST slow draw among
+    // the eight it converts (two in one lane: the earlier one stays unresolved) and, behind the fill's barrier, runs randexp_from_raw unrolled to
+    // depth one and a half on it, for the draw at window position i in layer idx with x = (double)ri * we[idx], the fill's own `ev`:
+    //     idx == 0 (the ziggurat's tail) or i + 2 >= WIN                              unresolved
+    //     (fe[idx - 1] - fe[idx]) * s_u[i + 1] + fe[idx] < exp(-x)                    E = x, 2 draws            (the wedge accepts)
+    //     otherwise, s_e[i + 2] is not NaN (the next candidate is a fast draw)        E = s_e[i + 2], 3 draws
+    //     otherwise                                                                   unresolved
+    // r.rand() at stream position i + 1 is u52_to_unit of that draw, which is s_u[i + 1] bit for bit; a fast candidate at i + 2 returns
+    // (double)ri * we[idx], which is s_e[i + 2] bit for bit; the wedge test is the expression of randexp_from_raw_hot, operation for operation
+    // (-ffp-contract=off), with the same exp.  The two ZIG_FE words are gathered from global memory, requested ahead of the exp chain.
+    // Lane j writes its record to slot j, so lane 0's entry looks position p up in slot p & 63: one LDS trip, no search.  What is unresolved, or
+    // lost to a second slow draw of the same lane, takes the path of round 10.  Every fill rewrites all 64 slots: no record outlives its window.
+#ifdef PTE_PROFILE_SECTIONS
+    long long prof[21] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};      // 16-19 (round 10): cycles and entries of the window refill and of lane 0's slow-path head exponential; round 11: 18-19 are the entries that MISSED the fill's records, 2 and 20 the cycles and the count of those that hit (20 also: records written << 24)
+#endif
+    constexpr unsigned S8_UNRESOLVED = 0xFFFFu;        // (as a position: no window has one)
     auto fill_window = [&]() __attribute__((always_inline)) {
         __syncthreads();                               // one wave per block: orders the LDS accesses
         double acc = 0.0;
+        double pend_x = 0.0;                           // this lane's pending slow draw: x, and position | layer << 16 (none: position WIN, which resolves to nothing)
+        int pend_m = WIN;
 #pragma unroll
         for (int k = 0; k < WIN / 64; ++k) {
             const int i = 64 * k + lane;
@@ -194,10 +219,29 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
             acc += fast ? ev : 0.0;
             const uint64_t sb = ballot64(!fast);
             slow_w[2 * k] = (unsigned)sb; slow_w[2 * k + 1] = (unsigned)(sb >> 32);
+            if constexpr (HOLD_POLICY) { pend_x = fast ? pend_x : ev; pend_m = fast ? pend_m : (i | (idx << 16)); }
         }
         wsum = wave_sum_dpp(acc);
         p = 0;
         __syncthreads();
+        if constexpr (HOLD_POLICY) {
+            // (nothing of the epilogue is scheduled among the eight conversions above: interleaved with them, its exp chain took k_explore_slice8<4, 9>
+            // from 196 to 211 VGPRs, past the 200 tests/test_codegen_frozen.py allows; behind this line it holds 193)
+            __builtin_amdgcn_sched_barrier(0);
+            const int pi = pend_m & 0xFFFF, pidx = pend_m >> 16;
+            const double f1 = ZIG_FE[pidx], f0 = ZIG_FE[(pidx - 1) & 0xFF];          // (layer 0 never uses f0: any entry inside the table will do)
+            const double un = s_u[min(pi + 1, WIN - 1)], en = s_e[min(pi + 2, WIN - 1)];      // (read inside the arrays whatever the position: decided below)
+            const double ex = exp(-pend_x);
+            const bool in_reach = (pidx != 0) && (pi + 2 < WIN);
+            const bool wedge = (f0 - f1) * un + f1 < ex;
+            const unsigned used = !in_reach ? 0u : wedge ? 2u : (en == en) ? 3u : 0u;
+            sm.rex[lane] = wedge ? pend_x : en;
+            sm.rmeta[lane] = used ? ((unsigned)pi | (used << 16)) : S8_UNRESOLVED;
+#ifdef PTE_PROFILE_SECTIONS
+            prof[20] += (long long)__popcll(ballot64(used != 0u)) << 24;       // records written (slot 20: entries that hit + records << 24)
+#endif
+            __syncthreads();
+        }
     };
     fill_window();
 
@@ -211,9 +255,6 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
     long long steps_sum = 0, fb_draws = 0, ex_total = 0;     // ex_total: extra draws of slow-path exponentials taken inside rounds
     int steps_n = 0, acc_sum = 0, acc_n = 0, n_fb = 0;
     int err = 0, err_coord = -1;
-#ifdef PTE_PROFILE_SECTIONS
-    long long prof[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};      // 16-19 (round 10): cycles and entries of the window refill and of lane 0's slow-path head exponential
-#endif
 
     for (int pass = 0; pass < sp.n_passes && !err; ++pass) {
         for (int b = 0; BLK * (int64_t)b < d && !err; ++b) {
@@ -267,6 +308,36 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                     // the certain hypothesis needs the ziggurat's slow path for its exponential (2.3 % of the coordinates):
                     // evaluate it exactly at its stream position; its other draws follow `ex0` positions later
                     PROF_T(ts0);
+                    if constexpr (HOLD_POLICY) {
+                        const auto head_moves = [&](const double Ex, const int used) __attribute__((always_inline)) {
+                            ex0 = used - 1;
+                            if (lane == 0) { E = Ex; idx0 += ex0; cnt_base = 2 + ex0; ua += 8 * ex0; }
+                            Sest += Ex * inv_abs_nhp;            // not among the window's fast-path exponentials summed into Sest
+                            ex_total += ex0;
+                            u0 = s_u[idx0 + 1];
+#pragma unroll
+                            for (int it = 0; it < S8_BD; ++it) Vd[it] = s_u[idx0 + 2 + it];
+                        };
+                        // round 11: the record the fill left for position p, if any (slot p & 63: every lane reads the same two words)
+                        const unsigned rmeta = (unsigned)__builtin_amdgcn_readfirstlane((int)sm.rmeta[p & 63]);
+                        const double rex = sm.rex[p & 63];
+                        if ((rmeta & 0xFFFFu) == (unsigned)p) {
+                            head_moves(rex, (int)(rmeta >> 16));
+#ifdef PTE_PROFILE_SECTIONS
+                            asm volatile("" :: "v"(E), "v"(u0), "v"(Vd[S8_BD - 1]), "v"(Sest));
+#endif
+                            PROF_T(ts1); PROF_ADD(2, ts1 - ts0); PROF_ADD(20, 1);
+                        } else {
+                            SeqRng rs{wseed + (uint64_t)p * gamma, gamma};
+                            const double Ex = exp_seq(rs);
+                            const int used = (int)((rs.seed - (wseed + (uint64_t)p * gamma)) * gamma_inv);
+                            if (used <= 17) head_moves(Ex, used);
+#ifdef PTE_PROFILE_SECTIONS
+                            asm volatile("" :: "v"(E), "v"(u0), "v"(Vd[S8_BD - 1]), "v"(Sest));
+#endif
+                            PROF_T(ts1); PROF_ADD(18, ts1 - ts0); PROF_ADD(19, 1);
+                        }
+                    } else {                                 // the many-replica twin: the statements of round 10, as they were
                     SeqRng rs{wseed + (uint64_t)p * gamma, gamma};
                     const double Ex = exp_seq(rs);
                     const int used = (int)((rs.seed - (wseed + (uint64_t)p * gamma)) * gamma_inv);
@@ -283,6 +354,7 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
                     asm volatile("" :: "v"(E), "v"(u0), "v"(Vd[S8_BD - 1]), "v"(Sest));
 #endif
                     PROF_T(ts1); PROF_ADD(18, ts1 - ts0); PROF_ADD(19, 1);
+                    }
                 }
                 // Round 7: every slice test of the round is ONE fused operation, d = fma(v, v, -Q) = RN(v^2 - Q), where it used to be
                 // RN(RN(v^2) - Q) in two (the build uses -ffp-contract=off: the fusion is spelled out).  Only the sign of d is used, and only
@@ -1001,7 +1073,7 @@ __device__ __forceinline__ void slice8_body(EngineDev e, SliceParams sp, const i
         e.expl_steps_sum[cl] += (double)steps_sum; e.expl_steps_n[cl] += steps_n;
         e.expl_acc_sum[cl] += (double)acc_sum;     e.expl_acc_n[cl] += acc_n;
 #ifdef PTE_PROFILE_SECTIONS
-        for (int i = 0; i < 20; ++i) e.on_m2[20 * cl + i] += (double)prof[i];   // debug builds only (needs d >= 20 K: tools/prof_sections7.py reads the slots back through the online variance)
+        for (int i = 0; i < 21; ++i) e.on_m2[21 * cl + i] += (double)prof[i];   // debug builds only (needs d >= 21 K: tools/prof_sections7.py reads the slots back through the online variance)
 #endif
     }
     record_after_explore(e, cl, c, slot, lane, lp_before, S, 0.0);
