@@ -12,7 +12,7 @@ import math
 
 import numpy as np
 
-from mixture_ref import tree_sum
+from path_ref import PathChain, tree_sum
 
 LOG2PI = 1.8378770664093453
 LOG2 = 0.6931471805599453
@@ -163,28 +163,4 @@ class Ar1:
         return self._quadrature(na, nl)[2]
 
 
-class Ar1Chain:
-    """one chain of the interpolated path (1 - beta) ScaledPrecisionNormal(ref_prec) + beta target, the interface of hier_ref.HierChain:
-    lp_grad is the AD form (no short-circuits), path_lp the plain callable SliceSampler evaluates"""
-
-    def __init__(self, ar1, beta, ref_prec):
-        self.ar1, self.beta, self.omb, self.ref_prec = ar1, beta, 1.0 - beta, ref_prec
-
-    def lp_grad(self, x):
-        x = np.asarray(x, dtype=np.float64)
-        with np.errstate(all="ignore"):
-            S = tree_sum(x * x)
-            l2, g2 = self.ar1.lp_grad(x)
-            l1 = (-0.5 * self.ref_prec) * S
-            return 0.0 + l1 * self.omb + l2 * self.beta, ((-self.ref_prec) * x) * self.omb + g2 * self.beta
-
-    def path_lp(self, x):
-        x = np.asarray(x, dtype=np.float64)
-        with np.errstate(all="ignore"):
-            S = tree_sum(x * x)
-            if self.beta == 0.0:
-                return (-0.5 * self.ref_prec) * S
-            l2 = self.ar1.lp(x)
-            if self.beta == 1.0:
-                return l2
-            return self.omb * ((-0.5 * self.ref_prec) * S) + self.beta * l2
+Ar1Chain = PathChain          # (ar1, beta, ref_prec): the chain of the interpolated path, tests/path_ref.py

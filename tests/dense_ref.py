@@ -10,7 +10,7 @@ import math
 
 import numpy as np
 
-from mixture_ref import tree_sum
+from path_ref import PathChain, tree_sum
 
 LOG2PI = 1.8378770664093453
 
@@ -61,41 +61,18 @@ class Dense:
         return -(self.d / 2.0) * math.log(2.0 * math.pi / prec)
 
 
-class DenseChain:
-    """one chain of the interpolated path (1 - beta) ScaledPrecisionNormal(ref_prec) + beta target, the interface of glm_ref.GlmChain:
-    lp_grad (= logdensity_and_gradient) is the AD form (no short-circuits), path_lp the plain callable SliceSampler evaluates"""
+class DenseChain(PathChain):
+    """(dense, beta, prec): the chain of the interpolated path (tests/path_ref.py) with the exact law of the chain beside it"""
 
-    def __init__(self, dense, beta, prec):
-        self.dense, self.beta, self.omb, self.ref_prec = dense, beta, 1.0 - beta, prec
-
-    def lp_grad(self, x):
-        x = np.asarray(x, dtype=np.float64)
-        with np.errstate(all="ignore"):
-            S = tree_sum(x * x)
-            l2, g2 = self.dense.lp_grad(x)
-            l1 = (-0.5 * self.ref_prec) * S
-            return 0.0 + l1 * self.omb + l2 * self.beta, ((-self.ref_prec) * x) * self.omb + g2 * self.beta
-
-    logdensity_and_gradient = lp_grad
-
-    def path_lp(self, x):
-        x = np.asarray(x, dtype=np.float64)
-        with np.errstate(all="ignore"):
-            S = tree_sum(x * x)
-            if self.beta == 0.0:
-                return (-0.5 * self.ref_prec) * S
-            l2 = self.dense.lp(x)
-            if self.beta == 1.0:
-                return l2
-            return self.omb * ((-0.5 * self.ref_prec) * S) + self.beta * l2
+    logdensity_and_gradient = PathChain.lp_grad
 
     def chain_moments(self):
         """(mean, covariance) of this chain, exactly: precision P = (1 - beta) p I + beta Q, mean P^-1 beta Q m"""
-        d = self.dense.d
-        P = self.omb * self.ref_prec * np.eye(d) + self.beta * self.dense.Q
+        d = self.model.d
+        P = self.omb * self.ref_prec * np.eye(d) + self.beta * self.model.Q
         cov = np.linalg.inv(P)
         cov = (cov + cov.T) / 2.0
-        return cov @ (self.beta * (self.dense.Q @ self.dense.mean)), cov
+        return cov @ (self.beta * (self.model.Q @ self.model.mean)), cov
 
 
 def spectrum_matrix(d, cond, seed):

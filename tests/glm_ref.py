@@ -10,7 +10,7 @@ import math
 
 import numpy as np
 
-from mixture_ref import tree_sum
+from path_ref import PathChain, tree_sum
 
 LOG2PI = 1.8378770664093453
 BERNOULLI_LOGIT, NORMAL_IDENTITY = 0, 1
@@ -96,28 +96,4 @@ class Glm:
         return -(self.d / 2.0) * math.log(2.0 * math.pi / self.prec)
 
 
-class GlmChain:
-    """one chain of the interpolated path (1 - beta) ScaledPrecisionNormal(ref_prec) + beta target, the interface of
-    mixture_ref.MixtureChain: lp_grad is the AD form (no short-circuits), path_lp the plain callable SliceSampler evaluates"""
-
-    def __init__(self, glm, beta, ref_prec):
-        self.glm, self.beta, self.omb, self.ref_prec = glm, beta, 1.0 - beta, ref_prec
-
-    def lp_grad(self, x):
-        x = np.asarray(x, dtype=np.float64)
-        with np.errstate(all="ignore"):
-            S = tree_sum(x * x)
-            l2, g2 = self.glm.lp_grad(x)
-            l1 = (-0.5 * self.ref_prec) * S
-            return 0.0 + l1 * self.omb + l2 * self.beta, ((-self.ref_prec) * x) * self.omb + g2 * self.beta
-
-    def path_lp(self, x):
-        x = np.asarray(x, dtype=np.float64)
-        with np.errstate(all="ignore"):
-            S = tree_sum(x * x)
-            if self.beta == 0.0:
-                return (-0.5 * self.ref_prec) * S
-            l2 = self.glm.lp(x)
-            if self.beta == 1.0:
-                return l2
-            return self.omb * ((-0.5 * self.ref_prec) * S) + self.beta * l2
+GlmChain = PathChain          # (glm, beta, ref_prec): the chain of the interpolated path, tests/path_ref.py

@@ -9,7 +9,7 @@ import math
 
 import numpy as np
 
-from mixture_ref import tree_sum
+from path_ref import PathChain, tree_sum
 
 
 def lane_tree_sum(t):
@@ -103,31 +103,7 @@ class MixtureModel:
         return (m[..., 0] + np.log(np.exp(a - m).sum(-1))).sum(-1) + self.c_obs
 
 
-class MixtureModelChain:
-    """one chain of the interpolated path (1 - beta) ScaledPrecisionNormal(ref_prec) + beta target, the interface of
-    mixture_ref.MixtureChain: lp_grad is the AD form (no short-circuits), path_lp the plain callable SliceSampler evaluates"""
-
-    def __init__(self, model, beta, ref_prec):
-        self.model, self.beta, self.omb, self.ref_prec = model, beta, 1.0 - beta, ref_prec
-
-    def lp_grad(self, x):
-        x = np.asarray(x, dtype=np.float64)
-        with np.errstate(all="ignore"):
-            S = tree_sum(x * x)
-            l2, g2 = self.model.lp_grad(x)
-            l1 = (-0.5 * self.ref_prec) * S
-            return 0.0 + l1 * self.omb + l2 * self.beta, ((-self.ref_prec) * x) * self.omb + g2 * self.beta
-
-    def path_lp(self, x):
-        x = np.asarray(x, dtype=np.float64)
-        with np.errstate(all="ignore"):
-            S = tree_sum(x * x)
-            if self.beta == 0.0:
-                return (-0.5 * self.ref_prec) * S
-            l2 = self.model.lp(x)
-            if self.beta == 1.0:
-                return l2
-            return self.omb * ((-0.5 * self.ref_prec) * S) + self.beta * l2
+MixtureModelChain = PathChain          # (model, beta, ref_prec): the chain of the interpolated path, tests/path_ref.py
 
 
 def prior_monte_carlo_log_evidence(y, n_components, prec, n_draws, seed, chunk=200000):

@@ -8,20 +8,9 @@ import math
 
 import numpy as np
 
+from path_ref import PathChain, tree_sum          # noqa: F401  (tree_sum: imported from here by the other restatements)
+
 LOG2PI = 1.8378770664093453
-
-
-def tree_sum(v):
-    """the fixed reduction tree of DESIGN 3 over the leaves v (natural order, zero-padded to a power of two)"""
-    a = np.asarray(v, dtype=np.float64).ravel()
-    P = 1
-    while P < a.size:
-        P <<= 1
-    b = np.zeros(P)
-    b[:a.size] = a
-    while b.size > 1:
-        b = b[0::2] + b[1::2]
-    return float(b[0])
 
 
 class Mixture:
@@ -73,31 +62,7 @@ class Mixture:
         return lp, g
 
 
-class MixtureChain:
-    """one chain of the interpolated path (1 - beta) ScaledPrecisionNormal(ref_prec) + beta mixture: lp_grad is the AD form of
-    AmTarget::logdensity_and_gradient_q (no short-circuits), path_lp the plain callable SliceSampler evaluates (InterpolatedLogPotential.jl:9-16)"""
-
-    def __init__(self, mix, beta, ref_prec):
-        self.mix, self.beta, self.omb, self.ref_prec = mix, beta, 1.0 - beta, ref_prec
-
-    def lp_grad(self, x):
-        x = np.asarray(x, dtype=np.float64)
-        with np.errstate(all="ignore"):
-            S = tree_sum(x * x)
-            l2, g2 = self.mix.lp_grad(x)
-            l1 = (-0.5 * self.ref_prec) * S
-            return 0.0 + l1 * self.omb + l2 * self.beta, ((-self.ref_prec) * x) * self.omb + g2 * self.beta
-
-    def path_lp(self, x):
-        x = np.asarray(x, dtype=np.float64)
-        with np.errstate(all="ignore"):
-            S = tree_sum(x * x)
-            if self.beta == 0.0:
-                return (-0.5 * self.ref_prec) * S
-            l2 = self.mix.lp(x)
-            if self.beta == 1.0:
-                return l2
-            return self.omb * ((-0.5 * self.ref_prec) * S) + self.beta * l2
+MixtureChain = PathChain          # (mix, beta, ref_prec): the chain of the interpolated path, tests/path_ref.py
 
 
 def analytic_lognormalization(d, ref_prec):

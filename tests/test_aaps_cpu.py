@@ -6,15 +6,9 @@ import numpy as np
 import pytest
 
 import aaps_ref as A
+import family_cpu as F
 import oracle as O
-
-
-@pytest.fixture(scope="module")
-def P():
-    import __graft_entry__ as g
-    g.build_hip()
-    import pigeons_amd
-    return pigeons_amd
+from family_cpu import P  # noqa: F401  (P: the module's fixture)
 
 
 def _one_transition_sample(prec, eps, K, n=4000, uniform_weights=False, seed=7):
@@ -109,20 +103,14 @@ _MVN = dict(target=0, dim=8, explorer=6)
     (dict(debug_kernel=0x1000), "AAPS has one kernel; debug_kernel must be 0"),
 ])
 def test_pte_create_refusals(P, kw, msg):
-    args = dict(_MVN, n_chains=4)
-    args.update(kw)
-    with pytest.raises(P.PteError, match=msg):
-        P.Engine(**args)
+    F.assert_create_refused(P, dict(_MVN, n_chains=4), kw, msg)
 
 
 def test_accepted_config_reaches_the_device_check(P):
     """a valid AAPS configuration passes validation: without a GPU it fails only where pte_create looks for the device"""
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("a device is present")
+    F.no_device()
     for target, dim in ((0, 1), (0, 512), (2, 2), (2, 512)):
-        with pytest.raises(P.PteError, match="no HIP device"):
-            P.Engine(n_chains=4, target=target, dim=dim, explorer=6, aaps_K=64)
+        F.assert_reaches_the_device_check(P, n_chains=4, target=target, dim=dim, explorer=6, aaps_K=64)
 
 
 def _captured_config(P, explorer, target=None):

@@ -11,25 +11,11 @@ import numpy as np
 import pytest
 
 import ar1_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import family_cpu as F
+from family_cpu import P  # noqa: F401  (P: the module's fixture)
 
 TRUTH_Y = (0.3, 0.9, 1.4, 0.8, 0.2, -0.5, -1.1, -0.6, 0.1, 0.7, 1.2, 0.9)
 TRUTH_KW = dict(obs_sd=0.5, mu_sd=2.0, phi_loc=0.0, phi_scale=1.0, sigma_scale=1.0)
-
-
-@pytest.fixture(scope="module")
-def P():
-    import __graft_entry__ as g
-    g.build_hip()
-    import pigeons_amd
-    return pigeons_amd
-
-
-def _no_device():
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("a device is present")
 
 
 def test_enum_and_export_mirrors(P):
@@ -39,10 +25,10 @@ def test_enum_and_export_mirrors(P):
     assert (_lib.AR1_STOCHASTIC_VOLATILITY, _lib.AR1_NORMAL_IDENTITY) == (0, 1)
     assert "pte_set_target_ar1" in _lib.EXPORTS
     assert hasattr(_lib.load(), "pte_set_target_ar1")
-    hdr = open(os.path.join(ROOT, "include", "pte.h")).read()
+    hdr = F.HEADER
     assert "PTE_TARGET_LATENT_AR1 = 10" in hdr and "int pte_set_target_ar1(pte_engine *h, int32_t likelihood, int64_t n_obs" in hdr
     assert "PTE_AR1_STOCHASTIC_VOLATILITY = 0" in hdr and "PTE_AR1_NORMAL_IDENTITY = 1" in hdr
-    jl = open(os.path.join(ROOT, "pigeons.jl_amd", "julia", "PigeonsMI355X.jl")).read()
+    jl = F.JULIA
     assert "const TARGET_LATENT_AR1 = Int32(10)\n" in jl
     assert "struct DeviceLatentAR1" in jl and "device_family(t::DeviceLatentAR1, inputs)" in jl
     assert ":pte_set_target_ar1" in jl
@@ -59,9 +45,8 @@ def test_enum_and_export_mirrors(P):
 @pytest.mark.parametrize("explorer,explorer2", [(2, 0), (3, 0), (5, 0), (2, 3)])
 def test_accepted_config_reaches_the_device_check(P, explorer, explorer2, dim):
     """fails on the code before the family existed ("target 10 has no device log-potential"): a valid configuration now passes validation"""
-    _no_device()
-    with pytest.raises(P.PteError, match="no HIP device"):
-        P.Engine(n_chains=4, target=10, dim=dim, explorer=explorer, explorer2=explorer2, target_params=[1.0])
+    F.no_device()
+    F.assert_reaches_the_device_check(P, n_chains=4, target=10, dim=dim, explorer=explorer, explorer2=explorer2, target_params=[1.0])
 
 
 _AR1 = dict(target=10, dim=15, explorer=2, n_chains=4)
@@ -85,63 +70,29 @@ _AR1 = dict(target=10, dim=15, explorer=2, n_chains=4)
     (dict(debug_kernel=1, n_chains_variational=4), r"debug_kernel 1 is not available on the latent-AR\(1\) path"),
 ])
 def test_pte_create_refusals(P, kw, msg):
-    args = dict(_AR1)
-    args.update(kw)
-    with pytest.raises(P.PteError, match=msg):
-        P.Engine(**args)
-
-
-def _captured(P, target, explorer=None, reference="default", **kw):
-    seen = {"ar1": []}
-
-    class Stub:
-        def __init__(self, **k):
-            seen.update(k)
-
-        def set_target_ar1(self, lik, y, obs_sd, mu_sd, phi_loc, phi_scale, sigma_scale):
-            seen["ar1"].append((lik, np.array(y), obs_sd, mu_sd, phi_loc, phi_scale, sigma_scale))
-
-    ref = P.ScaledPrecisionNormalLogPotential(0.5, target.dim) if reference == "default" else reference
-    P.PT(P.Inputs(target=target, reference=ref, n_chains=4, n_rounds=2, explorer=explorer, show_report=False, **kw), engine_factory=Stub)
-    return seen
+    F.assert_create_refused(P, _AR1, kw, msg)
 
 
 def test_python_mapping(P):
     from pigeons_amd import _lib
     t = P.LatentAR1(TRUTH_Y, likelihood="normal_identity", obs_sd=0.5, mu_sd=2.0, phi_loc=0.25, phi_scale=0.75, sigma_scale=1.5)
-    kw = _captured(P, t)
+    kw = F.captured(P, t)
     assert kw["target"] == _lib.TARGET_LATENT_AR1 and kw["dim"] == 15 and list(kw["target_params"]) == [0.5]
     assert kw["explorer"] == _lib.EXPLORER_SLICE                      # default explorer: SliceSampler (target.jl:20)
-    (lik, ys, *rest), = kw["ar1"]                                    # set after create, once per engine
+    (lik, ys, *rest), = kw["set_target_ar1"]                         # set after create, once per engine
     assert lik == _lib.AR1_NORMAL_IDENTITY and tuple(rest) == (0.5, 2.0, 0.25, 0.75, 1.5)
     np.testing.assert_array_equal(ys, TRUTH_Y)
     t = P.LatentAR1(TRUTH_Y)
-    kw = _captured(P, t, explorer=P.AutoMALA())
-    assert kw["explorer"] == _lib.EXPLORER_AUTOMALA and kw["ar1"][0][0] == _lib.AR1_STOCHASTIC_VOLATILITY
-    assert tuple(kw["ar1"][0][2:]) == (1.0, 5.0, 0.0, 1.0, 1.0)
-    kw = _captured(P, t, explorer=P.Compose(P.SliceSampler(), P.MALA()))
+    kw = F.captured(P, t, explorer=P.AutoMALA())
+    assert kw["explorer"] == _lib.EXPLORER_AUTOMALA and kw["set_target_ar1"][0][0] == _lib.AR1_STOCHASTIC_VOLATILITY
+    assert tuple(kw["set_target_ar1"][0][2:]) == (1.0, 5.0, 0.0, 1.0, 1.0)
+    kw = F.captured(P, t, explorer=P.Compose(P.SliceSampler(), P.MALA()))
     assert kw["explorer"] == _lib.EXPLORER_SLICE and kw["explorer2"] == _lib.EXPLORER_MALA
-    with pytest.raises(NotImplementedError, match="reference=ScaledPrecisionNormalLogPotential"):
-        _captured(P, t, reference=None)
-    with pytest.raises(NotImplementedError, match="reference=ScaledPrecisionNormalLogPotential"):
-        _captured(P, t, reference=P.ScaledPrecisionNormalLogPotential(1.0, 12))
-    with pytest.raises(NotImplementedError, match="GaussianReference"):
-        _captured(P, t, variational=P.GaussianReference())
+    F.assert_reference_refusals(P, t, wrong_dim=12)
 
 
 def test_every_shard_gets_the_data(P):
-    seen = []
-
-    class Stub:
-        def __init__(self, **k):
-            self.N, self.d = 4, 15
-
-        def set_target_ar1(self, *a):
-            seen.append(self)
-
-    pt = P.PT(P.Inputs(target=P.LatentAR1(TRUTH_Y), reference=P.ScaledPrecisionNormalLogPotential(1.0, 15),
-                       n_chains=4, n_rounds=2, show_report=False), engine_factory=Stub, n_shards=2)
-    assert len(seen) == 2 and seen[0] is not seen[1] and set(seen) == set(pt.shards.engines)
+    F.assert_every_shard_gets_the_data(P, P.LatentAR1(TRUTH_Y), P.ScaledPrecisionNormalLogPotential(1.0, 15), N=4, d=15, setter="set_target_ar1")
 
 
 @pytest.mark.parametrize("args,kw,msg", [
@@ -179,10 +130,8 @@ def test_latent_ar1_surface(P):
 
 def test_set_target_ar1_is_bound(P):
     from pigeons_amd import _lib
-    L = _lib.load()
-    at = L.pte_set_target_ar1.argtypes
-    assert len(at) == 9 and at[1] is C.c_int32 and at[2] is C.c_int64 and all(a is C.c_double for a in at[4:])
-    assert L.pte_set_target_ar1(None, 0, 2, None, 1.0, 5.0, 0.0, 1.0, 1.0) == 1            # a null engine is refused, not dereferenced
+    F.assert_null_engine_refused(_lib.load().pte_set_target_ar1, (None, 0, 2, None, 1.0, 5.0, 0.0, 1.0, 1.0),
+                                 {1: C.c_int32, 2: C.c_int64, **{i: C.c_double for i in range(4, 9)}}, n_args=9)
 
 
 # ---- the restatement ---------------------------------------------------------------------------------------------------------------------

@@ -9,24 +9,10 @@ import os
 import numpy as np
 import pytest
 
-import oracle as O
 import changepoint_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def P():
-    import __graft_entry__ as g
-    g.build_hip()
-    import pigeons_amd
-    return pigeons_amd
-
-
-def _no_device():
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("a device is present")
+import family_cpu as F
+import oracle as O
+from family_cpu import ROOT, P  # noqa: F401  (P: the module's fixture)
 
 
 def test_enum_and_export_mirrors(P):
@@ -35,9 +21,9 @@ def test_enum_and_export_mirrors(P):
     assert _lib.TARGET_CHANGE_POINT == 8
     assert "pte_set_target_changepoint" in _lib.EXPORTS and "pte_set_changepoint_form" in _lib.EXPORTS
     assert hasattr(_lib.load(), "pte_set_target_changepoint")
-    hdr = open(os.path.join(ROOT, "include", "pte.h")).read()
+    hdr = F.HEADER
     assert "PTE_TARGET_CHANGE_POINT = 8" in hdr and "int pte_set_target_changepoint(pte_engine *h, const double *y" in hdr
-    jl = open(os.path.join(ROOT, "pigeons.jl_amd", "julia", "PigeonsMI355X.jl")).read()
+    jl = F.JULIA
     assert "const TARGET_CHANGE_POINT = Int32(8)\n" in jl
     assert "struct DevicePoissonChangePoint" in jl and "device_family(t::DevicePoissonChangePoint, inputs)" in jl
     assert ":pte_set_target_changepoint" in jl
@@ -50,16 +36,13 @@ def test_enum_and_export_mirrors(P):
 @pytest.mark.parametrize("dim", [3, 9, 63, 65, 127])
 def test_accepted_config_reaches_the_device_check(P, dim):
     """fails on the code before the family existed ("target 8 has no device log-potential"): a valid configuration now passes validation"""
-    _no_device()
+    F.no_device()
     from pigeons_amd import _lib
-    with pytest.raises(P.PteError, match="no HIP device"):
-        P.Engine(n_chains=4, target=8, dim=dim, explorer=2, target_params=[1.0])
-    with pytest.raises(P.PteError, match="no HIP device"):
-        P.Engine(n_chains=4, target=8, dim=dim, explorer=2, slice_w=3.0)
+    F.assert_reaches_the_device_check(P, n_chains=4, target=8, dim=dim, explorer=2, target_params=[1.0])
+    F.assert_reaches_the_device_check(P, n_chains=4, target=8, dim=dim, explorer=2, slice_w=3.0)
     for dk in (0x1000, 0x2000):                         # the scan-loop flags (PTE_KERNEL_FLAG_BITS) are allowed
         if dk & _lib.KERNEL_FLAG_BITS:
-            with pytest.raises(P.PteError, match="no HIP device"):
-                P.Engine(n_chains=4, target=8, dim=dim, explorer=2, debug_kernel=dk)
+            F.assert_reaches_the_device_check(P, n_chains=4, target=8, dim=dim, explorer=2, debug_kernel=dk)
 
 
 _CP = dict(target=8, dim=7, explorer=2, n_chains=4)
@@ -88,10 +71,7 @@ _CP = dict(target=8, dim=7, explorer=2, n_chains=4)
     (dict(slice_w=float("inf")), r"for integer variables, the width should be an integer\. Got: inf"),
 ])
 def test_pte_create_refusals(P, kw, msg):
-    args = dict(_CP)
-    args.update(kw)
-    with pytest.raises(P.PteError, match=msg):
-        P.Engine(**args)
+    F.assert_create_refused(P, _CP, kw, msg)
 
 
 def test_the_setters_refusals_are_in_the_library():
@@ -110,19 +90,8 @@ def test_the_setters_refusals_are_in_the_library():
 _Y = [1, 0, 2, 1, 0, 2, 3, 5, 2, 4, 6, 3]
 
 
-def _captured(P, target, explorer=None, reference="default", **kw):
-    seen = {"changepoint": []}
-
-    class Stub:
-        def __init__(self, **k):
-            seen.update(k)
-
-        def set_target_changepoint(self, y):
-            seen["changepoint"].append(np.array(y))
-
-    ref = P.ScaledPrecisionNormalLogPotential(0.5, target.n_rates) if reference == "default" else reference
-    P.PT(P.Inputs(target=target, reference=ref, n_chains=4, n_rounds=2, explorer=explorer, show_report=False, **kw), engine_factory=Stub)
-    return seen
+def _captured(P, target, **kw):
+    return F.captured(P, target, ref_dim=target.n_rates, **kw)               # the reference has K + 1 coordinates, not 2 K + 1
 
 
 def test_python_mapping(P):
@@ -132,34 +101,19 @@ def test_python_mapping(P):
     assert kw["target"] == _lib.TARGET_CHANGE_POINT and kw["dim"] == 7 and list(kw["target_params"]) == [0.5]
     assert kw["explorer"] == _lib.EXPLORER_SLICE and "explorer2" not in kw          # default explorer: SliceSampler (target.jl:20)
     assert kw["slice_w"] == 10.0
-    (ys,), = [kw["changepoint"]]                                                    # set after create, once per engine
+    (ys,), = kw["set_target_changepoint"]                                           # set after create, once per engine
     np.testing.assert_array_equal(ys, np.array(_Y, dtype=np.float64))
     kw = _captured(P, t, explorer=P.SliceSampler(n_passes=2, w=4.0))
     assert kw["slice_n_passes"] == 2 and kw["slice_w"] == 4.0
     for ex in (P.AutoMALA(), P.MALA(), P.AAPS(), P.Compose(P.SliceSampler(), P.AutoMALA()), P.Compose(P.SliceSampler(), P.SliceSampler())):
         with pytest.raises(NotImplementedError, match="explored by SliceSampler only"):
             _captured(P, t, explorer=ex)
-    with pytest.raises(NotImplementedError, match="reference=ScaledPrecisionNormalLogPotential"):
-        _captured(P, t, reference=None)
-    with pytest.raises(NotImplementedError, match="reference=ScaledPrecisionNormalLogPotential"):
-        _captured(P, t, reference=P.ScaledPrecisionNormalLogPotential(1.0, 7))       # the reference has K + 1 coordinates, not 2 K + 1
-    with pytest.raises(NotImplementedError, match="GaussianReference"):
-        _captured(P, t, variational=P.GaussianReference())
+    F.assert_reference_refusals(P, t, wrong_dim=7, ref_dim=t.n_rates)               # (a reference of 2 K + 1 coordinates is the wrong one)
 
 
 def test_every_shard_gets_the_data(P):
-    seen = []
-
-    class Stub:
-        def __init__(self, **k):
-            self.N, self.d = 4, 5
-
-        def set_target_changepoint(self, y):
-            seen.append(self)
-
-    pt = P.PT(P.Inputs(target=P.PoissonChangePoint(_Y, 2), reference=P.ScaledPrecisionNormalLogPotential(1.0, 3), n_chains=4, n_rounds=2,
-                       show_report=False), engine_factory=Stub, n_shards=2)
-    assert len(seen) == 2 and seen[0] is not seen[1] and set(seen) == set(pt.shards.engines)
+    F.assert_every_shard_gets_the_data(P, P.PoissonChangePoint(_Y, 2), P.ScaledPrecisionNormalLogPotential(1.0, 3), N=4, d=5,
+                                       setter="set_target_changepoint")
 
 
 @pytest.mark.parametrize("args,msg", [
@@ -194,9 +148,7 @@ def test_change_point_surface(P):
 def test_set_target_changepoint_is_bound(P):
     from pigeons_amd import _lib
     L = _lib.load()
-    a = L.pte_set_target_changepoint.argtypes
-    assert len(a) == 3 and a[2] is C.c_int64
-    assert L.pte_set_target_changepoint(None, None, 2) == 1            # a null engine is refused, not dereferenced
+    F.assert_null_engine_refused(L.pte_set_target_changepoint, (None, None, 2), {2: C.c_int64}, n_args=3)
     assert L.pte_set_changepoint_form(None, 1) == 1
 
 

@@ -8,24 +8,10 @@ import os
 import numpy as np
 import pytest
 
+import family_cpu as F
 import oracle as O
 import checkerboard_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def P():
-    import __graft_entry__ as g
-    g.build_hip()
-    import pigeons_amd
-    return pigeons_amd
-
-
-def _no_device():
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("a device is present")
+from family_cpu import P  # noqa: F401  (P: the module's fixture)
 
 
 def _ea(L, seed):              # SpinGlassLogPotential.edwards_anderson's draws
@@ -164,9 +150,9 @@ def test_enum_export_and_unit_mirrors(P):
     from pigeons_amd import _lib
     import __graft_entry__ as g
     assert _lib.EXPLORER_CHECKERBOARD_METROPOLIS == 7
-    hdr = open(os.path.join(ROOT, "include", "pte.h")).read()
+    hdr = F.HEADER
     assert "PTE_EXPLORER_CHECKERBOARD_METROPOLIS = 7" in hdr and "#define PTE_ABI_VERSION 2\n" in hdr
-    jl = open(os.path.join(ROOT, "pigeons.jl_amd", "julia", "PigeonsMI355X.jl")).read()
+    jl = F.JULIA
     assert "const EXPLORER_CHECKERBOARD_METROPOLIS = Int32(7)" in jl
     assert "CheckerboardMetropolis" in P.__dict__ and P.CheckerboardMetropolis().n_steps == 3 and P.CheckerboardMetropolis(5).n_steps == 5
     assert isinstance(P.pt.default_explorer(P.IsingLogPotential(1.0, 4)), P.IsingMetropolis)         # unchanged
@@ -182,10 +168,9 @@ def test_enum_export_and_unit_mirrors(P):
 @pytest.mark.parametrize("dim", [4, 36, 1024, 65536])
 def test_accepted_config_reaches_the_device_check(P, target, dim):
     """fails on the code before the explorer existed ("explored by IsingMetropolis only"): a valid configuration now passes validation"""
-    _no_device()
+    F.no_device()
     for dk in (0, 102):
-        with pytest.raises(P.PteError, match="no HIP device"):
-            P.Engine(n_chains=4, target=target, dim=dim, explorer=7, target_params=[1.0], debug_kernel=dk)
+        F.assert_reaches_the_device_check(P, n_chains=4, target=target, dim=dim, explorer=7, target_params=[1.0], debug_kernel=dk)
 
 
 @pytest.mark.parametrize("target", [3, 12])

@@ -10,22 +10,8 @@ import numpy as np
 import pytest
 
 import dense_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def P():
-    import __graft_entry__ as g
-    g.build_hip()
-    import pigeons_amd
-    return pigeons_amd
-
-
-def _no_device():
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("a device is present")
+import family_cpu as F
+from family_cpu import P  # noqa: F401  (P: the module's fixture)
 
 
 def test_enum_and_export_mirrors(P):
@@ -34,10 +20,10 @@ def test_enum_and_export_mirrors(P):
     assert _lib.TARGET_DENSE_NORMAL == 11
     assert "pte_set_target_dense" in _lib.EXPORTS
     assert hasattr(_lib.load(), "pte_set_target_dense")
-    hdr = open(os.path.join(ROOT, "include", "pte.h")).read()
+    hdr = F.HEADER
     assert "PTE_TARGET_DENSE_NORMAL = 11" in hdr
     assert "int pte_set_target_dense(pte_engine *h, int64_t dim, const double *mean /*[dim]*/, const double *precision /*[dim][dim]*/);" in hdr
-    jl = open(os.path.join(ROOT, "pigeons.jl_amd", "julia", "PigeonsMI355X.jl")).read()
+    jl = F.JULIA
     assert "const TARGET_DENSE_NORMAL = Int32(11)\n" in jl
     assert "struct DeviceDenseNormal" in jl and "device_family(t::DeviceDenseNormal, inputs)" in jl
     assert ":pte_set_target_dense" in jl
@@ -54,9 +40,8 @@ def test_enum_and_export_mirrors(P):
 @pytest.mark.parametrize("explorer,explorer2", [(2, 0), (3, 0), (5, 0), (2, 3)])
 def test_accepted_config_reaches_the_device_check(P, explorer, explorer2, dim):
     """fails on the code before the family existed ("target 11 has no device log-potential"): a valid configuration now passes validation"""
-    _no_device()
-    with pytest.raises(P.PteError, match="no HIP device"):
-        P.Engine(n_chains=4, target=11, dim=dim, explorer=explorer, explorer2=explorer2, target_params=[1.0])
+    F.no_device()
+    F.assert_reaches_the_device_check(P, n_chains=4, target=11, dim=dim, explorer=explorer, explorer2=explorer2, target_params=[1.0])
 
 
 _DENSE = dict(target=11, dim=15, explorer=2, n_chains=4)
@@ -80,25 +65,7 @@ _DENSE = dict(target=11, dim=15, explorer=2, n_chains=4)
     (dict(debug_kernel=1, n_chains_variational=4), r"debug_kernel 1 is not available on the dense-normal path"),
 ])
 def test_pte_create_refusals(P, kw, msg):
-    args = dict(_DENSE)
-    args.update(kw)
-    with pytest.raises(P.PteError, match=msg):
-        P.Engine(**args)
-
-
-def _captured(P, target, explorer=None, reference="default", **kw):
-    seen = {"dense": []}
-
-    class Stub:
-        def __init__(self, **k):
-            seen.update(k)
-
-        def set_target_dense(self, mean, precision):
-            seen["dense"].append((np.array(mean), np.array(precision)))
-
-    ref = P.ScaledPrecisionNormalLogPotential(0.5, target.dim) if reference == "default" else reference
-    P.PT(P.Inputs(target=target, reference=ref, n_chains=4, n_rounds=2, explorer=explorer, show_report=False, **kw), engine_factory=Stub)
-    return seen
+    F.assert_create_refused(P, _DENSE, kw, msg)
 
 
 def test_python_mapping(P):
@@ -106,36 +73,21 @@ def test_python_mapping(P):
     Q = R.spectrum_matrix(7, 50.0, 1)
     m = np.arange(7.0)
     t = P.DenseNormal(m, Q)
-    kw = _captured(P, t)
+    kw = F.captured(P, t)
     assert kw["target"] == _lib.TARGET_DENSE_NORMAL and kw["dim"] == 7 and list(kw["target_params"]) == [0.5]
     assert kw["explorer"] == _lib.EXPLORER_SLICE                      # default explorer: SliceSampler (target.jl:20)
-    (ms, Qs), = kw["dense"]                                           # set after create, once per engine
+    (ms, Qs), = kw["set_target_dense"]                                # set after create, once per engine
     np.testing.assert_array_equal(ms, m); np.testing.assert_array_equal(Qs, Q)
-    kw = _captured(P, t, explorer=P.AutoMALA())
+    kw = F.captured(P, t, explorer=P.AutoMALA())
     assert kw["explorer"] == _lib.EXPLORER_AUTOMALA
-    kw = _captured(P, t, explorer=P.Compose(P.SliceSampler(), P.MALA()))
+    kw = F.captured(P, t, explorer=P.Compose(P.SliceSampler(), P.MALA()))
     assert kw["explorer"] == _lib.EXPLORER_SLICE and kw["explorer2"] == _lib.EXPLORER_MALA
-    with pytest.raises(NotImplementedError, match="reference=ScaledPrecisionNormalLogPotential"):
-        _captured(P, t, reference=None)
-    with pytest.raises(NotImplementedError, match="reference=ScaledPrecisionNormalLogPotential"):
-        _captured(P, t, reference=P.ScaledPrecisionNormalLogPotential(1.0, 8))
-    with pytest.raises(NotImplementedError, match="GaussianReference"):
-        _captured(P, t, variational=P.GaussianReference())
+    F.assert_reference_refusals(P, t, wrong_dim=8)
 
 
 def test_every_shard_gets_the_data(P):
-    seen = []
-
-    class Stub:
-        def __init__(self, **k):
-            self.N, self.d = 4, 5
-
-        def set_target_dense(self, mean, precision):
-            seen.append(self)
-
-    pt = P.PT(P.Inputs(target=P.DenseNormal(np.zeros(5), np.eye(5)), reference=P.ScaledPrecisionNormalLogPotential(1.0, 5),
-                       n_chains=4, n_rounds=2, show_report=False), engine_factory=Stub, n_shards=2)
-    assert len(seen) == 2 and seen[0] is not seen[1] and set(seen) == set(pt.shards.engines)
+    F.assert_every_shard_gets_the_data(P, P.DenseNormal(np.zeros(5), np.eye(5)), P.ScaledPrecisionNormalLogPotential(1.0, 5),
+                                       N=4, d=5, setter="set_target_dense")
 
 
 _I2 = np.eye(2)
@@ -185,9 +137,7 @@ def test_dense_normal_surface(P):
 
 def test_set_target_dense_is_bound(P):
     from pigeons_amd import _lib
-    L = _lib.load()
-    assert L.pte_set_target_dense.argtypes[1] is C.c_int64 and len(L.pte_set_target_dense.argtypes) == 4
-    assert L.pte_set_target_dense(None, 2, None, None) == 1          # a null engine is refused, not dereferenced
+    F.assert_null_engine_refused(_lib.load().pte_set_target_dense, (None, 2, None, None), {1: C.c_int64}, n_args=4)
 
 
 # ---- the restatement ---------------------------------------------------------------------------------------------------------------------

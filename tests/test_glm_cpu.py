@@ -3,28 +3,13 @@ device work -- what the device does not run; the Python and Julia surfaces map B
 restatement (tests/glm_ref.py) has the right gradient, and the normal-identity evidence in closed form agrees with quadrature."""
 import ctypes as C
 import math
-import os
 
 import numpy as np
 import pytest
 
+import family_cpu as F
 import glm_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def P():
-    import __graft_entry__ as g
-    g.build_hip()
-    import pigeons_amd
-    return pigeons_amd
-
-
-def _no_device():
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("a device is present")
+from family_cpu import P  # noqa: F401  (P: the module's fixture)
 
 
 def test_enum_and_export_mirrors(P):
@@ -33,10 +18,10 @@ def test_enum_and_export_mirrors(P):
     assert (_lib.GLM_BERNOULLI_LOGIT, _lib.GLM_NORMAL_IDENTITY) == (0, 1)
     assert "pte_set_target_glm" in _lib.EXPORTS
     assert hasattr(_lib.load(), "pte_set_target_glm")
-    hdr = open(os.path.join(ROOT, "include", "pte.h")).read()
+    hdr = F.HEADER
     assert "PTE_TARGET_BAYESIAN_GLM         = 5" in hdr and "int pte_set_target_glm(" in hdr
     assert "PTE_GLM_BERNOULLI_LOGIT = 0" in hdr and "PTE_GLM_NORMAL_IDENTITY = 1" in hdr
-    jl = open(os.path.join(ROOT, "pigeons.jl_amd", "julia", "PigeonsMI355X.jl")).read()
+    jl = F.JULIA
     assert "const TARGET_BAYESIAN_GLM = Int32(5)\n" in jl
     assert "const GLM_BERNOULLI_LOGIT, GLM_NORMAL_IDENTITY = Int32(0), Int32(1)" in jl
     assert "struct DeviceBayesianGLM" in jl and "device_family(t::DeviceBayesianGLM, inputs)" in jl
@@ -47,14 +32,12 @@ def test_enum_and_export_mirrors(P):
 @pytest.mark.parametrize("explorer,explorer2,dim", [(2, 0, 1), (3, 0, 8), (5, 0, 100), (2, 3, 512), (3, 2, 64), (5, 2, 7)])
 def test_accepted_config_reaches_the_device_check(P, explorer, explorer2, dim):
     """fails on the code before the family existed ("target 5 has no device log-potential"): a valid configuration now passes validation"""
-    _no_device()
+    F.no_device()
     from pigeons_amd import _lib
-    with pytest.raises(P.PteError, match="no HIP device"):
-        P.Engine(n_chains=4, target=5, dim=dim, explorer=explorer, explorer2=explorer2, target_params=[1.0])
+    F.assert_reaches_the_device_check(P, n_chains=4, target=5, dim=dim, explorer=explorer, explorer2=explorer2, target_params=[1.0])
     for dk in (0x1000, 0x2000):                         # the scan-loop flags (PTE_KERNEL_FLAG_BITS) are allowed
         if dk & _lib.KERNEL_FLAG_BITS:
-            with pytest.raises(P.PteError, match="no HIP device"):
-                P.Engine(n_chains=4, target=5, dim=dim, explorer=explorer, explorer2=explorer2, debug_kernel=dk)
+            F.assert_reaches_the_device_check(P, n_chains=4, target=5, dim=dim, explorer=explorer, explorer2=explorer2, debug_kernel=dk)
 
 
 _GLM = dict(target=5, dim=8, explorer=2, n_chains=4)
@@ -74,10 +57,7 @@ _GLM = dict(target=5, dim=8, explorer=2, n_chains=4)
     (dict(n_chains_variational=4), "two-leg tempering"),
 ])
 def test_pte_create_refusals(P, kw, msg):
-    args = dict(_GLM)
-    args.update(kw)
-    with pytest.raises(P.PteError, match=msg):
-        P.Engine(**args)
+    F.assert_create_refused(P, _GLM, kw, msg)
 
 
 def _data(n=20, d=3, lik="bernoulli_logit", seed=1):
@@ -87,58 +67,27 @@ def _data(n=20, d=3, lik="bernoulli_logit", seed=1):
     return X, y
 
 
-def _captured(P, target, explorer=None, reference="default", **kw):
-    seen = {"glm": []}
-
-    class Stub:
-        def __init__(self, **k):
-            seen.update(k)
-
-        def set_target_glm(self, lik, X, y, sd):
-            seen["glm"].append((lik, np.array(X), np.array(y), sd))
-
-    ref = P.ScaledPrecisionNormalLogPotential(0.5, target.dim) if reference == "default" else reference
-    P.PT(P.Inputs(target=target, reference=ref, n_chains=4, n_rounds=2, explorer=explorer, show_report=False, **kw), engine_factory=Stub)
-    return seen
-
-
 def test_python_mapping(P):
     from pigeons_amd import _lib
     X, y = _data(20, 3, "normal_identity")
     t = P.BayesianGLM(X, y, likelihood="normal_identity", noise_sd=0.7)
-    kw = _captured(P, t)
+    kw = F.captured(P, t)
     assert kw["target"] == _lib.TARGET_BAYESIAN_GLM and kw["dim"] == 3 and list(kw["target_params"]) == [0.5]
     assert kw["explorer"] == _lib.EXPLORER_SLICE                      # default explorer: SliceSampler (target.jl:20)
-    (lik, Xs, ys, sd), = kw["glm"]                                   # set after create, once per engine
+    (lik, Xs, ys, sd), = kw["set_target_glm"]                        # set after create, once per engine
     assert lik == _lib.GLM_NORMAL_IDENTITY and sd == 0.7
     np.testing.assert_array_equal(Xs, X); np.testing.assert_array_equal(ys, y)
     X, y = _data(20, 3)
-    kw = _captured(P, P.BayesianGLM(X, y), explorer=P.AutoMALA())
-    assert kw["explorer"] == _lib.EXPLORER_AUTOMALA and kw["glm"][0][0] == _lib.GLM_BERNOULLI_LOGIT
-    kw = _captured(P, t, explorer=P.Compose(P.SliceSampler(), P.MALA()))
+    kw = F.captured(P, P.BayesianGLM(X, y), explorer=P.AutoMALA())
+    assert kw["explorer"] == _lib.EXPLORER_AUTOMALA and kw["set_target_glm"][0][0] == _lib.GLM_BERNOULLI_LOGIT
+    kw = F.captured(P, t, explorer=P.Compose(P.SliceSampler(), P.MALA()))
     assert kw["explorer"] == _lib.EXPLORER_SLICE and kw["explorer2"] == _lib.EXPLORER_MALA
-    with pytest.raises(NotImplementedError, match="reference=ScaledPrecisionNormalLogPotential"):
-        _captured(P, t, reference=None)
-    with pytest.raises(NotImplementedError, match="reference=ScaledPrecisionNormalLogPotential"):
-        _captured(P, t, reference=P.ScaledPrecisionNormalLogPotential(1.0, 4))
-    with pytest.raises(NotImplementedError, match="GaussianReference"):
-        _captured(P, t, variational=P.GaussianReference())
+    F.assert_reference_refusals(P, t, wrong_dim=4)
 
 
 def test_every_shard_gets_the_data(P):
-    seen = []
-
-    class Stub:
-        def __init__(self, **k):
-            self.N, self.d = 4, 3
-
-        def set_target_glm(self, lik, X, y, sd):
-            seen.append(self)
-
     X, y = _data(10, 3)
-    pt = P.PT(P.Inputs(target=P.BayesianGLM(X, y), reference=P.ScaledPrecisionNormalLogPotential(1.0, 3), n_chains=4, n_rounds=2,
-                       show_report=False), engine_factory=Stub, n_shards=2)
-    assert len(seen) == 2 and seen[0] is not seen[1] and set(seen) == set(pt.shards.engines)
+    F.assert_every_shard_gets_the_data(P, P.BayesianGLM(X, y), P.ScaledPrecisionNormalLogPotential(1.0, 3), N=4, d=3, setter="set_target_glm")
 
 
 @pytest.mark.parametrize("args,kw,msg", [
@@ -176,10 +125,7 @@ def test_bayesian_glm_surface(P):
 
 def test_set_target_glm_is_bound(P):
     from pigeons_amd import _lib
-    L = _lib.load()
-    assert L.pte_set_target_glm.argtypes[1] is C.c_int32 and L.pte_set_target_glm.argtypes[2] is C.c_int64
-    assert L.pte_set_target_glm.argtypes[5] is C.c_double
-    assert L.pte_set_target_glm(None, 0, 2, None, None, 1.0) == 1            # a null engine is refused, not dereferenced
+    F.assert_null_engine_refused(_lib.load().pte_set_target_glm, (None, 0, 2, None, None, 1.0), {1: C.c_int32, 2: C.c_int64, 5: C.c_double})
 
 
 # ---- the restatement ---------------------------------------------------------------------------------------------------------------------

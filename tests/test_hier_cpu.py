@@ -10,26 +10,12 @@ import os
 import numpy as np
 import pytest
 
+import family_cpu as F
 import hier_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from family_cpu import P  # noqa: F401  (P: the module's fixture)
 
 SCHOOLS_Y = (28.0, 8.0, -3.0, 7.0, -1.0, 1.0, 18.0, 12.0)
 SCHOOLS_SIGMA = (15.0, 10.0, 16.0, 11.0, 9.0, 11.0, 10.0, 18.0)
-
-
-@pytest.fixture(scope="module")
-def P():
-    import __graft_entry__ as g
-    g.build_hip()
-    import pigeons_amd
-    return pigeons_amd
-
-
-def _no_device():
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("a device is present")
 
 
 def test_enum_and_export_mirrors(P):
@@ -39,10 +25,10 @@ def test_enum_and_export_mirrors(P):
     assert (_lib.HIER_CENTERED, _lib.HIER_NONCENTERED) == (0, 1)
     assert "pte_set_target_hier" in _lib.EXPORTS
     assert hasattr(_lib.load(), "pte_set_target_hier")
-    hdr = open(os.path.join(ROOT, "include", "pte.h")).read()
+    hdr = F.HEADER
     assert "PTE_TARGET_HIERARCHICAL_NORMAL = 9" in hdr and "int pte_set_target_hier(pte_engine *h, int32_t parameterization, int64_t n_groups" in hdr
     assert "PTE_HIER_CENTERED = 0" in hdr and "PTE_HIER_NONCENTERED = 1" in hdr
-    jl = open(os.path.join(ROOT, "pigeons.jl_amd", "julia", "PigeonsMI355X.jl")).read()
+    jl = F.JULIA
     assert "const TARGET_HIERARCHICAL_NORMAL = Int32(9)\n" in jl
     assert "struct DeviceHierarchicalNormalMeans" in jl and "device_family(t::DeviceHierarchicalNormalMeans, inputs)" in jl
     assert ":pte_set_target_hier" in jl
@@ -59,9 +45,8 @@ def test_enum_and_export_mirrors(P):
 @pytest.mark.parametrize("explorer,explorer2", [(2, 0), (3, 0), (5, 0), (2, 3)])
 def test_accepted_config_reaches_the_device_check(P, explorer, explorer2, dim):
     """fails on the code before the family existed ("target 9 has no device log-potential"): a valid configuration now passes validation"""
-    _no_device()
-    with pytest.raises(P.PteError, match="no HIP device"):
-        P.Engine(n_chains=4, target=9, dim=dim, explorer=explorer, explorer2=explorer2, target_params=[1.0])
+    F.no_device()
+    F.assert_reaches_the_device_check(P, n_chains=4, target=9, dim=dim, explorer=explorer, explorer2=explorer2, target_params=[1.0])
 
 
 _HIER = dict(target=9, dim=10, explorer=2, n_chains=4)
@@ -80,64 +65,32 @@ _HIER = dict(target=9, dim=10, explorer=2, n_chains=4)
     (dict(n_chains_variational=4), "two-leg tempering"),
 ])
 def test_pte_create_refusals(P, kw, msg):
-    args = dict(_HIER)
-    args.update(kw)
-    with pytest.raises(P.PteError, match=msg):
-        P.Engine(**args)
-
-
-def _captured(P, target, explorer=None, reference="default", **kw):
-    seen = {"hier": []}
-
-    class Stub:
-        def __init__(self, **k):
-            seen.update(k)
-
-        def set_target_hier(self, param, y, sigma, mu_sd, tau_scale):
-            seen["hier"].append((param, np.array(y), np.array(sigma), mu_sd, tau_scale))
-
-    ref = P.ScaledPrecisionNormalLogPotential(0.5, target.dim) if reference == "default" else reference
-    P.PT(P.Inputs(target=target, reference=ref, n_chains=4, n_rounds=2, explorer=explorer, show_report=False, **kw), engine_factory=Stub)
-    return seen
+    F.assert_create_refused(P, _HIER, kw, msg)
 
 
 def test_python_mapping(P):
     from pigeons_amd import _lib
     t = P.HierarchicalNormalMeans(SCHOOLS_Y, SCHOOLS_SIGMA, mu_sd=4.0, tau_scale=3.0, parameterization="noncentered")
-    kw = _captured(P, t)
+    kw = F.captured(P, t)
     assert kw["target"] == _lib.TARGET_HIERARCHICAL_NORMAL and kw["dim"] == 10 and list(kw["target_params"]) == [0.5]
     assert kw["explorer"] == _lib.EXPLORER_SLICE                      # default explorer: SliceSampler (target.jl:20)
-    (param, ys, ss, mu_sd, tau_scale), = kw["hier"]                  # set after create, once per engine
+    (param, ys, ss, mu_sd, tau_scale), = kw["set_target_hier"]       # set after create, once per engine
     assert param == _lib.HIER_NONCENTERED and (mu_sd, tau_scale) == (4.0, 3.0)
     np.testing.assert_array_equal(ys, SCHOOLS_Y); np.testing.assert_array_equal(ss, SCHOOLS_SIGMA)
     t = P.HierarchicalNormalMeans(SCHOOLS_Y, SCHOOLS_SIGMA)
-    kw = _captured(P, t, explorer=P.AutoMALA())
-    assert kw["explorer"] == _lib.EXPLORER_AUTOMALA and kw["hier"][0][0] == _lib.HIER_CENTERED and kw["hier"][0][3:] == (5.0, 5.0)
-    kw = _captured(P, t, explorer=P.Compose(P.SliceSampler(), P.MALA()))
+    kw = F.captured(P, t, explorer=P.AutoMALA())
+    call = kw["set_target_hier"][0]
+    assert kw["explorer"] == _lib.EXPLORER_AUTOMALA and call[0] == _lib.HIER_CENTERED and call[3:] == (5.0, 5.0)
+    kw = F.captured(P, t, explorer=P.Compose(P.SliceSampler(), P.MALA()))
     assert kw["explorer"] == _lib.EXPLORER_SLICE and kw["explorer2"] == _lib.EXPLORER_MALA
-    with pytest.raises(NotImplementedError, match="reference=ScaledPrecisionNormalLogPotential"):
-        _captured(P, t, reference=None)
-    with pytest.raises(NotImplementedError, match="reference=ScaledPrecisionNormalLogPotential"):
-        _captured(P, t, reference=P.ScaledPrecisionNormalLogPotential(1.0, 8))
-    with pytest.raises(NotImplementedError, match="GaussianReference"):
-        _captured(P, t, variational=P.GaussianReference())
+    F.assert_reference_refusals(P, t, wrong_dim=8)
     with pytest.raises((ValueError, AttributeError, TypeError)):
         P.analytic_lognormalization(t, P.ScaledPrecisionNormalLogPotential(1.0, 10))          # not defined for this family
 
 
 def test_every_shard_gets_the_data(P):
-    seen = []
-
-    class Stub:
-        def __init__(self, **k):
-            self.N, self.d = 4, 10
-
-        def set_target_hier(self, param, y, sigma, mu_sd, tau_scale):
-            seen.append(self)
-
-    pt = P.PT(P.Inputs(target=P.HierarchicalNormalMeans(SCHOOLS_Y, SCHOOLS_SIGMA), reference=P.ScaledPrecisionNormalLogPotential(1.0, 10),
-                       n_chains=4, n_rounds=2, show_report=False), engine_factory=Stub, n_shards=2)
-    assert len(seen) == 2 and seen[0] is not seen[1] and set(seen) == set(pt.shards.engines)
+    F.assert_every_shard_gets_the_data(P, P.HierarchicalNormalMeans(SCHOOLS_Y, SCHOOLS_SIGMA), P.ScaledPrecisionNormalLogPotential(1.0, 10),
+                                       N=4, d=10, setter="set_target_hier")
 
 
 @pytest.mark.parametrize("args,kw,msg", [
@@ -177,10 +130,8 @@ def test_hierarchical_normal_means_surface(P):
 
 def test_set_target_hier_is_bound(P):
     from pigeons_amd import _lib
-    L = _lib.load()
-    assert L.pte_set_target_hier.argtypes[1] is C.c_int32 and L.pte_set_target_hier.argtypes[2] is C.c_int64
-    assert L.pte_set_target_hier.argtypes[5] is C.c_double and L.pte_set_target_hier.argtypes[6] is C.c_double
-    assert L.pte_set_target_hier(None, 0, 2, None, None, 5.0, 5.0) == 1            # a null engine is refused, not dereferenced
+    F.assert_null_engine_refused(_lib.load().pte_set_target_hier, (None, 0, 2, None, None, 5.0, 5.0),
+                                 {1: C.c_int32, 2: C.c_int64, 5: C.c_double, 6: C.c_double})
 
 
 # ---- the restatement ---------------------------------------------------------------------------------------------------------------------

@@ -9,16 +9,7 @@ import numpy as np
 import pytest
 
 import oracle as O
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def P():
-    import __graft_entry__ as g
-    g.build_hip()
-    import pigeons_amd
-    return pigeons_amd
+from family_cpu import ROOT, P  # noqa: F401  (P: the module's fixture)
 
 
 def test_library_exports_every_declared_symbol(P):

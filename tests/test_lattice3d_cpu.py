@@ -10,24 +10,10 @@ import os
 import numpy as np
 import pytest
 
+import family_cpu as F
 import oracle as O
 import lattice3d_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def P():
-    import __graft_entry__ as g
-    g.build_hip()
-    import pigeons_amd
-    return pigeons_amd
-
-
-def _no_device():
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("a device is present")
+from family_cpu import P  # noqa: F401  (P: the module's fixture)
 
 
 def _transition(lat, sites, r):
@@ -193,10 +179,10 @@ def test_enum_export_and_unit_mirrors(P):
     import __graft_entry__ as g
     assert _lib.TARGET_SPIN_GLASS_3D == 13
     assert "pte_set_target_spin_glass_3d" in _lib.EXPORTS and hasattr(_lib.load(), "pte_set_target_spin_glass_3d")
-    hdr = open(os.path.join(ROOT, "include", "pte.h")).read()
+    hdr = F.HEADER
     assert "PTE_TARGET_SPIN_GLASS_3D = 13" in hdr and "#define PTE_ABI_VERSION 2\n" in hdr
     assert "int pte_set_target_spin_glass_3d(pte_engine *h, int64_t base_length, const int8_t *bonds_x" in hdr
-    jl = open(os.path.join(ROOT, "pigeons.jl_amd", "julia", "PigeonsMI355X.jl")).read()
+    jl = F.JULIA
     assert "const TARGET_SPIN_GLASS_3D = Int32(13)" in jl and ":pte_set_target_spin_glass_3d" in jl
     assert "SpinGlass3DLogPotential" in P.__dict__ and hasattr(P.Engine, "set_target_spin_glass_3d")
     # a translation unit of its own, in a list of its own, with pte_spinglass.hip's flags; the other lists did not grow
@@ -250,9 +236,8 @@ def test_python_surface_and_its_refusals(P):
 @pytest.mark.parametrize("dim", [8, 64, 216, 1000, 32768])
 def test_accepted_config_reaches_the_device_check(P, dim):
     """fails on the code before the family existed ("target 13 has no device log-potential"): a valid configuration now passes validation"""
-    _no_device()
-    with pytest.raises(P.PteError, match="no HIP device"):
-        P.Engine(n_chains=4, target=13, dim=dim, explorer=7, target_params=[1.0])
+    F.no_device()
+    F.assert_reaches_the_device_check(P, n_chains=4, target=13, dim=dim, explorer=7, target_params=[1.0])
 
 
 CAP = r"a row of the lattice is held in one 32-bit word, so 32 is the cap although 34\.\.40 would fit the 65536-site limit"
@@ -279,10 +264,7 @@ ONLY = r"the 3-D spin-glass path is explored by CheckerboardMetropolis only \(go
     (dict(debug_kernel=1), r"the 3-D spin-glass path has one kernel; debug_kernel must be 0 \(got 1\)"),
 ])
 def test_pte_create_refusals(P, kw, msg):
-    args = dict(n_chains=4, target=13, dim=64, explorer=7, target_params=[1.0])
-    args.update(kw)
-    with pytest.raises(P.PteError, match=msg):
-        P.Engine(**args)
+    F.assert_create_refused(P, dict(n_chains=4, target=13, dim=64, explorer=7, target_params=[1.0]), kw, msg)
 
 
 def test_the_2d_refusals_keep_their_text(P):

@@ -3,28 +3,13 @@ any device work -- what the device does not run; the Python and Julia surfaces m
 the NumPy restatement (tests/mixture_ref.py) has the right gradient, is normalised, and gives the path's known log normalising constant."""
 import ctypes as C
 import math
-import os
 
 import numpy as np
 import pytest
 
+import family_cpu as F
 import mixture_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def P():
-    import __graft_entry__ as g
-    g.build_hip()
-    import pigeons_amd
-    return pigeons_amd
-
-
-def _no_device():
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("a device is present")
+from family_cpu import P  # noqa: F401  (P: the module's fixture)
 
 
 def test_enum_and_export_mirrors(P):
@@ -32,9 +17,9 @@ def test_enum_and_export_mirrors(P):
     assert _lib.TARGET_GAUSSIAN_MIXTURE == 4
     assert "pte_set_target_mixture" in _lib.EXPORTS
     assert hasattr(_lib.load(), "pte_set_target_mixture")
-    hdr = open(os.path.join(ROOT, "include", "pte.h")).read()
+    hdr = F.HEADER
     assert "PTE_TARGET_GAUSSIAN_MIXTURE     = 4" in hdr and "int pte_set_target_mixture(" in hdr
-    jl = open(os.path.join(ROOT, "pigeons.jl_amd", "julia", "PigeonsMI355X.jl")).read()
+    jl = F.JULIA
     assert "TARGET_GAUSSIAN_MIXTURE = Int32(0), Int32(1), Int32(2), Int32(3), Int32(4)" in jl
     assert "struct DeviceGaussianMixture" in jl and "device_family(t::DeviceGaussianMixture, inputs)" in jl
     assert ":pte_set_target_mixture" in jl
@@ -44,14 +29,12 @@ def test_enum_and_export_mirrors(P):
 @pytest.mark.parametrize("explorer,explorer2,dim", [(2, 0, 1), (3, 0, 8), (5, 0, 100), (2, 3, 512), (3, 2, 64), (5, 2, 7)])
 def test_accepted_config_reaches_the_device_check(P, explorer, explorer2, dim):
     """fails on the code before the family existed ("target 4 has no device log-potential"): a valid configuration now passes validation"""
-    _no_device()
-    with pytest.raises(P.PteError, match="no HIP device"):
-        P.Engine(n_chains=4, target=4, dim=dim, explorer=explorer, explorer2=explorer2, target_params=[1.0])
+    F.no_device()
+    F.assert_reaches_the_device_check(P, n_chains=4, target=4, dim=dim, explorer=explorer, explorer2=explorer2, target_params=[1.0])
     for dk in (0x1000, 0x2000):                         # the scan-loop flags (PTE_KERNEL_FLAG_BITS) are allowed
         from pigeons_amd import _lib
         if dk & _lib.KERNEL_FLAG_BITS:
-            with pytest.raises(P.PteError, match="no HIP device"):
-                P.Engine(n_chains=4, target=4, dim=dim, explorer=explorer, explorer2=explorer2, debug_kernel=dk)
+            F.assert_reaches_the_device_check(P, n_chains=4, target=4, dim=dim, explorer=explorer, explorer2=explorer2, debug_kernel=dk)
 
 
 _MIX = dict(target=4, dim=8, explorer=2, n_chains=4)
@@ -71,10 +54,7 @@ _MIX = dict(target=4, dim=8, explorer=2, n_chains=4)
     (dict(n_chains_variational=4), "two-leg tempering"),
 ])
 def test_pte_create_refusals(P, kw, msg):
-    args = dict(_MIX)
-    args.update(kw)
-    with pytest.raises(P.PteError, match=msg):
-        P.Engine(**args)
+    F.assert_create_refused(P, _MIX, kw, msg)
 
 
 def _mix(d=3, K=2):
@@ -87,55 +67,23 @@ def P_GM(w, m, s):
     return pigeons_amd.GaussianMixture(w, m, s)
 
 
-def _captured(P, target, explorer=None, reference="default", **kw):
-    seen = {"mixture": []}
-
-    class Stub:
-        def __init__(self, **k):
-            seen.update(k)
-
-        def set_target_mixture(self, w, m, s):
-            seen["mixture"].append((np.array(w), np.array(m), np.array(s)))
-
-    ref = P.ScaledPrecisionNormalLogPotential(0.5, target.dim) if reference == "default" else reference
-    P.PT(P.Inputs(target=target, reference=ref, n_chains=4, n_rounds=2, explorer=explorer, show_report=False, **kw), engine_factory=Stub)
-    return seen
-
-
 def test_python_mapping(P):
     from pigeons_amd import _lib
     t = _mix(d=3, K=2)
-    kw = _captured(P, t)
+    kw = F.captured(P, t)
     assert kw["target"] == _lib.TARGET_GAUSSIAN_MIXTURE and kw["dim"] == 3 and list(kw["target_params"]) == [0.5]
     assert kw["explorer"] == _lib.EXPLORER_SLICE                      # default explorer: SliceSampler (target.jl:20)
-    (w, m, s), = kw["mixture"]                                       # set after create, once per engine
+    (w, m, s), = kw["set_target_mixture"]                            # set after create, once per engine
     np.testing.assert_array_equal(w, t.weights); np.testing.assert_array_equal(m, t.means); np.testing.assert_array_equal(s, t.std_devs)
-    kw = _captured(P, t, explorer=P.AutoMALA())
+    kw = F.captured(P, t, explorer=P.AutoMALA())
     assert kw["explorer"] == _lib.EXPLORER_AUTOMALA
-    kw = _captured(P, t, explorer=P.Compose(P.SliceSampler(), P.MALA()))
+    kw = F.captured(P, t, explorer=P.Compose(P.SliceSampler(), P.MALA()))
     assert kw["explorer"] == _lib.EXPLORER_SLICE and kw["explorer2"] == _lib.EXPLORER_MALA
-    with pytest.raises(NotImplementedError, match="reference=ScaledPrecisionNormalLogPotential"):
-        _captured(P, t, reference=None)
-    with pytest.raises(NotImplementedError, match="reference=ScaledPrecisionNormalLogPotential"):
-        _captured(P, t, reference=P.ScaledPrecisionNormalLogPotential(1.0, 4))
-    with pytest.raises(NotImplementedError, match="GaussianReference"):
-        _captured(P, t, variational=P.GaussianReference())
+    F.assert_reference_refusals(P, t, wrong_dim=4)
 
 
 def test_every_shard_gets_the_mixture(P):
-    seen = []
-
-    class Stub:
-        def __init__(self, **k):
-            self.N, self.d = 4, 3
-
-        def set_target_mixture(self, w, m, s):
-            seen.append(self)
-
-    t = _mix(d=3, K=3)
-    pt = P.PT(P.Inputs(target=t, reference=P.ScaledPrecisionNormalLogPotential(1.0, 3), n_chains=4, n_rounds=2, show_report=False),
-              engine_factory=Stub, n_shards=2)
-    assert len(seen) == 2 and seen[0] is not seen[1] and set(seen) == set(pt.shards.engines)
+    F.assert_every_shard_gets_the_data(P, _mix(d=3, K=3), P.ScaledPrecisionNormalLogPotential(1.0, 3), N=4, d=3, setter="set_target_mixture")
 
 
 @pytest.mark.parametrize("args,msg", [
@@ -170,9 +118,7 @@ def test_gaussian_mixture_surface(P):
 
 def test_set_target_mixture_is_bound(P):
     from pigeons_amd import _lib
-    L = _lib.load()
-    assert L.pte_set_target_mixture.argtypes[1] is C.c_int64
-    assert L.pte_set_target_mixture(None, 2, None, None, None) == 1          # a null engine is refused, not dereferenced
+    F.assert_null_engine_refused(_lib.load().pte_set_target_mixture, (None, 2, None, None, None), {1: C.c_int64})
 
 
 # ---- the restatement ---------------------------------------------------------------------------------------------------------------------

@@ -5,29 +5,15 @@ symmetric under relabelling, keeps its -inf / NaN rules, and prior Monte Carlo g
 import ctypes as C
 import itertools
 import math
-import os
 
 import numpy as np
 import pytest
 
+import family_cpu as F
 import mixture_model_ref as R
+from family_cpu import P  # noqa: F401  (P: the module's fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 Y8 = [-1.6, -1.3, -1.0, -0.9, 0.8, 1.1, 1.3, 1.7]
-
-
-@pytest.fixture(scope="module")
-def P():
-    import __graft_entry__ as g
-    g.build_hip()
-    import pigeons_amd
-    return pigeons_amd
-
-
-def _no_device():
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("a device is present")
 
 
 def test_enum_and_export_mirrors(P):
@@ -35,10 +21,10 @@ def test_enum_and_export_mirrors(P):
     assert _lib.TARGET_MIXTURE_MODEL == 6
     assert "pte_set_target_mixture_model" in _lib.EXPORTS
     assert hasattr(_lib.load(), "pte_set_target_mixture_model")
-    hdr = open(os.path.join(ROOT, "include", "pte.h")).read()
+    hdr = F.HEADER
     assert "PTE_TARGET_MIXTURE_MODEL        = 6" in hdr
     assert "int pte_set_target_mixture_model(pte_engine *h, int64_t n_obs, const double *y" in hdr
-    jl = open(os.path.join(ROOT, "pigeons.jl_amd", "julia", "PigeonsMI355X.jl")).read()
+    jl = F.JULIA
     assert "const TARGET_MIXTURE_MODEL = Int32(6)\n" in jl
     assert "struct DeviceMixtureModelPosterior" in jl and "device_family(t::DeviceMixtureModelPosterior, inputs)" in jl
     assert ":pte_set_target_mixture_model" in jl
@@ -50,14 +36,12 @@ def test_enum_and_export_mirrors(P):
 @pytest.mark.parametrize("explorer,explorer2,dim", [(2, 0, 3), (3, 0, 6), (5, 0, 9), (2, 3, 24), (3, 2, 12), (5, 2, 15), (2, 0, 18), (3, 0, 21)])
 def test_accepted_config_reaches_the_device_check(P, explorer, explorer2, dim):
     """fails on the code before the family existed ("target 6 has no device log-potential"): a valid configuration now passes validation"""
-    _no_device()
+    F.no_device()
     from pigeons_amd import _lib
-    with pytest.raises(P.PteError, match="no HIP device"):
-        P.Engine(n_chains=4, target=6, dim=dim, explorer=explorer, explorer2=explorer2, target_params=[1.0])
+    F.assert_reaches_the_device_check(P, n_chains=4, target=6, dim=dim, explorer=explorer, explorer2=explorer2, target_params=[1.0])
     for dk in (0x1000, 0x2000):                         # the scan-loop flags (PTE_KERNEL_FLAG_BITS) are allowed
         if dk & _lib.KERNEL_FLAG_BITS:
-            with pytest.raises(P.PteError, match="no HIP device"):
-                P.Engine(n_chains=4, target=6, dim=dim, explorer=explorer, explorer2=explorer2, debug_kernel=dk)
+            F.assert_reaches_the_device_check(P, n_chains=4, target=6, dim=dim, explorer=explorer, explorer2=explorer2, debug_kernel=dk)
 
 
 _MM = dict(target=6, dim=6, explorer=2, n_chains=4)
@@ -77,60 +61,27 @@ _DIM = r"mixture-model path holds theta = \[mu, s, alpha\] of 1\.\.8 components,
     (dict(n_chains_variational=4), "two-leg tempering .* is not available on the mixture-model path"),
 ])
 def test_pte_create_refusals(P, kw, msg):
-    args = dict(_MM)
-    args.update(kw)
-    with pytest.raises(P.PteError, match=msg):
-        P.Engine(**args)
-
-
-def _captured(P, target, explorer=None, reference="default", **kw):
-    seen = {"y": []}
-
-    class Stub:
-        def __init__(self, **k):
-            seen.update(k)
-
-        def set_target_mixture_model(self, y):
-            seen["y"].append(np.array(y))
-
-    ref = P.ScaledPrecisionNormalLogPotential(0.5, target.dim) if reference == "default" else reference
-    P.PT(P.Inputs(target=target, reference=ref, n_chains=4, n_rounds=2, explorer=explorer, show_report=False, **kw), engine_factory=Stub)
-    return seen
+    F.assert_create_refused(P, _MM, kw, msg)
 
 
 def test_python_mapping(P):
     from pigeons_amd import _lib
     t = P.MixtureModelPosterior(Y8, 2)
-    kw = _captured(P, t)
+    kw = F.captured(P, t)
     assert kw["target"] == _lib.TARGET_MIXTURE_MODEL and kw["dim"] == 6 and list(kw["target_params"]) == [0.5]
     assert kw["explorer"] == _lib.EXPLORER_SLICE                      # default explorer: SliceSampler (target.jl:20)
-    (ys,), = [kw["y"]]                                                # set after create, once per engine
+    (ys,), = kw["set_target_mixture_model"]                           # set after create, once per engine
     np.testing.assert_array_equal(ys, np.array(Y8))
-    kw = _captured(P, P.MixtureModelPosterior(Y8, 3), explorer=P.AutoMALA())
+    kw = F.captured(P, P.MixtureModelPosterior(Y8, 3), explorer=P.AutoMALA())
     assert kw["explorer"] == _lib.EXPLORER_AUTOMALA and kw["dim"] == 9
-    kw = _captured(P, t, explorer=P.Compose(P.SliceSampler(), P.MALA()))
+    kw = F.captured(P, t, explorer=P.Compose(P.SliceSampler(), P.MALA()))
     assert kw["explorer"] == _lib.EXPLORER_SLICE and kw["explorer2"] == _lib.EXPLORER_MALA
-    with pytest.raises(NotImplementedError, match="reference=ScaledPrecisionNormalLogPotential"):
-        _captured(P, t, reference=None)
-    with pytest.raises(NotImplementedError, match="reference=ScaledPrecisionNormalLogPotential"):
-        _captured(P, t, reference=P.ScaledPrecisionNormalLogPotential(1.0, 5))
-    with pytest.raises(NotImplementedError, match="GaussianReference"):
-        _captured(P, t, variational=P.GaussianReference())
+    F.assert_reference_refusals(P, t, wrong_dim=5)
 
 
 def test_every_shard_gets_the_data(P):
-    seen = []
-
-    class Stub:
-        def __init__(self, **k):
-            self.N, self.d = 4, 6
-
-        def set_target_mixture_model(self, y):
-            seen.append(self)
-
-    pt = P.PT(P.Inputs(target=P.MixtureModelPosterior(Y8, 2), reference=P.ScaledPrecisionNormalLogPotential(1.0, 6), n_chains=4, n_rounds=2,
-                       show_report=False), engine_factory=Stub, n_shards=2)
-    assert len(seen) == 2 and seen[0] is not seen[1] and set(seen) == set(pt.shards.engines)
+    F.assert_every_shard_gets_the_data(P, P.MixtureModelPosterior(Y8, 2), P.ScaledPrecisionNormalLogPotential(1.0, 6), N=4, d=6,
+                                       setter="set_target_mixture_model")
 
 
 @pytest.mark.parametrize("args,msg", [
@@ -160,9 +111,7 @@ def test_mixture_model_posterior_surface(P):
 
 def test_set_target_mixture_model_is_bound(P):
     from pigeons_amd import _lib
-    L = _lib.load()
-    assert L.pte_set_target_mixture_model.argtypes[1] is C.c_int64 and len(L.pte_set_target_mixture_model.argtypes) == 3
-    assert L.pte_set_target_mixture_model(None, 2, None) == 1            # a null engine is refused, not dereferenced
+    F.assert_null_engine_refused(_lib.load().pte_set_target_mixture_model, (None, 2, None), {1: C.c_int64}, n_args=3)
 
 
 # ---- the restatement ---------------------------------------------------------------------------------------------------------------------

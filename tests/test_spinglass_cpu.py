@@ -7,24 +7,10 @@ import os
 import numpy as np
 import pytest
 
+import family_cpu as F
 import oracle as O
 import spinglass_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def P():
-    import __graft_entry__ as g
-    g.build_hip()
-    import pigeons_amd
-    return pigeons_amd
-
-
-def _no_device():
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("a device is present")
+from family_cpu import P  # noqa: F401  (P: the module's fixture)
 
 
 def _ea(L, seed):
@@ -126,10 +112,10 @@ def test_enum_and_export_mirrors(P):
     import __graft_entry__ as g
     assert _lib.TARGET_SPIN_GLASS == 12
     assert "pte_set_target_spin_glass" in _lib.EXPORTS and hasattr(_lib.load(), "pte_set_target_spin_glass")
-    hdr = open(os.path.join(ROOT, "include", "pte.h")).read()
+    hdr = F.HEADER
     assert "PTE_TARGET_SPIN_GLASS = 12" in hdr and "#define PTE_ABI_VERSION 2\n" in hdr
     assert "int pte_set_target_spin_glass(pte_engine *h, int64_t base_length, const int8_t *bonds_right" in hdr
-    jl = open(os.path.join(ROOT, "pigeons.jl_amd", "julia", "PigeonsMI355X.jl")).read()
+    jl = F.JULIA
     assert "const TARGET_SPIN_GLASS = Int32(12)\n" in jl and ":pte_set_target_spin_glass" in jl
     assert "SpinGlassLogPotential" in P.__dict__
     # a translation unit of its own, with the flags of the Ising kernels' unit
@@ -172,10 +158,9 @@ def test_python_validation_messages(P):
 @pytest.mark.parametrize("dim", [4, 9, 1024, 65536])
 def test_accepted_config_reaches_the_device_check(P, dim):
     """fails on the code before the family existed ("target 12 has no device log-potential"): a valid configuration now passes validation"""
-    _no_device()
+    F.no_device()
     for dk in (0, 102):
-        with pytest.raises(P.PteError, match="no HIP device"):
-            P.Engine(n_chains=4, target=12, dim=dim, explorer=4, target_params=[1.0], debug_kernel=dk)
+        F.assert_reaches_the_device_check(P, n_chains=4, target=12, dim=dim, explorer=4, target_params=[1.0], debug_kernel=dk)
 
 
 @pytest.mark.parametrize("kw,msg", [

@@ -9,24 +9,10 @@ import os
 import numpy as np
 import pytest
 
+import family_cpu as F
 import oracle as O
 import varsel_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def P():
-    import __graft_entry__ as g
-    g.build_hip()
-    import pigeons_amd
-    return pigeons_amd
-
-
-def _no_device():
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("a device is present")
+from family_cpu import ROOT, P  # noqa: F401  (P: the module's fixture)
 
 
 def test_enum_and_export_mirrors(P):
@@ -35,9 +21,9 @@ def test_enum_and_export_mirrors(P):
     assert _lib.TARGET_VARIABLE_SELECTION == 7
     assert "pte_set_target_varsel" in _lib.EXPORTS
     assert hasattr(_lib.load(), "pte_set_target_varsel")
-    hdr = open(os.path.join(ROOT, "include", "pte.h")).read()
+    hdr = F.HEADER
     assert "PTE_TARGET_VARIABLE_SELECTION = 7" in hdr and "int pte_set_target_varsel(pte_engine *h, const double *X" in hdr
-    jl = open(os.path.join(ROOT, "pigeons.jl_amd", "julia", "PigeonsMI355X.jl")).read()
+    jl = F.JULIA
     assert "const TARGET_VARIABLE_SELECTION = Int32(7)\n" in jl
     assert "struct DeviceSpikeSlabRegression" in jl and "device_family(t::DeviceSpikeSlabRegression, inputs)" in jl
     assert ":pte_set_target_varsel" in jl
@@ -50,14 +36,12 @@ def test_enum_and_export_mirrors(P):
 @pytest.mark.parametrize("dim", [2, 8, 64, 130, 512])
 def test_accepted_config_reaches_the_device_check(P, dim):
     """fails on the code before the family existed ("target 7 has no device log-potential"): a valid configuration now passes validation"""
-    _no_device()
+    F.no_device()
     from pigeons_amd import _lib
-    with pytest.raises(P.PteError, match="no HIP device"):
-        P.Engine(n_chains=4, target=7, dim=dim, explorer=2, target_params=[1.0])
+    F.assert_reaches_the_device_check(P, n_chains=4, target=7, dim=dim, explorer=2, target_params=[1.0])
     for dk in (0x1000, 0x2000):                         # the scan-loop flags (PTE_KERNEL_FLAG_BITS) are allowed
         if dk & _lib.KERNEL_FLAG_BITS:
-            with pytest.raises(P.PteError, match="no HIP device"):
-                P.Engine(n_chains=4, target=7, dim=dim, explorer=2, debug_kernel=dk)
+            F.assert_reaches_the_device_check(P, n_chains=4, target=7, dim=dim, explorer=2, debug_kernel=dk)
 
 
 _VS = dict(target=7, dim=8, explorer=2, n_chains=4)
@@ -83,10 +67,7 @@ _VS = dict(target=7, dim=8, explorer=2, n_chains=4)
     (dict(n_chains_variational=4), "two-leg tempering"),
 ])
 def test_pte_create_refusals(P, kw, msg):
-    args = dict(_VS)
-    args.update(kw)
-    with pytest.raises(P.PteError, match=msg):
-        P.Engine(**args)
+    F.assert_create_refused(P, _VS, kw, msg)
 
 
 def test_the_setters_refusals_are_in_the_library():
@@ -107,19 +88,8 @@ def _data(n=20, d=3, lik="bernoulli_logit", seed=1):
     return X, y
 
 
-def _captured(P, target, explorer=None, reference="default", **kw):
-    seen = {"varsel": []}
-
-    class Stub:
-        def __init__(self, **k):
-            seen.update(k)
-
-        def set_target_varsel(self, lik, X, y, sd, pi):
-            seen["varsel"].append((lik, np.array(X), np.array(y), sd, pi))
-
-    ref = P.ScaledPrecisionNormalLogPotential(0.5, target.n_columns) if reference == "default" else reference
-    P.PT(P.Inputs(target=target, reference=ref, n_chains=4, n_rounds=2, explorer=explorer, show_report=False, **kw), engine_factory=Stub)
-    return seen
+def _captured(P, target, **kw):
+    return F.captured(P, target, ref_dim=target.n_columns, **kw)             # the reference has d coordinates, not 2 d
 
 
 def test_python_mapping(P):
@@ -129,36 +99,21 @@ def test_python_mapping(P):
     kw = _captured(P, t)
     assert kw["target"] == _lib.TARGET_VARIABLE_SELECTION and kw["dim"] == 6 and list(kw["target_params"]) == [0.5]
     assert kw["explorer"] == _lib.EXPLORER_SLICE and "explorer2" not in kw          # default explorer: SliceSampler (target.jl:20)
-    (lik, Xs, ys, sd, pi), = kw["varsel"]                                           # set after create, once per engine
+    (lik, Xs, ys, sd, pi), = kw["set_target_varsel"]                                # set after create, once per engine
     assert lik == _lib.GLM_NORMAL_IDENTITY and sd == 0.7 and pi == 0.3
     np.testing.assert_array_equal(Xs, X); np.testing.assert_array_equal(ys, y)
     kw = _captured(P, P.SpikeSlabRegression(*_data(20, 3)), explorer=P.SliceSampler(n_passes=2))
-    assert kw["slice_n_passes"] == 2 and kw["varsel"][0][0] == _lib.GLM_BERNOULLI_LOGIT and kw["varsel"][0][4] == 0.5
+    assert kw["slice_n_passes"] == 2 and kw["set_target_varsel"][0][0] == _lib.GLM_BERNOULLI_LOGIT and kw["set_target_varsel"][0][4] == 0.5
     for ex in (P.AutoMALA(), P.MALA(), P.AAPS(), P.Compose(P.SliceSampler(), P.AutoMALA()), P.Compose(P.SliceSampler(), P.SliceSampler())):
         with pytest.raises(NotImplementedError, match="explored by SliceSampler only"):
             _captured(P, t, explorer=ex)
-    with pytest.raises(NotImplementedError, match="reference=ScaledPrecisionNormalLogPotential"):
-        _captured(P, t, reference=None)
-    with pytest.raises(NotImplementedError, match="reference=ScaledPrecisionNormalLogPotential"):
-        _captured(P, t, reference=P.ScaledPrecisionNormalLogPotential(1.0, 6))       # the reference has d coordinates, not 2 d
-    with pytest.raises(NotImplementedError, match="GaussianReference"):
-        _captured(P, t, variational=P.GaussianReference())
+    F.assert_reference_refusals(P, t, wrong_dim=6, ref_dim=t.n_columns)             # (a reference of 2 d coordinates is the wrong one)
 
 
 def test_every_shard_gets_the_data(P):
-    seen = []
-
-    class Stub:
-        def __init__(self, **k):
-            self.N, self.d = 4, 6
-
-        def set_target_varsel(self, lik, X, y, sd, pi):
-            seen.append(self)
-
     X, y = _data(10, 3)
-    pt = P.PT(P.Inputs(target=P.SpikeSlabRegression(X, y), reference=P.ScaledPrecisionNormalLogPotential(1.0, 3), n_chains=4, n_rounds=2,
-                       show_report=False), engine_factory=Stub, n_shards=2)
-    assert len(seen) == 2 and seen[0] is not seen[1] and set(seen) == set(pt.shards.engines)
+    F.assert_every_shard_gets_the_data(P, P.SpikeSlabRegression(X, y), P.ScaledPrecisionNormalLogPotential(1.0, 3), N=4, d=6,
+                                       setter="set_target_varsel")
 
 
 @pytest.mark.parametrize("args,kw,msg", [
@@ -194,10 +149,8 @@ def test_spike_slab_surface(P):
 
 def test_set_target_varsel_is_bound(P):
     from pigeons_amd import _lib
-    L = _lib.load()
-    a = L.pte_set_target_varsel.argtypes
-    assert a[3] is C.c_int64 and a[4] is C.c_int64 and a[5] is C.c_int32 and a[6] is C.c_double and a[7] is C.c_double
-    assert L.pte_set_target_varsel(None, None, None, 2, 1, 0, 1.0, 0.5) == 1            # a null engine is refused, not dereferenced
+    F.assert_null_engine_refused(_lib.load().pte_set_target_varsel, (None, None, None, 2, 1, 0, 1.0, 0.5),
+                                 {3: C.c_int64, 4: C.c_int64, 5: C.c_int32, 6: C.c_double, 7: C.c_double})
 
 
 # ---- the restatement ---------------------------------------------------------------------------------------------------------------------
