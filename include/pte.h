@@ -419,6 +419,37 @@ int pte_comm_allgather(pte_engine *h, const void *send, int64_t bytes, void *rec
 /* G engines of ONE process, engines[g] = rank g of a world of G (same N, d, explorer): the fused scan loop. */
 int pte_group_run_scans(pte_engine *const *engines, int32_t n_engines, int64_t first_scan, int64_t n_scans);
 
+/* ---- the replica overlap between two runs of a lattice family (the project's own specification) ----------------
+ * Two engines a, b over the same lattice model -- PTE_TARGET_ISING, PTE_TARGET_SPIN_GLASS or PTE_TARGET_SPIN_GLASS_3D, the same
+ * bonds, the same N and schedule, different seeds -- hold two independent copies of the system at every temperature.  For chain c,
+ * with t = (bits of the replica at chain c in a) XOR (the same in b) over the dim site bits, a record adds
+ *   site overlap   k  = popcount(t), 0..dim            q   = 1 - 2 k / dim           to hist[c][k] and n[c]
+ *   link overlap   kl = sum_dir popcount(t XOR shift_dir(t)), shift_dir the periodic shift by one site along each lattice direction
+ *                  (every site owns its +dir bond; at base_length 2 the two bonds between the same pair of sites are distinct terms;
+ *                  the bonds cancel, J^2 = 1)          q_l = 1 - 2 kl / n_links      to link_n[c], link_sum[c], link_sum2[c]
+ * All accumulators are exact int64.  The link overlap is recorded on the cube at every base_length (n_links = 3 dim) and on the 2-D
+ * lattices where base_length % 32 == 0 (n_links = 2 dim); elsewhere pte_overlap_info reports n_links = 0 and link_n stays 0.
+ * The object holds no state of either engine: destroying it leaves both usable.  Errors of pte_overlap_create are read with
+ * pte_last_error(NULL), errors of the other calls with pte_last_error(a) (an error of b is copied there).
+ *   pte_overlap_create    refuses, naming what it got: a null argument or a == b; engines on different devices; a target that is not a
+ *                         lattice; differing target, dim or N; world_size != 1; n_chains_variational > 0; a spin-glass engine without
+ *                         bonds; bond planes that differ (both engines' device planes are downloaded and compared); histograms of
+ *                         more than 2 GiB (N (dim + 1) 8 bytes)
+ *   pte_overlap_record    one record of the states as they are; synchronous
+ *   pte_overlap_run_scans for s = first_scan .. first_scan + n_scans - 1: explore!(s) and communicate!(s) of a on a's stream and of b on
+ *                         b's, then one record of the post-swap states; each engine ends exactly where pte_run_scans alone would have
+ *                         left it.  record and run_scans refuse when the two engines' schedules differ in any bit, and a poisoned engine
+ *   pte_overlap_reduce    snapshot the accumulators to the host and zero them on the device
+ *   pte_overlap_get       the snapshot: n[N], hist[N][dim + 1], link_n[N], link_sum[N], link_sum2[N]; NULLs are skipped */
+typedef struct pte_overlap pte_overlap;
+int pte_overlap_create(pte_engine *a, pte_engine *b, pte_overlap **out);
+int pte_overlap_destroy(pte_overlap *ov);
+int pte_overlap_info(const pte_overlap *ov, int64_t *n_chains, int64_t *dim, int64_t *n_links);
+int pte_overlap_record(pte_overlap *ov);
+int pte_overlap_run_scans(pte_overlap *ov, int64_t first_scan, int64_t n_scans);
+int pte_overlap_reduce(pte_overlap *ov);
+int pte_overlap_get(const pte_overlap *ov, int64_t *n, int64_t *hist, int64_t *link_n, int64_t *link_sum, int64_t *link_sum2);
+
 /* Name of the kernel that explores on this engine (e.g. "k_explore_slice8"), for profiles and bench.py. */
 const char *pte_kernel_name(const pte_engine *h);
 

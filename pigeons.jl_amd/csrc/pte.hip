@@ -35,6 +35,7 @@
 #include "pte_spinglass_params.hpp"
 #include "pte_checkerboard_params.hpp"
 #include "pte_lattice3d_params.hpp"
+#include "pte_overlap_params.hpp"
 #else                              // tools / development builds: one translation unit
 #include "pte_langevin_launch.hpp"
 #include "pte_aaps.hpp"
@@ -49,6 +50,7 @@
 #include "pte_spinglass.hpp"
 #include "pte_checkerboard.hpp"
 #include "pte_lattice3d.hpp"
+#include "pte_overlap.hpp"
 #endif
 #include "pte_ising.hpp"
 #if defined(PTE_PROFILE_AM)               // debug builds only (tools/prof_automala.py): 12 words per wave, section times of k_explore_automala
@@ -2119,6 +2121,204 @@ int pte_group_run_scans(pte_engine *const *hs, int32_t G, int64_t first_scan, in
     for (int g = 0; g < G; ++g)
         if (pte_shard_sync(hs[g], nullptr)) { if (hs[g] != h0) h0->err = hs[g]->err; rc = 1; }
     return rc;
+}
+
+}  // extern "C"
+
+// ---- the replica overlap between two engines (pte_overlap.hpp) ----------------------------------------------------------------
+// Two single-GPU lattice engines over the same model -- the same bonds, the same ladder -- whose chains c are two independent copies at
+// beta_c.  The object owns the accumulators and two events, and holds no state of either engine: it reads their rows and chain -> slot maps
+// when a record is launched.
+struct pte_overlap {
+    pte_engine *a = nullptr, *b = nullptr;
+    int device = 0;
+    int64_t N = 0, d = 0, n_links = 0;
+    int geom = OVERLAP_GEOM_NONE, L = 0;
+    int64_t *d_acc = nullptr;             // one allocation: hist [N][d + 1], n [N], link_n [N], link_sum [N], link_sum2 [N]
+    size_t words = 0;                     // its int64 words
+    OverlapAcc acc{};
+    hipEvent_t ev_b = nullptr;            // B's stream has finished what the record reads
+    hipEvent_t ev_rec = nullptr;          // the record has read B's rows: B's next explore may write them
+    std::vector<int64_t> snap;            // the accumulators of the last pte_overlap_reduce
+};
+
+namespace {
+
+// the bonds as the device holds them, downloaded: the byte plane of the 2-D family (d bytes), the three word planes of the 3-D one
+int download_bonds(pte_engine *h, std::vector<unsigned char> &out) {
+    const bool cube = h->cfg.target == PTE_TARGET_SPIN_GLASS_3D;
+    const int64_t L3 = lattice3d_base_length(h->d);
+    const size_t bytes = cube ? sizeof(unsigned) * (size_t)(3 * L3 * L3) : (size_t)h->d;
+    out.resize(bytes);
+    HIP_OK(h, hipMemcpyAsync(out.data(), cube ? (const void *)h->d_sg3_words : (const void *)h->d_sg_bytes, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// what pte_overlap_record and pte_overlap_run_scans ask of the pair before they launch anything: both engines alive, one ladder bit for bit
+int overlap_entry(pte_overlap *ov, const char *what) {
+    pte_engine *a = ov->a, *b = ov->b;
+    PTE_ALIVE(a, what);
+    if (b->poisoned) { poisoned_error(b, what); a->err = b->err; return 1; }
+    if (a->betas.size() != b->betas.size() || std::memcmp(a->betas.data(), b->betas.data(), sizeof(double) * a->betas.size()) != 0) {
+        size_t c = 0;
+        while (c < a->betas.size() && c < b->betas.size() && std::memcmp(&a->betas[c], &b->betas[c], sizeof(double)) == 0) ++c;
+        return fail(a, "%s: the two engines' schedules differ (first at chain %lld: %.17g and %.17g); a chain of the pair must be one temperature -- "
+                       "give both engines the same grids", what, (long long)c, c < a->betas.size() ? a->betas[c] : NAN, c < b->betas.size() ? b->betas[c] : NAN);
+    }
+    return 0;
+}
+
+// one record on A's stream, ordered behind what B's stream holds so far; B's stream then waits for it
+int overlap_enqueue_record(pte_overlap *ov) {
+    pte_engine *a = ov->a, *b = ov->b;
+    HIP_OK(a, hipEventRecord(ov->ev_b, b->stream));
+    HIP_OK(a, hipStreamWaitEvent(a->stream, ov->ev_b, 0));
+    if (overlap_launch(a->stream, OverlapSide{a->dev.x, a->dev.ld, a->dev.slot_of_chain}, OverlapSide{b->dev.x, b->dev.ld, b->dev.slot_of_chain},
+                       (int)ov->d, (int)ov->N, ov->geom, ov->L, ov->acc))
+        return fail(a, "this build holds no overlap kernel for dim %lld", (long long)ov->d);
+    HIP_OK(a, hipGetLastError());
+    HIP_OK(a, hipEventRecord(ov->ev_rec, a->stream));
+    HIP_OK(a, hipStreamWaitEvent(b->stream, ov->ev_rec, 0));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pte_overlap_create(pte_engine *a, pte_engine *b, pte_overlap **out) {
+    if (out) *out = nullptr;
+    if (!a || !b || !out) return fail(nullptr, "pte_overlap_create: null argument (a = %p, b = %p, out = %p)", (void *)a, (void *)b, (void *)out);
+    if (a == b) return fail(nullptr, "pte_overlap_create: a and b are the same engine (%p); the overlap is between two independent runs", (void *)a);
+    if (a->poisoned || b->poisoned) return fail(nullptr, "pte_overlap_create: engine %s is poisoned; restore it with pte_set_state first", a->poisoned ? "a" : "b");
+    if (a->cfg.device != b->cfg.device)
+        return fail(nullptr, "pte_overlap_create: the engines are on different devices (%d and %d); the kernel reads both lattices from one GPU", a->cfg.device, b->cfg.device);
+    for (const pte_engine *h : {a, b})
+        if (!on_lattice(h->cfg.target))
+            return fail(nullptr, "pte_overlap_create: engine %s has target %d; the overlap is recorded on the lattice targets (PTE_TARGET_ISING, PTE_TARGET_SPIN_GLASS, "
+                                 "PTE_TARGET_SPIN_GLASS_3D)", h == a ? "a" : "b", h->cfg.target);
+    if (a->cfg.target != b->cfg.target || a->d != b->d || a->N != b->N)
+        return fail(nullptr, "pte_overlap_create: the engines differ: target %d and %d, dim %lld and %lld, %lld and %lld chains", a->cfg.target, b->cfg.target,
+                    (long long)a->d, (long long)b->d, (long long)a->N, (long long)b->N);
+    if (a->world != 1 || b->world != 1)
+        return fail(nullptr, "pte_overlap_create: world_size must be 1 (got %d and %d); a sharded pair is not supported", a->world, b->world);
+    if (a->cfg.n_chains_variational > 0 || b->cfg.n_chains_variational > 0)
+        return fail(nullptr, "pte_overlap_create: n_chains_variational must be 0 (got %lld and %lld); a two-leg ladder holds every temperature twice",
+                    (long long)a->cfg.n_chains_variational, (long long)b->cfg.n_chains_variational);
+    const bool glass = a->cfg.target != PTE_TARGET_ISING;
+    for (pte_engine *h : {a, b})
+        if (!family_ready(h))
+            return fail(nullptr, "pte_overlap_create: engine %s has no bonds yet; call %s first", h == a ? "a" : "b",
+                        h->cfg.target == PTE_TARGET_SPIN_GLASS_3D ? "pte_set_target_spin_glass_3d" : "pte_set_target_spin_glass");
+    if (hipSetDevice(a->cfg.device) != hipSuccess) return fail(nullptr, "pte_overlap_create: hipSetDevice(%d) failed", a->cfg.device);
+    if (glass) {
+        std::vector<unsigned char> ja, jb;
+        if (download_bonds(a, ja)) return fail(nullptr, "pte_overlap_create: %s", a->err.c_str());
+        if (download_bonds(b, jb)) return fail(nullptr, "pte_overlap_create: %s", b->err.c_str());
+        size_t i = 0;
+        while (i < ja.size() && ja[i] == jb[i]) ++i;
+        if (i < ja.size())
+            return fail(nullptr, "pte_overlap_create: the engines' bonds differ (first at %s %lld of the device planes); the overlap is between two copies of ONE "
+                                 "disorder sample", a->cfg.target == PTE_TARGET_SPIN_GLASS_3D ? "word" : "site", (long long)(a->cfg.target == PTE_TARGET_SPIN_GLASS_3D ? i / 4 : i));
+    }
+    const int64_t N = a->N, d = a->d;
+    if (d < 1 || d > OVERLAP_MAX_DIM) return fail(nullptr, "pte_overlap_create: dim must be in 1..%d (got %lld)", OVERLAP_MAX_DIM, (long long)d);
+    if ((double)N * (double)(d + 1) * 8.0 > 2147483648.0)
+        return fail(nullptr, "pte_overlap_create: the histograms of %lld chains x %lld bins take %.0f bytes, more than the 2 GiB this recorder allows",
+                    (long long)N, (long long)(d + 1), (double)N * (double)(d + 1) * 8.0);
+    pte_overlap *ov = new pte_overlap();
+    ov->a = a; ov->b = b; ov->device = a->cfg.device; ov->N = N; ov->d = d;
+    if (a->cfg.target == PTE_TARGET_SPIN_GLASS_3D) { ov->geom = OVERLAP_GEOM_CUBE; ov->L = (int)lattice3d_base_length(d); ov->n_links = 3 * d; }
+    else {
+        ov->L = (int)std::llround(std::sqrt((double)d));
+        if (ov->L % 32 == 0) { ov->geom = OVERLAP_GEOM_SQUARE; ov->n_links = 2 * d; }
+    }
+    ov->words = (size_t)N * (size_t)(d + 1) + 4 * (size_t)N;
+    hipError_t e = hipMalloc((void **)&ov->d_acc, sizeof(int64_t) * ov->words);
+    if (e == hipSuccess) e = hipMemsetAsync(ov->d_acc, 0, sizeof(int64_t) * ov->words, a->stream);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ov->ev_b, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ov->ev_rec, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipStreamSynchronize(a->stream);
+    if (e != hipSuccess) { pte_overlap_destroy(ov); return fail(nullptr, "pte_overlap_create: %s", hipGetErrorString(e)); }
+    int64_t *p = ov->d_acc;
+    ov->acc.hist = p; p += (size_t)N * (size_t)(d + 1);
+    ov->acc.n = p; ov->acc.link_n = p + N; ov->acc.link_sum = p + 2 * N; ov->acc.link_sum2 = p + 3 * N;
+    ov->snap.assign(ov->words, 0);
+    *out = ov;
+    return 0;
+}
+
+// touches neither engine: both stay usable, and either may have been destroyed before
+int pte_overlap_destroy(pte_overlap *ov) {
+    if (!ov) return 0;
+    hipSetDevice(ov->device);
+    if (ov->ev_b) hipEventDestroy(ov->ev_b);
+    if (ov->ev_rec) hipEventDestroy(ov->ev_rec);
+    if (ov->d_acc) hipFree(ov->d_acc);
+    delete ov;
+    return 0;
+}
+
+int pte_overlap_info(const pte_overlap *ov, int64_t *n_chains, int64_t *dim, int64_t *n_links) {
+    if (!ov) return 1;
+    if (n_chains) *n_chains = ov->N;
+    if (dim) *dim = ov->d;
+    if (n_links) *n_links = ov->n_links;
+    return 0;
+}
+
+int pte_overlap_record(pte_overlap *ov) {
+    if (!ov) return 1;
+    if (overlap_entry(ov, "pte_overlap_record")) return 1;
+    pte_engine *a = ov->a;
+    HIP_OK(a, hipSetDevice(ov->device));
+    if (overlap_enqueue_record(ov)) return 1;
+    HIP_OK(a, hipStreamSynchronize(a->stream));
+    return 0;
+}
+
+// for s = first_scan .. first_scan + n_scans - 1: explore!(s), communicate!(s) of A on A's stream and of B on B's, then one record of the
+// post-swap states on A's stream behind B's swap; B's next explore waits for the record.  The launches are those of pte_run_scans on a
+// lattice engine (explore and swap per scan), so each engine ends where pte_run_scans alone would have left it.
+int pte_overlap_run_scans(pte_overlap *ov, int64_t first_scan, int64_t n_scans) {
+    if (!ov) return 1;
+    if (overlap_entry(ov, "pte_overlap_run_scans")) return 1;
+    pte_engine *a = ov->a, *b = ov->b;
+    HIP_OK(a, hipSetDevice(ov->device));
+    auto from_b = [&](int rc) { if (rc) a->err = b->err; return rc; };
+    for (int64_t s = first_scan; s < first_scan + n_scans; ++s) {
+        if (launch_explore(a, s) || launch_swap(a, s)) return 1;
+        if (from_b(launch_explore(b, s) || launch_swap(b, s))) return 1;
+        if (overlap_enqueue_record(ov)) return 1;
+    }
+    const int rc_a = check_device_error(a), rc_b = check_device_error(b);
+    time_collect(a);
+    time_collect(b);
+    if (rc_a) return rc_a;
+    return from_b(rc_b);
+}
+
+int pte_overlap_reduce(pte_overlap *ov) {
+    if (!ov) return 1;
+    pte_engine *a = ov->a;
+    HIP_OK(a, hipSetDevice(ov->device));
+    HIP_OK(a, hipMemcpyAsync(ov->snap.data(), ov->d_acc, sizeof(int64_t) * ov->words, hipMemcpyDeviceToHost, a->stream));
+    HIP_OK(a, hipMemsetAsync(ov->d_acc, 0, sizeof(int64_t) * ov->words, a->stream));
+    HIP_OK(a, hipStreamSynchronize(a->stream));
+    return 0;
+}
+
+int pte_overlap_get(const pte_overlap *ov, int64_t *n, int64_t *hist, int64_t *link_n, int64_t *link_sum, int64_t *link_sum2) {
+    if (!ov) return 1;
+    const size_t N = (size_t)ov->N, H = N * (size_t)(ov->d + 1);
+    const int64_t *s = ov->snap.data();
+    if (hist) std::memcpy(hist, s, sizeof(int64_t) * H);
+    if (n) std::memcpy(n, s + H, sizeof(int64_t) * N);
+    if (link_n) std::memcpy(link_n, s + H + N, sizeof(int64_t) * N);
+    if (link_sum) std::memcpy(link_sum, s + H + 2 * N, sizeof(int64_t) * N);
+    if (link_sum2) std::memcpy(link_sum2, s + H + 3 * N, sizeof(int64_t) * N);
+    return 0;
 }
 
 const char *pte_kernel_name(const pte_engine *h) {

@@ -19,14 +19,6 @@
 
 namespace pte {
 
-// row r of the HBM bit string: bits [r L, r L + L), a funnel shift of the two words it may straddle (the second is read only where the row
-// reaches into it: never past the word of the row's last bit)
-__device__ __forceinline__ unsigned lattice3d_load_row(const unsigned *wrow, int r, int L, unsigned mask) {
-    const int o = r * L, w = o >> 5, sh = o & 31;
-    const unsigned lo = wrow[w], hi = sh + L > 32 ? wrow[w + 1] : 0u;
-    return (unsigned)(((((uint64_t)hi) << 32) | lo) >> sh) & mask;
-}
-
 struct Checker3DThresholds { uint64_t t4, t8, t12; };
 __device__ __forceinline__ Checker3DThresholds checker3d_thresholds(double beta, double bt) {
     auto uniform64 = [](uint64_t v) {

@@ -15,6 +15,15 @@ struct SpinGlass3DParams {
     const unsigned *jw = nullptr;          // three planes of L * L words: JX, then JY, then JZ
 };
 
+// row r of the HBM bit string: bits [r L, r L + L), a funnel shift of the two words it may straddle (the second is read only where the row
+// reaches into it: never past the word of the row's last bit).  Here, not in pte_lattice3d.hpp: the overlap kernel (pte_overlap.hpp, a
+// unit of its own) takes its rows the same way.
+__device__ __forceinline__ unsigned lattice3d_load_row(const unsigned *wrow, int r, int L, unsigned mask) {
+    const int o = r * L, w = o >> 5, sh = o & 31;
+    const unsigned lo = wrow[w], hi = sh + L > 32 ? wrow[w + 1] : 0u;
+    return (unsigned)(((((uint64_t)hi) << 32) | lo) >> sh) & mask;
+}
+
 // one launch of the CheckerboardMetropolis sweep on this target (k_explore_checkerboard3d), one workgroup of one wave per replica
 int lattice3d_launch(const LaunchSite &at, const EngineDev &dev, const SpinGlass3DParams &gp);
 int lattice3d_refresh_stats(unsigned N, hipStream_t stream, const EngineDev &dev, const SpinGlass3DParams &gp);     // k_refresh_lattice3d_stats

@@ -1,0 +1,5 @@
+// pte_overlap.hip -- the twelfth translation unit of libpte.so: the replica-overlap kernel (pte_overlap.hpp) behind overlap_launch.
+// Compiled with the flags of pte_lattice3d.hip (-O2, -amdgpu-sched-strategy=max-ilp); a unit of its own keeps the generated code of the
+// shipped kernels unchanged.  The kernel draws no random number: the unit needs no RNG-policy setter (it is not in PTE_KERNEL_UNITS).
+#define PTE_TU_LANGEVIN 1          // pte_kernels.hpp, pte_ising.hpp: leave the engine's non-template kernels to pte.hip
+#include "pte_overlap.hpp"

@@ -648,4 +648,36 @@ function run_scans_group!(rs::Vector{DeviceReplicas}, first_scan, n_scans)
     check(rs[1], ccall((:pte_group_run_scans, libpte), Cint, (Ptr{Ptr{Cvoid}}, Int32, Int64, Int64), hs, length(hs), first_scan, n_scans))
 end
 
+# ---- the replica overlap between two runs of a lattice family (include/pte.h pte_overlap_*; DESIGN 4.20) -----------------------
+"""The overlap recorder over two `DeviceReplicas` of the same lattice model (same bonds, N and schedule; different seeds).  It holds no
+state of either; `close!` leaves both usable.  `n_links == 0`: no link overlap is recorded on this lattice."""
+mutable struct DeviceOverlap
+    handle::Ptr{Cvoid}
+    a::DeviceReplicas
+    b::DeviceReplicas
+    n_chains::Int
+    dim::Int
+    n_links::Int
+end
+function DeviceOverlap(a::DeviceReplicas, b::DeviceReplicas)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = ccall((:pte_overlap_create, libpte), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Ptr{Cvoid}}), a.handle, b.handle, h)
+    rc == 0 || error(unsafe_string(ccall((:pte_last_error, libpte), Cstring, (Ptr{Cvoid},), C_NULL)))
+    n, d, nl = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+    check(a, ccall((:pte_overlap_info, libpte), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}), h[], n, d, nl))
+    return DeviceOverlap(h[], a, b, n[], d[], nl[])
+end
+close!(o::DeviceOverlap) = (ccall((:pte_overlap_destroy, libpte), Cint, (Ptr{Cvoid},), o.handle); o.handle = C_NULL; nothing)
+record!(o::DeviceOverlap) = check(o.a, ccall((:pte_overlap_record, libpte), Cint, (Ptr{Cvoid},), o.handle))
+run_scans!(o::DeviceOverlap, first_scan, n_scans) =
+    check(o.a, ccall((:pte_overlap_run_scans, libpte), Cint, (Ptr{Cvoid}, Int64, Int64), o.handle, first_scan, n_scans))
+"""-> (n, hist [d + 1, N] (column c = chain c), link_n, link_sum, link_sum2), all Int64; the device's accumulators start again from zero"""
+function reduce!(o::DeviceOverlap)
+    check(o.a, ccall((:pte_overlap_reduce, libpte), Cint, (Ptr{Cvoid},), o.handle))
+    n, ln, ls, ls2 = (zeros(Int64, o.n_chains) for _ in 1:4)
+    hist = zeros(Int64, o.dim + 1, o.n_chains)          # the ABI's row-major [N][d + 1]
+    check(o.a, ccall((:pte_overlap_get, libpte), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}), o.handle, n, hist, ln, ls, ls2))
+    return (n = n, hist = hist, link_n = ln, link_sum = ls, link_sum2 = ls2)
+end
+
 end # module

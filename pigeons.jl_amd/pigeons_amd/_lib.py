@@ -98,6 +98,8 @@ EXPORTS = [
     "pte_set_target_dense",
     "pte_set_target_spin_glass",
     "pte_set_target_spin_glass_3d",
+    "pte_overlap_create", "pte_overlap_destroy", "pte_overlap_info", "pte_overlap_record", "pte_overlap_run_scans", "pte_overlap_reduce",
+    "pte_overlap_get",
 ]
 
 _libs = {}
@@ -211,6 +213,13 @@ def load(path=None):
     L.pte_scan_loop_name.restype = C.c_char_p
     L.pte_scan_loop_info.argtypes = [vp, ip, ip, ip]
     L.pte_scan_loop_stats.argtypes = [vp, ip, ip, i32p]
+    L.pte_overlap_create.argtypes = [vp, vp, C.POINTER(vp)]
+    L.pte_overlap_destroy.argtypes = [vp]
+    L.pte_overlap_info.argtypes = [vp, ip, ip, ip]
+    L.pte_overlap_record.argtypes = [vp]
+    L.pte_overlap_run_scans.argtypes = [vp, C.c_int64, C.c_int64]
+    L.pte_overlap_reduce.argtypes = [vp]
+    L.pte_overlap_get.argtypes = [vp, ip, ip, ip, ip, ip]
     for name in EXPORTS:
         if name not in ("pte_last_error", "pte_boundary_payload_bytes", "pte_get_stream", "pte_shard_message_bytes", "pte_kernel_name", "pte_scan_loop_name"):
             getattr(L, name).restype = C.c_int
