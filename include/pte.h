@@ -438,7 +438,7 @@ int pte_group_run_scans(pte_engine *const *engines, int32_t n_engines, int64_t f
  *   pte_overlap_record    one record of the states as they are; synchronous
  *   pte_overlap_run_scans for s = first_scan .. first_scan + n_scans - 1: explore!(s) and communicate!(s) of a on a's stream and of b on
  *                         b's, then one record of the post-swap states; each engine ends exactly where pte_run_scans alone would have
- *                         left it.  record and run_scans refuse when the two engines' schedules differ in any bit, and a poisoned engine
+ *                         left it unless the cluster move is on.  record and run_scans refuse when the two engines' schedules differ in any bit, and a poisoned engine
  *   pte_overlap_reduce    snapshot the accumulators to the host and zero them on the device
  *   pte_overlap_get       the snapshot: n[N], hist[N][dim + 1], link_n[N], link_sum[N], link_sum2[N]; NULLs are skipped */
 typedef struct pte_overlap pte_overlap;
@@ -449,6 +449,31 @@ int pte_overlap_record(pte_overlap *ov);
 int pte_overlap_run_scans(pte_overlap *ov, int64_t first_scan, int64_t n_scans);
 int pte_overlap_reduce(pte_overlap *ov);
 int pte_overlap_get(const pte_overlap *ov, int64_t *n, int64_t *hist, int64_t *link_n, int64_t *link_sum, int64_t *link_sum2);
+
+/* ---- Houdayer's cluster move between the two copies (the project's own specification; off after pte_overlap_create) ----
+ * For chain c with betas[c] >= min_beta, t = a XOR b as above and k = popcount(t): if k == 0 nothing is written and empty[c] += 1; else
+ *   the draw     u = mix64(seed + (uint64)(m N + c + 1) 0x9E3779B97F4A7C15) mod 2^64, m the launch counter (0 at set, +1 per launch);
+ *                j = ((u >> 32) k) >> 32; the seed site is the j-th set bit of t in increasing site index.  No engine's RNG word is read
+ *   the cluster  C = the connected component of the seed site among the set bits of t under the lattice's nearest-neighbour links with
+ *                periodic wrap (4 on the square, 6 on the cube; the bonds' signs play no part; diagonal contact does not connect)
+ *   the flip     a ^= C, b ^= C in both engines' rows; S_a + S_b is unchanged, so the move is always accepted, and it is its own inverse
+ *   the swap's   delta = sum_dir (4 popcount(B & x) - 2 popcount(B)), B = C XOR shift_dir(C), x = a XOR shift_dir(a) XOR J_dir, every site
+ *   statistic    owning its +dir bond: the pair sum of a's replica gains delta, that of b's replica loses it, as exact integers
+ * It runs on the cube at every base_length and on the 2-D lattices where base_length % 32 == 0 (the link overlap's condition).
+ * Accumulators per chain, int64, zeroed by pte_overlap_reduce with the others: n moves made, empty moves with k == 0, size_sum += |C|,
+ * k_sum += k, abs_ds_sum += |delta|, passes_sum += passes of the kernel's fixed-point loop (a measurement, not part of the specification).
+ *   pte_overlap_set_cluster_move  every = 0 turns the move off; otherwise pte_overlap_run_scans launches it at every scan s with
+ *                                 s % every == 0, after both swaps and before the record (whose values it does not change: t stays).
+ *                                 Refuses, naming what it got: every < 0; min_beta outside [0, 1] or NaN; a 2-D lattice whose base_length
+ *                                 is not a multiple of 32.  Resets m
+ *   pte_overlap_cluster_move      one move on the states as they are; synchronous; the entry checks of pte_overlap_record; refused if the
+ *                                 move was never set
+ *   pte_overlap_cluster_get       the snapshot taken by pte_overlap_reduce: the six arrays [N] and the number of launches it covers;
+ *                                 NULLs are skipped */
+int pte_overlap_set_cluster_move(pte_overlap *ov, int64_t every, double min_beta, uint64_t seed);
+int pte_overlap_cluster_move(pte_overlap *ov);
+int pte_overlap_cluster_get(const pte_overlap *ov, int64_t *n, int64_t *empty, int64_t *size_sum, int64_t *k_sum, int64_t *abs_ds_sum, int64_t *passes_sum,
+                            int64_t *moves_launched);
 
 /* Name of the kernel that explores on this engine (e.g. "k_explore_slice8"), for profiles and bench.py. */
 const char *pte_kernel_name(const pte_engine *h);

@@ -36,6 +36,7 @@
 #include "pte_checkerboard_params.hpp"
 #include "pte_lattice3d_params.hpp"
 #include "pte_overlap_params.hpp"
+#include "pte_cluster_params.hpp"
 #else                              // tools / development builds: one translation unit
 #include "pte_langevin_launch.hpp"
 #include "pte_aaps.hpp"
@@ -51,6 +52,7 @@
 #include "pte_checkerboard.hpp"
 #include "pte_lattice3d.hpp"
 #include "pte_overlap.hpp"
+#include "pte_cluster.hpp"
 #endif
 #include "pte_ising.hpp"
 #if defined(PTE_PROFILE_AM)               // debug builds only (tools/prof_automala.py): 12 words per wave, section times of k_explore_automala
@@ -2140,6 +2142,15 @@ struct pte_overlap {
     hipEvent_t ev_b = nullptr;            // B's stream has finished what the record reads
     hipEvent_t ev_rec = nullptr;          // the record has read B's rows: B's next explore may write them
     std::vector<int64_t> snap;            // the accumulators of the last pte_overlap_reduce
+    // Houdayer's cluster move (pte_cluster.hpp): off until pte_overlap_set_cluster_move
+    int64_t *d_cl = nullptr;              // one allocation: n, empty, size_sum, k_sum, abs_ds_sum, passes_sum, [N] each
+    ClusterAcc cl_acc{};
+    bool cl_set = false;
+    int64_t cl_every = 0;                 // run_scans launches the move at every scan s with s % every == 0; 0 = never
+    double cl_min_beta = 0.0;
+    uint64_t cl_seed = 0, cl_m = 0;       // the move's own stream: the seed and the launch counter
+    int64_t cl_launched = 0;              // launches since the last pte_overlap_reduce
+    std::vector<int64_t> cl_snap;         // the six accumulators of the last pte_overlap_reduce, then the launches it covers
 };
 
 namespace {
@@ -2169,13 +2180,24 @@ int overlap_entry(pte_overlap *ov, const char *what) {
     return 0;
 }
 
-// one record on A's stream, ordered behind what B's stream holds so far; B's stream then waits for it
-int overlap_enqueue_record(pte_overlap *ov) {
+// one cluster move and / or one record on A's stream, the move first, ordered behind what B's stream holds so far; B's stream then waits for
+// them: one hand-over whatever is launched.  The move writes both engines' rows and suff; the record reads t = a xor b, which the move leaves
+int overlap_enqueue(pte_overlap *ov, bool move, bool record) {
     pte_engine *a = ov->a, *b = ov->b;
     HIP_OK(a, hipEventRecord(ov->ev_b, b->stream));
     HIP_OK(a, hipStreamWaitEvent(a->stream, ov->ev_b, 0));
-    if (overlap_launch(a->stream, OverlapSide{a->dev.x, a->dev.ld, a->dev.slot_of_chain}, OverlapSide{b->dev.x, b->dev.ld, b->dev.slot_of_chain},
-                       (int)ov->d, (int)ov->N, ov->geom, ov->L, ov->acc))
+    if (move) {
+        const unsigned *jw = a->cfg.target == PTE_TARGET_SPIN_GLASS_3D ? a->spinglass3d.jw : a->cfg.target == PTE_TARGET_SPIN_GLASS ? a->spinglass.jw : nullptr;
+        if (cluster_launch(a->stream, ClusterSide{a->dev.x, a->dev.ld, a->dev.slot_of_chain, a->dev.suff}, ClusterSide{b->dev.x, b->dev.ld, b->dev.slot_of_chain, b->dev.suff},
+                           ClusterMove{(int)ov->d, (int)ov->N, ov->geom, ov->L, jw, a->dev.beta, ov->cl_min_beta,
+                                       ov->cl_seed + ov->cl_m * (uint64_t)ov->N * CLUSTER_GAMMA}, ov->cl_acc))
+            return fail(a, "this build holds no cluster-move kernel for dim %lld", (long long)ov->d);
+        HIP_OK(a, hipGetLastError());
+        ov->cl_m += 1;
+        ov->cl_launched += 1;
+    }
+    if (record && overlap_launch(a->stream, OverlapSide{a->dev.x, a->dev.ld, a->dev.slot_of_chain}, OverlapSide{b->dev.x, b->dev.ld, b->dev.slot_of_chain},
+                                 (int)ov->d, (int)ov->N, ov->geom, ov->L, ov->acc))
         return fail(a, "this build holds no overlap kernel for dim %lld", (long long)ov->d);
     HIP_OK(a, hipGetLastError());
     HIP_OK(a, hipEventRecord(ov->ev_rec, a->stream));
@@ -2237,6 +2259,8 @@ int pte_overlap_create(pte_engine *a, pte_engine *b, pte_overlap **out) {
     ov->words = (size_t)N * (size_t)(d + 1) + 4 * (size_t)N;
     hipError_t e = hipMalloc((void **)&ov->d_acc, sizeof(int64_t) * ov->words);
     if (e == hipSuccess) e = hipMemsetAsync(ov->d_acc, 0, sizeof(int64_t) * ov->words, a->stream);
+    if (e == hipSuccess) e = hipMalloc((void **)&ov->d_cl, sizeof(int64_t) * 6 * (size_t)N);
+    if (e == hipSuccess) e = hipMemsetAsync(ov->d_cl, 0, sizeof(int64_t) * 6 * (size_t)N, a->stream);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ov->ev_b, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ov->ev_rec, hipEventDisableTiming);
     if (e == hipSuccess) e = hipStreamSynchronize(a->stream);
@@ -2245,6 +2269,8 @@ int pte_overlap_create(pte_engine *a, pte_engine *b, pte_overlap **out) {
     ov->acc.hist = p; p += (size_t)N * (size_t)(d + 1);
     ov->acc.n = p; ov->acc.link_n = p + N; ov->acc.link_sum = p + 2 * N; ov->acc.link_sum2 = p + 3 * N;
     ov->snap.assign(ov->words, 0);
+    ov->cl_acc = ClusterAcc{ov->d_cl};
+    ov->cl_snap.assign(CLUSTER_ACC_ARRAYS * (size_t)N + 1, 0);
     *out = ov;
     return 0;
 }
@@ -2256,6 +2282,7 @@ int pte_overlap_destroy(pte_overlap *ov) {
     if (ov->ev_b) hipEventDestroy(ov->ev_b);
     if (ov->ev_rec) hipEventDestroy(ov->ev_rec);
     if (ov->d_acc) hipFree(ov->d_acc);
+    if (ov->d_cl) hipFree(ov->d_cl);
     delete ov;
     return 0;
 }
@@ -2273,14 +2300,15 @@ int pte_overlap_record(pte_overlap *ov) {
     if (overlap_entry(ov, "pte_overlap_record")) return 1;
     pte_engine *a = ov->a;
     HIP_OK(a, hipSetDevice(ov->device));
-    if (overlap_enqueue_record(ov)) return 1;
+    if (overlap_enqueue(ov, false, true)) return 1;
     HIP_OK(a, hipStreamSynchronize(a->stream));
     return 0;
 }
 
 // for s = first_scan .. first_scan + n_scans - 1: explore!(s), communicate!(s) of A on A's stream and of B on B's, then one record of the
 // post-swap states on A's stream behind B's swap; B's next explore waits for the record.  The launches are those of pte_run_scans on a
-// lattice engine (explore and swap per scan), so each engine ends where pte_run_scans alone would have left it.
+// lattice engine (explore and swap per scan), so each engine ends where pte_run_scans alone would have left it -- unless the cluster move is
+// on: at every scan s with s % every == 0 it is launched ahead of the record, behind the same event.
 int pte_overlap_run_scans(pte_overlap *ov, int64_t first_scan, int64_t n_scans) {
     if (!ov) return 1;
     if (overlap_entry(ov, "pte_overlap_run_scans")) return 1;
@@ -2290,7 +2318,7 @@ int pte_overlap_run_scans(pte_overlap *ov, int64_t first_scan, int64_t n_scans) 
     for (int64_t s = first_scan; s < first_scan + n_scans; ++s) {
         if (launch_explore(a, s) || launch_swap(a, s)) return 1;
         if (from_b(launch_explore(b, s) || launch_swap(b, s))) return 1;
-        if (overlap_enqueue_record(ov)) return 1;
+        if (overlap_enqueue(ov, ov->cl_every > 0 && s % ov->cl_every == 0, true)) return 1;
     }
     const int rc_a = check_device_error(a), rc_b = check_device_error(b);
     time_collect(a);
@@ -2305,7 +2333,11 @@ int pte_overlap_reduce(pte_overlap *ov) {
     HIP_OK(a, hipSetDevice(ov->device));
     HIP_OK(a, hipMemcpyAsync(ov->snap.data(), ov->d_acc, sizeof(int64_t) * ov->words, hipMemcpyDeviceToHost, a->stream));
     HIP_OK(a, hipMemsetAsync(ov->d_acc, 0, sizeof(int64_t) * ov->words, a->stream));
+    HIP_OK(a, hipMemcpyAsync(ov->cl_snap.data(), ov->d_cl, sizeof(int64_t) * 6 * (size_t)ov->N, hipMemcpyDeviceToHost, a->stream));
+    HIP_OK(a, hipMemsetAsync(ov->d_cl, 0, sizeof(int64_t) * 6 * (size_t)ov->N, a->stream));
     HIP_OK(a, hipStreamSynchronize(a->stream));
+    ov->cl_snap[6 * (size_t)ov->N] = ov->cl_launched;
+    ov->cl_launched = 0;
     return 0;
 }
 
@@ -2318,6 +2350,43 @@ int pte_overlap_get(const pte_overlap *ov, int64_t *n, int64_t *hist, int64_t *l
     if (link_n) std::memcpy(link_n, s + H + N, sizeof(int64_t) * N);
     if (link_sum) std::memcpy(link_sum, s + H + 2 * N, sizeof(int64_t) * N);
     if (link_sum2) std::memcpy(link_sum2, s + H + 3 * N, sizeof(int64_t) * N);
+    return 0;
+}
+
+// Houdayer's cluster move.  Host, once per call: the refusals, then the three numbers the launches read; the launch counter of
+// the move's stream starts again from 0.  A refused call leaves the setting as it was.
+int pte_overlap_set_cluster_move(pte_overlap *ov, int64_t every, double min_beta, uint64_t seed) {
+    if (!ov) return 1;
+    pte_engine *a = ov->a;
+    if (every < 0) return fail(a, "pte_overlap_set_cluster_move: every must be >= 0 (got %lld); 0 turns the move off", (long long)every);
+    if (!(min_beta >= 0.0 && min_beta <= 1.0)) return fail(a, "pte_overlap_set_cluster_move: min_beta must be in [0, 1] (got %g)", min_beta);
+    if (ov->geom == OVERLAP_GEOM_NONE)
+        return fail(a, "pte_overlap_set_cluster_move: on the 2-D lattices the move runs where base_length %% 32 == 0 (got base_length %d): the packed bond "
+                       "planes exist only there", ov->L);
+    ov->cl_set = true; ov->cl_every = every; ov->cl_min_beta = min_beta; ov->cl_seed = seed; ov->cl_m = 0;
+    return 0;
+}
+
+int pte_overlap_cluster_move(pte_overlap *ov) {
+    if (!ov) return 1;
+    if (overlap_entry(ov, "pte_overlap_cluster_move")) return 1;
+    pte_engine *a = ov->a;
+    if (!ov->cl_set) return fail(a, "pte_overlap_cluster_move: the move was never set; call pte_overlap_set_cluster_move first");
+    HIP_OK(a, hipSetDevice(ov->device));
+    if (overlap_enqueue(ov, true, false)) return 1;
+    HIP_OK(a, hipStreamSynchronize(a->stream));
+    return 0;
+}
+
+int pte_overlap_cluster_get(const pte_overlap *ov, int64_t *n, int64_t *empty, int64_t *size_sum, int64_t *k_sum, int64_t *abs_ds_sum, int64_t *passes_sum,
+                            int64_t *moves_launched) {
+    if (!ov) return 1;
+    const size_t N = (size_t)ov->N;
+    const int64_t *s = ov->cl_snap.data();
+    int64_t *const out[6] = {n, empty, size_sum, k_sum, abs_ds_sum, passes_sum};
+    for (int i = 0; i < 6; ++i)
+        if (out[i]) std::memcpy(out[i], s + i * N, sizeof(int64_t) * N);
+    if (moves_launched) *moves_launched = s[6 * N];
     return 0;
 }
 

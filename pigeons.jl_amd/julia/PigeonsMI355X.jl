@@ -680,4 +680,20 @@ function reduce!(o::DeviceOverlap)
     return (n = n, hist = hist, link_n = ln, link_sum = ls, link_sum2 = ls2)
 end
 
+# Houdayer's cluster move between the two copies (include/pte.h pte_overlap_*cluster*; DESIGN 4.21)
+"""`every = 0` turns the move off; otherwise `run_scans!` makes it at every scan `s` with `s % every == 0`, on the chains with
+`betas[c] >= min_beta`.  The move draws from a stream of its own, keyed by `seed`."""
+set_cluster_move!(o::DeviceOverlap; every = 1, min_beta = 0.0, seed = 1) =
+    check(o.a, ccall((:pte_overlap_set_cluster_move, libpte), Cint, (Ptr{Cvoid}, Int64, Cdouble, UInt64), o.handle, every, min_beta, seed))
+cluster_move!(o::DeviceOverlap) = check(o.a, ccall((:pte_overlap_cluster_move, libpte), Cint, (Ptr{Cvoid},), o.handle))
+"""-> the cluster accumulators of the last `reduce!`, all Int64 and keyed by chain, and the number of launches they cover"""
+function cluster_record(o::DeviceOverlap)
+    n, empty, size_sum, k_sum, abs_ds_sum, passes_sum = (zeros(Int64, o.n_chains) for _ in 1:6)
+    launched = Ref{Int64}(0)
+    check(o.a, ccall((:pte_overlap_cluster_get, libpte), Cint,
+                     (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+                     o.handle, n, empty, size_sum, k_sum, abs_ds_sum, passes_sum, launched))
+    return (n = n, empty = empty, size_sum = size_sum, k_sum = k_sum, abs_ds_sum = abs_ds_sum, passes_sum = passes_sum, moves_launched = launched[])
+end
+
 end # module

@@ -20,4 +20,4 @@ from .pt import (Inputs, PT, pigeons, toy_mvn_target, ScaledPrecisionNormalPath,
 from .checkpoint import write_checkpoint, load_checkpoint, latest_checkpoint_folder, increment_n_rounds
 from .tempering import (Schedule, equally_spaced_schedule, optimal_schedule,
                         FritschCarlsonMonotonicInterpolation, CommunicationBarriers, rejections)
-from .overlap import Overlap, OverlapRecord, PTPair, pigeons_pair, adapt_pair, run_pair_round
+from .overlap import Overlap, OverlapRecord, PTPair, pigeons_pair, adapt_pair, run_pair_round, HoudayerMove, ClusterRecord

@@ -8,6 +8,13 @@ the Binder ratio, which tell the glassy phase from the paramagnet where the magn
   Overlap(eng_a, eng_b)      the ctypes wrapper of pte_overlap_* (include/pte.h)
   OverlapRecord              the reduced accumulators of one round and what is computed from them
   pigeons_pair(...) -> PTPair   the round loop: the two engines kept in step scan by scan, their ladders kept equal round by round
+
+Two copies at one temperature also admit Houdayer's cluster move (Houdayer 2001; with parallel tempering the isoenergetic cluster
+move of Zhu, Ochoa and Katzgraber 2015): the connected cluster of disagreeing sites around a drawn one is flipped in both copies, which
+leaves the sum of the two energies as it was -- always accepted, and non-local where single-spin flips are frozen.  Off unless asked for.
+
+  HoudayerMove(every, min_beta, seed)   the setting: Overlap.set_cluster_move(move), pigeons_pair(cluster_move=move)
+  ClusterRecord                         the reduced accumulators of the move
 """
 import ctypes as C
 import dataclasses
@@ -63,6 +70,52 @@ class OverlapRecord:
         return out
 
 
+@dataclass
+class HoudayerMove:
+    """Houdayer's cluster move between the two copies of a pair: made at every scan s with s % every == 0 (0: never), on the chains with
+    betas[c] >= min_beta -- in three dimensions the disagreeing sites percolate at high temperature and the move then only relabels the copies
+    (ClusterRecord.mean_fraction() shows where) -- from a stream of its own keyed by seed (None: the pair's Inputs.seed)."""
+    every: int = 1
+    min_beta: float = 0.0
+    seed: Any = None
+
+    def __post_init__(self):
+        if isinstance(self.every, bool) or not isinstance(self.every, (int, np.integer)) or self.every < 0:
+            raise ValueError("HoudayerMove: every must be an integer >= 0 (got %r); 0 turns the move off" % (self.every,))
+        if not (isinstance(self.min_beta, (int, float, np.integer, np.floating)) and 0.0 <= float(self.min_beta) <= 1.0):
+            raise ValueError("HoudayerMove: min_beta must be in [0, 1] (got %r)" % (self.min_beta,))
+        if self.seed is not None and (isinstance(self.seed, bool) or not isinstance(self.seed, (int, np.integer)) or not 0 <= int(self.seed) < 2 ** 64):
+            raise ValueError("HoudayerMove: seed must be None or an integer in 0 .. 2^64 - 1 (got %r)" % (self.seed,))
+
+
+@dataclass
+class ClusterRecord:
+    """The cluster move's accumulators of one pte_overlap_reduce, all int64 and keyed by chain, and the schedule in force meanwhile."""
+    betas: Any          # float64 [N]
+    n: Any              # [N] moves made (chains below min_beta: 0)
+    empty: Any          # [N] moves that found the two copies equal (k = 0) and wrote nothing
+    size_sum: Any       # [N] sum of |C|, the sites flipped
+    k_sum: Any          # [N] sum of k, the sites at which the copies differed
+    abs_ds_sum: Any     # [N] sum of |delta|, the pair sum handed from one copy to the other
+    passes_sum: Any     # [N] sum of the passes of the kernel's fixed-point loop (a cost figure, not part of the specification)
+    moves_launched: int = 0   # launches the record covers
+
+    def mean_fraction(self):
+        """size_sum / k_sum per chain: the share of the disagreeing sites a move flips.  Near 1 the sites percolate and the move only relabels
+        the copies: put min_beta above those chains.  NaN where k_sum == 0."""
+        k = np.asarray(self.k_sum, dtype=np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(k > 0, np.asarray(self.size_sum, dtype=np.float64) / k, np.nan)
+
+
+def cluster_move_geometry(target):
+    """None where the move runs on this lattice target (the cube; the 2-D lattices with base_length % 32 == 0), else the refusal's text"""
+    if isinstance(target, SpinGlass3DLogPotential) or int(target.base_length) % 32 == 0:
+        return None
+    return ("HoudayerMove runs on the cube and on the 2-D lattices whose base_length is a multiple of 32 (got base_length %d): the packed "
+            "bond planes exist only there" % int(target.base_length))
+
+
 class Overlap:
     """pte_overlap_*: the overlap recorder over two engines.  It holds no state of either engine; close() leaves both usable."""
 
@@ -108,20 +161,50 @@ class Overlap:
         n, link_n, link_sum, link_sum2 = (np.zeros(self.N, dtype=np.int64) for _ in range(4))
         hist = np.zeros((self.N, self.d + 1), dtype=np.int64)
         self._chk(self.L.pte_overlap_get(self.h, _ip(n), _ip(hist), _ip(link_n), _ip(link_sum), _ip(link_sum2)))
+        self._cluster_betas = betas
         return OverlapRecord(betas, self.d, self.n_links, n, hist, link_n, link_sum, link_sum2)
+
+    def set_cluster_move(self, move, seed=None):
+        """the setting of Houdayer's cluster move from now on (move.seed None: `seed`); the launch counter of its stream starts again from 0"""
+        if not isinstance(move, HoudayerMove):
+            raise TypeError("Overlap.set_cluster_move: expected a HoudayerMove (got %r)" % (move,))
+        s = move.seed if move.seed is not None else seed
+        if s is None:
+            raise ValueError("Overlap.set_cluster_move: HoudayerMove(seed=None) needs the seed of the run; pass seed=")
+        self._chk(self.L.pte_overlap_set_cluster_move(self.h, int(move.every), float(move.min_beta), int(s)))
+
+    def cluster_move(self):
+        """one cluster move on the two engines' states as they are"""
+        self._chk(self.L.pte_overlap_cluster_move(self.h))
+
+    def reduce_clusters(self):
+        """-> ClusterRecord of the moves covered by the last reduce(): one pte_overlap_reduce snapshots and zeroes the overlap's and the
+        move's accumulators together, so a round calls reduce(), then this"""
+        betas = getattr(self, "_cluster_betas", None)
+        if betas is None:
+            betas = self.a.schedule()
+        arrays = [np.zeros(self.N, dtype=np.int64) for _ in range(6)]
+        launched = np.zeros(1, dtype=np.int64)
+        self._chk(self.L.pte_overlap_cluster_get(self.h, *[_ip(v) for v in arrays], _ip(launched)))
+        return ClusterRecord(betas, *arrays, moves_launched=int(launched[0]))
 
 
 class PTPair:
     """Two PTs over one target and an Overlap between their engines.  `a` and `b` stay ordinary PTs (stepping_stone, n_round_trips, ... work
-    on each); `overlap` is the OverlapRecord of the last round, `overlaps` holds one per round."""
+    on each); `overlap` is the OverlapRecord of the last round, `overlaps` holds one per round; with a cluster move, `cluster` and `clusters`
+    hold its ClusterRecords the same way."""
 
     def __init__(self, a, b, recorder=None):
         self.a, self.b, self.recorder = a, b, recorder
         self.overlap, self.overlaps = None, []
+        self.cluster_move = None                        # the HoudayerMove in force (pigeons_pair(cluster_move=...)), or None
+        self.cluster, self.clusters = None, []          # its ClusterRecord of the last round and of every round
 
 
-def check_pair_inputs(inputs, seed_b, pt_kwargs=()):
+def check_pair_inputs(inputs, seed_b, pt_kwargs=(), cluster_move=None):
     """what a pair refuses, before any device work"""
+    if cluster_move is not None and not isinstance(cluster_move, HoudayerMove):
+        raise TypeError("pigeons_pair: cluster_move must be None or a HoudayerMove (got %r)" % (cluster_move,))
     sharding = [k for k in SHARDING_ARGUMENTS if k in pt_kwargs]
     if sharding:
         raise NotImplementedError("pigeons_pair: sharded or multi-GPU pairs are not supported (got %s)" % ", ".join(sharding))
@@ -135,6 +218,8 @@ def check_pair_inputs(inputs, seed_b, pt_kwargs=()):
         raise NotImplementedError("pigeons_pair: checkpoint=True is not supported: a pair has no checkpoint format")
     if seed_b == inputs.seed:
         raise ValueError("pigeons_pair: seed_b must differ from seed (both %d): identical runs give q = 1 at every record" % inputs.seed)
+    if cluster_move is not None and cluster_move_geometry(inputs.target):
+        raise NotImplementedError("pigeons_pair: " + cluster_move_geometry(inputs.target))
 
 
 def run_pair_round(pair):
@@ -147,6 +232,9 @@ def run_pair_round(pair):
     red_a, red_b = reduce_recorders(pair.a, elapsed), reduce_recorders(pair.b, elapsed)
     pair.overlap = pair.recorder.reduce()
     pair.overlaps.append(pair.overlap)
+    if pair.cluster_move is not None:
+        pair.cluster = pair.recorder.reduce_clusters()
+        pair.clusters.append(pair.cluster)
     return red_a, red_b
 
 
@@ -169,17 +257,21 @@ def adapt_pair(pair, red_a, red_b):
     return pair
 
 
-def pigeons_pair(seed_b=None, **inputs_kwargs):
+def pigeons_pair(seed_b=None, cluster_move=None, **inputs_kwargs):
     """pigeons(; ...) twice over, in step: two PTs over the same target and inputs with seeds `seed` and `seed_b` (default seed + 1), the
-    overlap between them recorded at every scan -> PTPair.  Only the first run prints its report."""
+    overlap between them recorded at every scan -> PTPair.  Only the first run prints its report.  cluster_move: None, or the HoudayerMove
+    made between the two copies (its accumulators per round in pair.clusters, the last in pair.cluster)."""
     pt_kwargs = {k: inputs_kwargs.pop(k) for k in SHARDING_ARGUMENTS if k in inputs_kwargs}
     inputs = Inputs(**inputs_kwargs)
     if seed_b is None:
         seed_b = inputs.seed + 1
-    check_pair_inputs(inputs, seed_b, pt_kwargs)
+    check_pair_inputs(inputs, seed_b, pt_kwargs, cluster_move)
     a = PT(inputs)
     b = PT(dataclasses.replace(inputs, seed=seed_b, show_report=False, record=list(inputs.record)))
     pair = PTPair(a, b, Overlap(a.replicas, b.replicas))
+    pair.cluster_move = cluster_move
+    if cluster_move is not None:
+        pair.recorder.set_cluster_move(cluster_move, seed=inputs.seed)
     while next_round(a) and next_round(b):
         adapt_pair(pair, *run_pair_round(pair))
         report(a)
