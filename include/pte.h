@@ -347,6 +347,8 @@ int pte_set_target_changepoint(pte_engine *h, const double *y /*[n_obs]*/, int64
 enum { PTE_CHANGEPOINT_FORM_AUTO = 0, PTE_CHANGEPOINT_FORM_FULL = 1, PTE_CHANGEPOINT_FORM_CACHED = 2 };
 int pte_set_changepoint_form(pte_engine *h, int32_t form);
 int pte_get_state(const pte_engine *h, double *state, int64_t *chain, uint64_t *rng);
+/* NULL leaves a field as it is.  chain must be a permutation of the engine's own chains (of a shard: [c0, c0 + K)); it is judged before
+ * anything is copied, so a refused call has changed nothing -- and a poisoned engine (pte_scan_loop_stats) stays poisoned. */
 int pte_set_state(pte_engine *h, const double *state, const int64_t *chain, const uint64_t *rng);
 
 /* ---- chain-sharded engines (one engine per GPU; rank g owns chains [g*N/G, (g+1)*N/G)) -----------

@@ -2901,19 +2901,20 @@ int pte_set_state(pte_engine *h, const double *state, const int64_t *chain, cons
     if (!h) return 1;
     HIP_OK(h, hipSetDevice(h->cfg.device));
     const int64_t N = h->K, d = h->d;
-    if (h->poisoned) {
-        // the one way back after a failure inside the one-launch scan loop: every field of every replica replaced, the round's recorders
-        // discarded, the hand-shake flags re-based to the epochs handed out so far ("every chain has published everything up to now")
-        if ((!state && d > 0) || !chain || !rng) return fail(h, "pte_set_state: a poisoned engine needs state, chain and rng of every replica");
+    // a refused call changes nothing: every argument is judged before the first copy, and a poisoned engine stays poisoned until the last
+    // step below has succeeded
+    const bool revive = h->poisoned;
+    if (revive && ((!state && d > 0) || !chain || !rng)) return fail(h, "pte_set_state: a poisoned engine needs state, chain and rng of every replica");
+    std::vector<int32_t> ch(N), inv(N, -1);
+    if (chain)
+        for (int64_t i = 0; i < N; ++i) {
+            const int64_t cl = chain[i] - h->c0;
+            if (cl < 0 || cl >= N || inv[cl] != -1) return fail(h, "pte_set_state: chain is not a permutation of the local chains");
+            ch[i] = (int32_t)chain[i]; inv[cl] = (int32_t)i;
+        }
+    if (revive) {
         HIP_OK(h, hipStreamSynchronize(h->stream));
         HIP_OK(h, hipMemsetAsync(h->dev.error, 0, 4 * sizeof(int32_t), h->stream));
-        if (h->hs_flag) {
-            std::vector<unsigned long long> fl((size_t)N, h->hs_epoch);
-            HIP_OK(h, hipMemcpyAsync(h->hs_flag, fl.data(), sizeof(unsigned long long) * N, hipMemcpyHostToDevice, h->stream));
-            HIP_OK(h, hipStreamSynchronize(h->stream));
-        }
-        if (reset_recorders(h)) return 1;
-        h->poisoned = false;
     }
     std::vector<uint32_t> packed;
     if (state && d > 0 && on_lattice(h->cfg.target)) {
@@ -2926,13 +2927,7 @@ int pte_set_state(pte_engine *h, const double *state, const int64_t *chain, cons
     } else if (state && d > 0)
         HIP_OK(h, hipMemcpy2DAsync(h->dev.x, sizeof(double) * h->dev.ld, state, sizeof(double) * d,
                                    sizeof(double) * d, N, hipMemcpyHostToDevice, h->stream));
-    std::vector<int32_t> ch(N), inv(N, -1);
     if (chain) {
-        for (int64_t i = 0; i < N; ++i) {
-            const int64_t cl = chain[i] - h->c0;
-            if (cl < 0 || cl >= N || inv[cl] != -1) return fail(h, "pte_set_state: chain is not a permutation of the local chains");
-            ch[i] = (int32_t)chain[i]; inv[cl] = (int32_t)i;
-        }
         HIP_OK(h, hipMemcpyAsync(h->dev.chain_of_slot, ch.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, h->stream));
         HIP_OK(h, hipMemcpyAsync(h->dev.slot_of_chain, inv.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, h->stream));
     }
@@ -2973,6 +2968,17 @@ int pte_set_state(pte_engine *h, const double *state, const int64_t *chain, cons
         hipFree(tmp);
         HIP_OK(h, e1);
         if (family_ready(h) && refresh_path_stats(h)) return 1;   // + the target (and variational) log densities, once the family's data is there
+    }
+    if (revive) {
+        // the one way back after a failure inside the one-launch scan loop: every field of every replica replaced above, the round's recorders
+        // discarded, the hand-shake flags re-based to the epochs handed out so far ("every chain has published everything up to now")
+        if (h->hs_flag) {
+            std::vector<unsigned long long> fl((size_t)N, h->hs_epoch);
+            HIP_OK(h, hipMemcpyAsync(h->hs_flag, fl.data(), sizeof(unsigned long long) * N, hipMemcpyHostToDevice, h->stream));
+            HIP_OK(h, hipStreamSynchronize(h->stream));
+        }
+        if (reset_recorders(h)) return 1;
+        h->poisoned = false;
     }
     return 0;
 }

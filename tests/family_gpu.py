@@ -9,6 +9,7 @@ family whose arithmetic differs from its restatement's in less says so in its ow
 1e-12, the change points 1e-13.)
 
 Nothing here touches the device at import: pigeons_amd is imported by the P fixture, when a test first asks for it."""
+import dataclasses
 import math
 
 import numpy as np
@@ -216,15 +217,61 @@ def assert_compose_runs(P, inputs, kernel_name):
     return pt
 
 
-def assert_sharded_equals_single(P, make_inputs, n_shards):
-    """every round of make_inputs() on one engine and on n_shards: index process and traces equal round by round, the final states too"""
-    one, many = P.PT(make_inputs()), P.PT(make_inputs(), n_shards=n_shards)
-    for _ in range(one.inputs.n_rounds):
+def with_recorders(P, inputs, *names):
+    """inputs with the recorders `names` (pigeons_amd's builders) added where its record list lacks them"""
+    have = {b() for b in inputs.record}
+    return dataclasses.replace(inputs, record=list(inputs.record) + [getattr(P, n) for n in names if n not in have])
+
+
+def _same(a, b):
+    """np.array_equal of two recorders (arrays, or tuples of arrays and counts); an entry that is NaN in both is equal"""
+    if isinstance(a, (tuple, list)):
+        return isinstance(b, (tuple, list)) and len(a) == len(b) and all(_same(u, v) for u, v in zip(a, b))
+    a, b = np.asarray(a), np.asarray(b)
+    return np.array_equal(a, b, equal_nan=a.dtype.kind == "f" and b.dtype.kind == "f")
+
+
+def boundary_swap_counts(index_process, final_chain, K):
+    """accepted swaps of each pair (gK - 1, gK), g = 1 .. N / K - 1, read off one engine's index process: index_process[replica][scan] is the
+    chain a replica was on when scan's swap began (the rounds' arrays side by side), final_chain[replica] the chain it ended on.  Only the
+    swap of that pair takes a replica from gK - 1 to gK between two scans"""
+    ip = np.asarray(index_process)
+    nxt = np.concatenate([ip[:, 1:], np.asarray(final_chain)[:, None]], axis=1)
+    return [int(np.sum((ip == b - 1) & (nxt == b))) for b in range(K, ip.shape[0], K)]
+
+
+def assert_sharded_equals_single(P, make_inputs, n_shards, **pt_kw):
+    """every round of make_inputs() on one engine and on n_shards (pt_kw: device_messages=True or transport="group", the drivers of the
+    message kernels; neither: the host two-phase driver).  Round by round and bit for bit: index process, round trips, traces and online where
+    recorded, swap acceptance, log_sum_ratio, the explorer's two recorders, energy_ac1's three arrays, the adapted schedule; then the final
+    states.  Every shard boundary's pair has accepted swaps in the single engine's index process -- a condition on make_inputs(): choose the
+    seed so -- and the shards applied exactly that many, per boundary and side where the device counts them.  Returns the counts"""
+    one, many = P.PT(make_inputs()), P.PT(make_inputs(), n_shards=n_shards, **pt_kw)
+    names = {b() for b in one.inputs.record}
+    assert "index_process" in names, "the boundary swaps are counted from the index process"
+    ips = []
+    for rnd in range(one.inputs.n_rounds):
         assert P.next_round(one) and P.next_round(many)
-        ra = P.run_one_round(one); P.adapt(one, ra)
-        rb = P.run_one_round(many); P.adapt(many, rb)
-        assert np.array_equal(ra.index_process, rb.index_process) and np.array_equal(ra.traces, rb.traces)
+        ra, rb = P.run_one_round(one), P.run_one_round(many)
+        for name in ("index_process", "round_trip", "traces", "online"):
+            if name in names:
+                assert _same(getattr(ra, name), getattr(rb, name)), (rnd, name, getattr(ra, name), getattr(rb, name))
+        for name in ("swap_acceptance_pr", "log_sum_ratio", "explorer_acceptance_pr", "explorer_n_steps", "energy_ac1"):
+            assert _same(getattr(ra, name), getattr(rb, name)), (rnd, name, getattr(ra, name), getattr(rb, name))
+        P.adapt(one, ra); P.adapt(many, rb)
+        assert np.array_equal(one.shared.tempering.schedule.grids, many.shared.tempering.schedule.grids), rnd
+        ips.append(ra.index_process)
     assert_same_states(one.replicas, many.shards)
+    G, K = n_shards, one.inputs.n_chains // n_shards
+    counts = boundary_swap_counts(np.concatenate(ips, axis=1), one.replicas.states()[1], K)
+    assert len(counts) == G - 1 and min(counts) >= 1, counts
+    if pt_kw.get("device_messages") or pt_kw.get("transport") == "group":
+        for g, e in enumerate(many.shards.engines):      # side 0: the pair below the shard's first chain, side 1: the pair above its last
+            want = [counts[g - 1] if g > 0 else 0, counts[g] if g < G - 1 else 0]
+            assert list(e.shard_sync()) == want and list(e.comm_info()[2]) == want, (g, want, e.shard_sync(), e.comm_info()[2])
+    else:
+        assert many.shards.n_boundary_swaps == sum(counts), (many.shards.n_boundary_swaps, counts)
+    return counts
 
 
 def assert_checkpoint_resume(P, make_inputs, tmp_path):

@@ -165,7 +165,7 @@ def test_compose_slice_automala_runs(P):
 
 @pytest.mark.parametrize("explorer", ["slice", "automala"])
 def test_sharded_equals_single_engine(P, explorer):
-    mk = lambda: _inputs(P, seed=4, n_rounds=4, explorer=P.SliceSampler() if explorer == "slice" else P.AutoMALA())
+    mk = lambda: G.with_recorders(P, _inputs(P, seed=4, n_rounds=4, explorer=P.SliceSampler() if explorer == "slice" else P.AutoMALA()), "online")
     G.assert_sharded_equals_single(P, mk, n_shards=2)
 
 

@@ -263,7 +263,7 @@ def test_two_runs_are_equal_bit_for_bit(P):
 
 
 def test_sharded_equals_single_engine(P):
-    G.assert_sharded_equals_single(P, lambda: _inputs(P, seed=4, n_rounds=4), n_shards=2)
+    G.assert_sharded_equals_single(P, lambda: G.with_recorders(P, _inputs(P, seed=4, n_rounds=4), "online"), n_shards=2)
 
 
 def test_checkpoint_resume_equals_uninterrupted(P, tmp_path):
