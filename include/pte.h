@@ -477,6 +477,30 @@ int pte_overlap_cluster_move(pte_overlap *ov);
 int pte_overlap_cluster_get(const pte_overlap *ov, int64_t *n, int64_t *empty, int64_t *size_sum, int64_t *k_sum, int64_t *abs_ds_sum, int64_t *passes_sum,
                             int64_t *moves_launched);
 
+/* ---- the plane autocorrelation of the overlap field (the project's own specification; off after pte_overlap_create) ----
+ * What the wave-vector-dependent spin-glass susceptibility chi_SG(k) along the lattice axes and the correlation length xi_L are computed
+ * from.  n_axes = 3 on the cube, 2 on the 2-D lattices; axis 0 is the fastest site index (x of site (z, y, x) at (z L + y) L + x; the
+ * column j of site (i, j) at i L + j), axis 1 the next (y; the row i), axis 2 the cube's z; L = base_length, M = dim / L.  For chain c, with
+ * t = a XOR b as above, a record taken while the feature is on adds, as exact integers,
+ *   P_axis[p]  = the set bits of t among the M sites whose coordinate along the axis is p, p = 0 .. L - 1
+ *   Q_axis[p]  = M - 2 P_axis[p]                             the sum of q_i = s_i^a s_i^b over that plane (2-D: that line)
+ *   C_axis(r)  = sum_p Q_axis[p] Q_axis[(p + r) mod L]       to plane_corr[c][axis][r], r = 0 .. L - 1, and 1 to plane_n[c]
+ * C(r) = C(L - r) and |C| <= L M^2.  On the host, along an axis and with k = 2 pi m / L,
+ *   chi_SG(m) = (1 / (dim plane_n)) sum_r plane_corr[c][axis][r] cos(2 pi m r / L),   chi_SG(0) = dim <q^2>
+ *   xi_L      = 1 / (2 sin(pi / L)) sqrt(chi_SG(0) / chi_SG(1) - 1)
+ * and sum_r plane_corr[c][axis][r] == sum_k hist[c][k] (dim - 2 k)^2 on every axis when every record of the round was taken with the
+ * feature on.  It runs where the link overlap is recorded: the cube at every base_length, the 2-D lattices where base_length % 32 == 0.
+ *   pte_overlap_set_planes    on != 0: pte_overlap_record and pte_overlap_run_scans launch the kernel right after the record's own
+ *                             (behind a cluster move of the same scan); 0: they do not.  Refuses, naming the base length, a 2-D lattice
+ *                             whose base_length is not a multiple of 32.  The accumulators are allocated at the first on != 0: with the
+ *                             feature never on, no call makes a launch, a copy or an allocation on its account
+ *   pte_overlap_planes_info   n_axes (0 where the feature cannot run), base_length, on (0 / 1); NULLs are skipped
+ *   pte_overlap_planes_get    the snapshot taken by pte_overlap_reduce, which zeroes these accumulators with the others:
+ *                             plane_n[N], plane_corr[N][n_axes][base_length] (zeros if the feature was never on); NULLs are skipped */
+int pte_overlap_set_planes(pte_overlap *ov, int on);
+int pte_overlap_planes_info(const pte_overlap *ov, int64_t *n_axes, int64_t *base_length, int64_t *on);
+int pte_overlap_planes_get(const pte_overlap *ov, int64_t *plane_n, int64_t *plane_corr);
+
 /* Name of the kernel that explores on this engine (e.g. "k_explore_slice8"), for profiles and bench.py. */
 const char *pte_kernel_name(const pte_engine *h);
 

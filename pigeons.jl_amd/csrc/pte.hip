@@ -37,6 +37,7 @@
 #include "pte_lattice3d_params.hpp"
 #include "pte_overlap_params.hpp"
 #include "pte_cluster_params.hpp"
+#include "pte_overlap_planes_params.hpp"
 #else                              // tools / development builds: one translation unit
 #include "pte_langevin_launch.hpp"
 #include "pte_aaps.hpp"
@@ -53,6 +54,7 @@
 #include "pte_lattice3d.hpp"
 #include "pte_overlap.hpp"
 #include "pte_cluster.hpp"
+#include "pte_overlap_planes.hpp"
 #endif
 #include "pte_ising.hpp"
 #if defined(PTE_PROFILE_AM)               // debug builds only (tools/prof_automala.py): 12 words per wave, section times of k_explore_automala
@@ -2151,6 +2153,12 @@ struct pte_overlap {
     uint64_t cl_seed = 0, cl_m = 0;       // the move's own stream: the seed and the launch counter
     int64_t cl_launched = 0;              // launches since the last pte_overlap_reduce
     std::vector<int64_t> cl_snap;         // the six accumulators of the last pte_overlap_reduce, then the launches it covers
+    // the plane autocorrelation (pte_overlap_planes.hpp): off until pte_overlap_set_planes, which makes the allocation
+    int pl_axes = 0;                      // 3 on the cube, 2 on the square, 0 where the kernel does not run
+    bool pl_on = false;
+    int64_t *d_pl = nullptr;              // one allocation: plane_n [N], plane_corr [N][pl_axes][L]
+    size_t pl_words = 0;                  // its int64 words
+    std::vector<int64_t> pl_snap;         // the two accumulators of the last pte_overlap_reduce
 };
 
 namespace {
@@ -2182,6 +2190,7 @@ int overlap_entry(pte_overlap *ov, const char *what) {
 
 // one cluster move and / or one record on A's stream, the move first, ordered behind what B's stream holds so far; B's stream then waits for
 // them: one hand-over whatever is launched.  The move writes both engines' rows and suff; the record reads t = a xor b, which the move leaves
+// as it was.  With the plane autocorrelation on a record is two launches, k_overlap and then k_overlap_planes: both only read
 int overlap_enqueue(pte_overlap *ov, bool move, bool record) {
     pte_engine *a = ov->a, *b = ov->b;
     HIP_OK(a, hipEventRecord(ov->ev_b, b->stream));
@@ -2199,6 +2208,9 @@ int overlap_enqueue(pte_overlap *ov, bool move, bool record) {
     if (record && overlap_launch(a->stream, OverlapSide{a->dev.x, a->dev.ld, a->dev.slot_of_chain}, OverlapSide{b->dev.x, b->dev.ld, b->dev.slot_of_chain},
                                  (int)ov->d, (int)ov->N, ov->geom, ov->L, ov->acc))
         return fail(a, "this build holds no overlap kernel for dim %lld", (long long)ov->d);
+    if (record && ov->pl_on && planes_launch(a->stream, OverlapSide{a->dev.x, a->dev.ld, a->dev.slot_of_chain}, OverlapSide{b->dev.x, b->dev.ld, b->dev.slot_of_chain},
+                                             (int)ov->d, (int)ov->N, ov->geom, ov->L, PlanesAcc{ov->d_pl, ov->d_pl + ov->N}))
+        return fail(a, "this build holds no plane-correlation kernel for dim %lld", (long long)ov->d);
     HIP_OK(a, hipGetLastError());
     HIP_OK(a, hipEventRecord(ov->ev_rec, a->stream));
     HIP_OK(a, hipStreamWaitEvent(b->stream, ov->ev_rec, 0));
@@ -2271,6 +2283,9 @@ int pte_overlap_create(pte_engine *a, pte_engine *b, pte_overlap **out) {
     ov->snap.assign(ov->words, 0);
     ov->cl_acc = ClusterAcc{ov->d_cl};
     ov->cl_snap.assign(CLUSTER_ACC_ARRAYS * (size_t)N + 1, 0);
+    ov->pl_axes = planes_axes(ov->geom);
+    ov->pl_words = (size_t)N + (size_t)N * (size_t)ov->pl_axes * (size_t)ov->L;
+    ov->pl_snap.assign(ov->pl_words, 0);
     *out = ov;
     return 0;
 }
@@ -2283,6 +2298,7 @@ int pte_overlap_destroy(pte_overlap *ov) {
     if (ov->ev_rec) hipEventDestroy(ov->ev_rec);
     if (ov->d_acc) hipFree(ov->d_acc);
     if (ov->d_cl) hipFree(ov->d_cl);
+    if (ov->d_pl) hipFree(ov->d_pl);
     delete ov;
     return 0;
 }
@@ -2335,6 +2351,10 @@ int pte_overlap_reduce(pte_overlap *ov) {
     HIP_OK(a, hipMemsetAsync(ov->d_acc, 0, sizeof(int64_t) * ov->words, a->stream));
     HIP_OK(a, hipMemcpyAsync(ov->cl_snap.data(), ov->d_cl, sizeof(int64_t) * 6 * (size_t)ov->N, hipMemcpyDeviceToHost, a->stream));
     HIP_OK(a, hipMemsetAsync(ov->d_cl, 0, sizeof(int64_t) * 6 * (size_t)ov->N, a->stream));
+    if (ov->d_pl) {
+        HIP_OK(a, hipMemcpyAsync(ov->pl_snap.data(), ov->d_pl, sizeof(int64_t) * ov->pl_words, hipMemcpyDeviceToHost, a->stream));
+        HIP_OK(a, hipMemsetAsync(ov->d_pl, 0, sizeof(int64_t) * ov->pl_words, a->stream));
+    }
     HIP_OK(a, hipStreamSynchronize(a->stream));
     ov->cl_snap[6 * (size_t)ov->N] = ov->cl_launched;
     ov->cl_launched = 0;
@@ -2387,6 +2407,44 @@ int pte_overlap_cluster_get(const pte_overlap *ov, int64_t *n, int64_t *empty, i
     for (int i = 0; i < 6; ++i)
         if (out[i]) std::memcpy(out[i], s + i * N, sizeof(int64_t) * N);
     if (moves_launched) *moves_launched = s[6 * N];
+    return 0;
+}
+
+// The plane autocorrelation.  Host, once per call: the refusal, then the switch the records read.  The accumulators are
+// allocated when the feature is first turned on: a pair that never asks for it makes no allocation, copy or launch on its account.
+int pte_overlap_set_planes(pte_overlap *ov, int on) {
+    if (!ov) return 1;
+    pte_engine *a = ov->a;
+    if (ov->geom == OVERLAP_GEOM_NONE)
+        return fail(a, "pte_overlap_set_planes: on the 2-D lattices the plane sums are recorded where base_length %% 32 == 0 (got base_length %d): the rows "
+                       "are whole words only there", ov->L);
+    if (on && !ov->d_pl) {
+        HIP_OK(a, hipSetDevice(ov->device));
+        int64_t *p = nullptr;
+        HIP_OK(a, hipMalloc((void **)&p, sizeof(int64_t) * ov->pl_words));
+        hipError_t e = hipMemsetAsync(p, 0, sizeof(int64_t) * ov->pl_words, a->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(a->stream);
+        if (e != hipSuccess) { hipFree(p); return fail(a, "pte_overlap_set_planes: %s", hipGetErrorString(e)); }
+        ov->d_pl = p;
+    }
+    ov->pl_on = on != 0;
+    return 0;
+}
+
+int pte_overlap_planes_info(const pte_overlap *ov, int64_t *n_axes, int64_t *base_length, int64_t *on) {
+    if (!ov) return 1;
+    if (n_axes) *n_axes = ov->pl_axes;
+    if (base_length) *base_length = ov->L;
+    if (on) *on = ov->pl_on ? 1 : 0;
+    return 0;
+}
+
+int pte_overlap_planes_get(const pte_overlap *ov, int64_t *plane_n, int64_t *plane_corr) {
+    if (!ov) return 1;
+    const size_t N = (size_t)ov->N;
+    const int64_t *s = ov->pl_snap.data();
+    if (plane_n) std::memcpy(plane_n, s, sizeof(int64_t) * N);
+    if (plane_corr && ov->pl_words > N) std::memcpy(plane_corr, s + N, sizeof(int64_t) * (ov->pl_words - N));
     return 0;
 }
 

@@ -16,6 +16,10 @@
 //   pte_spinglass.hip the spin-glass kernels (pte_spinglass.hpp) with pte.hip's flags: they are the Ising kernels with bonds
 //   pte_checkerboard.hip the CheckerboardMetropolis kernels of both lattice targets (pte_checkerboard.hpp) with pte_spinglass.hip's flags
 //   pte_lattice3d.hip the 3-D spin-glass kernels (pte_lattice3d.hpp) with pte_spinglass.hip's flags
+//   pte_overlap.hip, pte_cluster.hip, pte_overlap_planes.hip
+//                     the kernels of a lattice pair, a unit and a list each (OVERLAP_UNITS, CLUSTER_UNITS, PLANES_UNITS) with
+//                     pte_lattice3d.hip's flags: the replica overlap (pte_overlap.hpp), Houdayer's cluster move (pte_cluster.hpp,
+//                     DESIGN 4.21) and the plane autocorrelation behind chi_SG(k) and xi_L (pte_overlap_planes.hpp) -- fourteen in all
 // Every unit includes pte_kernels.hpp and therefore holds its own copy of the `static __device__` word g_rng_policy: PTE_KERNEL_UNITS below.
 // Tools and development builds compile pte.hip alone (no -DPTE_SPLIT_LANGEVIN): it then includes the kernel headers and their entry points itself.
 #pragma once

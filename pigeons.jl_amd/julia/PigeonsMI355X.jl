@@ -696,4 +696,24 @@ function cluster_record(o::DeviceOverlap)
     return (n = n, empty = empty, size_sum = size_sum, k_sum = k_sum, abs_ds_sum = abs_ds_sum, passes_sum = passes_sum, moves_launched = launched[])
 end
 
+# the plane autocorrelation of the overlap field (include/pte.h pte_overlap_*planes*; DESIGN 4.22): chi_SG(k) along the axes and xi_L
+"""`on = true`: every record from now on also adds the plane autocorrelation; refused on a 2-D lattice whose base length is not a
+multiple of 32."""
+set_planes!(o::DeviceOverlap, on::Bool = true) = check(o.a, ccall((:pte_overlap_set_planes, libpte), Cint, (Ptr{Cvoid}, Cint), o.handle, on ? 1 : 0))
+"""-> (n_axes, base_length, on); `n_axes == 0`: the plane sums are not recorded on this lattice"""
+function planes_info(o::DeviceOverlap)
+    na, bl, on = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+    check(o.a, ccall((:pte_overlap_planes_info, libpte), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}), o.handle, na, bl, on))
+    return (n_axes = Int(na[]), base_length = Int(bl[]), on = on[] != 0)
+end
+"""-> the plane accumulators of the last `reduce!`, Int64: `plane_n [N]` and `plane_corr [L, n_axes, N]` (the ABI's row-major
+`[N][n_axes][L]`: `plane_corr[r + 1, axis + 1, c + 1]` is the sum of C_axis(r) of chain c)"""
+function planes_record(o::DeviceOverlap)
+    info = planes_info(o)
+    plane_n = zeros(Int64, o.n_chains)
+    plane_corr = zeros(Int64, info.base_length, info.n_axes, o.n_chains)
+    check(o.a, ccall((:pte_overlap_planes_get, libpte), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), o.handle, plane_n, plane_corr))
+    return (plane_n = plane_n, plane_corr = plane_corr)
+end
+
 end # module

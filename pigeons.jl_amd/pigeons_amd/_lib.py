@@ -101,6 +101,7 @@ EXPORTS = [
     "pte_overlap_create", "pte_overlap_destroy", "pte_overlap_info", "pte_overlap_record", "pte_overlap_run_scans", "pte_overlap_reduce",
     "pte_overlap_get",
     "pte_overlap_set_cluster_move", "pte_overlap_cluster_move", "pte_overlap_cluster_get",
+    "pte_overlap_set_planes", "pte_overlap_planes_info", "pte_overlap_planes_get",
 ]
 
 _libs = {}
@@ -224,6 +225,9 @@ def load(path=None):
     L.pte_overlap_set_cluster_move.argtypes = [vp, C.c_int64, C.c_double, C.c_uint64]
     L.pte_overlap_cluster_move.argtypes = [vp]
     L.pte_overlap_cluster_get.argtypes = [vp, ip, ip, ip, ip, ip, ip, ip]
+    L.pte_overlap_set_planes.argtypes = [vp, C.c_int]
+    L.pte_overlap_planes_info.argtypes = [vp, ip, ip, ip]
+    L.pte_overlap_planes_get.argtypes = [vp, ip, ip]
     for name in EXPORTS:
         if name not in ("pte_last_error", "pte_boundary_payload_bytes", "pte_get_stream", "pte_shard_message_bytes", "pte_kernel_name", "pte_scan_loop_name"):
             getattr(L, name).restype = C.c_int

@@ -15,11 +15,21 @@ leaves the sum of the two energies as it was -- always accepted, and non-local w
 
   HoudayerMove(every, min_beta, seed)   the setting: Overlap.set_cluster_move(move), pigeons_pair(cluster_move=move)
   ClusterRecord                         the reduced accumulators of the move
+
+The scalar overlap is the k = 0 term of the quantity a spin-glass study is built around, the wave-vector-dependent susceptibility
+chi_SG(k) = (1 / d) <|sum_i q_i exp(i k . x_i)|^2>, q_i = s_i^a s_i^b, and the finite-size correlation length xi_L derived from it, whose
+ratio xi_L / L crosses at the transition.  For k along a lattice axis both follow from the autocorrelation of the plane sums
+of q, which the device adds up per chain and per record as exact integers.  Off unless asked for.
+
+  Overlap.set_planes(on), pigeons_pair(wave_vector=True)   the switch
+  OverlapRecord.plane_n, .plane_corr                       the reduced accumulators (None when the feature is off)
+  OverlapRecord.chi_sg(m), .correlation_length()           chi_SG(2 pi m / L) per chain and axis; xi_L, xi_L / L per chain
 """
 import ctypes as C
 import dataclasses
+import math
 import time
-from dataclasses import dataclass
+from dataclasses import InitVar, dataclass
 from typing import Any
 
 import numpy as np
@@ -45,6 +55,47 @@ class OverlapRecord:
     link_n: Any         # [N]        records with a link overlap
     link_sum: Any       # [N]        sum of kl
     link_sum2: Any      # [N]        sum of kl^2
+    # the plane autocorrelation, None unless the feature was on.  Init-only: they are set as attributes of the same names, and
+    # dataclasses.fields() stays the eight accumulators of 4.20 that code written against it enumerates
+    plane_n: InitVar[Any] = None       # [N]              records taken with the feature on
+    plane_corr: InitVar[Any] = None    # [N][n_axes][L]   sum over those records of C_axis(r) = sum_p Q_axis[p] Q_axis[(p + r) mod L]
+
+    def __post_init__(self, plane_n, plane_corr):
+        self.plane_n, self.plane_corr = plane_n, plane_corr
+
+    def chi_sg(self, m=1):
+        """chi_SG at the wave vector 2 pi m / L along every axis, float64 [N][n_axes]:  (1 / (d plane_n)) sum_r plane_corr[c][axis][r]
+        cos(2 pi m r / L), from Python integers (the sine part vanishes: C(r) = C(L - r)); chi_sg(0) = d <q^2> on every axis.  None when
+        the plane sums were not recorded; NaN where a chain has no record."""
+        if self.plane_corr is None:
+            return None
+        corr = np.asarray(self.plane_corr)
+        N, n_axes, L = corr.shape
+        w = [_cos_turn((int(m) * r) % L, L) for r in range(L)]
+        out = np.full((N, n_axes), np.nan)
+        for c in range(N):
+            n = int(self.plane_n[c])
+            if n <= 0:
+                continue
+            for ax in range(n_axes):
+                vals = [int(v) for v in corr[c, ax]]
+                num = float(sum(vals)) if int(m) % L == 0 else math.fsum(v * wr for v, wr in zip(vals, w))
+                out[c, ax] = num / (float(self.dim) * n)
+        return out
+
+    def correlation_length(self):
+        """per chain, float64 [N]: chi0 = chi_SG(0), chi_kmin = the mean over the axes of chi_SG(k_min), k_min = 2 pi / L,
+        xi = sqrt(chi0 / chi_kmin - 1) / (2 sin(k_min / 2)) and xi_over_L.  xi is NaN where chi_kmin <= 0, where chi0 / chi_kmin < 1 and
+        where a chain has no record.  None when the plane sums were not recorded."""
+        if self.plane_corr is None:
+            return None
+        L = np.asarray(self.plane_corr).shape[2]
+        chi0, chi_kmin = self.chi_sg(0).mean(axis=1), self.chi_sg(1).mean(axis=1)
+        xi = np.full(len(chi0), np.nan)
+        for c in range(len(chi0)):
+            if chi_kmin[c] > 0.0 and chi0[c] / chi_kmin[c] >= 1.0:
+                xi[c] = math.sqrt(chi0[c] / chi_kmin[c] - 1.0) / (2.0 * math.sin(math.pi / L))
+        return dict(xi=xi, xi_over_L=xi / L, chi0=chi0, chi_kmin=chi_kmin)
 
     def q_values(self):
         """q of every bin: 1 - 2 k / d, k = 0 .. d"""
@@ -68,6 +119,18 @@ class OverlapRecord:
                         ql_var[c] = 4.0 * ((m * s2 - s1 * s1) / (m * m)) / (self.n_links * self.n_links)
                 out.update(ql=ql, ql_var=ql_var)
         return out
+
+
+def _cos_turn(j, L):
+    """cos(2 pi j / L), 0 <= j < L, folded into the first quarter turn so that the table is symmetric and antisymmetric to the last bit: a
+    constant C(r) then sums to exactly 0 at every m != 0"""
+    if 2 * j > L:
+        j = L - j
+    if 4 * j == L:
+        return 0.0
+    if 4 * j > L and L % 2 == 0:
+        return -math.cos(2.0 * math.pi * (L // 2 - j) / L)
+    return math.cos(2.0 * math.pi * j / L)
 
 
 @dataclass
@@ -116,6 +179,15 @@ def cluster_move_geometry(target):
             "bond planes exist only there" % int(target.base_length))
 
 
+def planes_geometry(target):
+    """None where the plane sums are recorded on this lattice target (the cube; the 2-D lattices with base_length % 32 == 0), else the
+    refusal's text"""
+    if isinstance(target, SpinGlass3DLogPotential) or int(target.base_length) % 32 == 0:
+        return None
+    return ("wave_vector=True runs on the cube and on the 2-D lattices whose base_length is a multiple of 32 (got base_length %d): the rows "
+            "are whole words only there" % int(target.base_length))
+
+
 class Overlap:
     """pte_overlap_*: the overlap recorder over two engines.  It holds no state of either engine; close() leaves both usable."""
 
@@ -130,6 +202,9 @@ class Overlap:
         info = np.zeros(3, dtype=np.int64)
         self._chk(self.L.pte_overlap_info(h, _ip(info[0:1]), _ip(info[1:2]), _ip(info[2:3])))
         self.N, self.d, self.n_links = int(info[0]), int(info[1]), int(info[2])
+        self._chk(self.L.pte_overlap_planes_info(h, _ip(info[0:1]), _ip(info[1:2]), _ip(info[2:3])))
+        self.n_axes, self.base_length = int(info[0]), int(info[1])      # n_axes == 0: the plane sums are not recorded on this lattice
+        self._planes = False                                           # set_planes(True) was called at some time
 
     def _chk(self, rc):
         if rc != 0:
@@ -162,7 +237,23 @@ class Overlap:
         hist = np.zeros((self.N, self.d + 1), dtype=np.int64)
         self._chk(self.L.pte_overlap_get(self.h, _ip(n), _ip(hist), _ip(link_n), _ip(link_sum), _ip(link_sum2)))
         self._cluster_betas = betas
-        return OverlapRecord(betas, self.d, self.n_links, n, hist, link_n, link_sum, link_sum2)
+        plane_n = plane_corr = None
+        if self._planes:
+            plane_n, plane_corr = np.zeros(self.N, dtype=np.int64), np.zeros((self.N, self.n_axes, self.base_length), dtype=np.int64)
+            self._chk(self.L.pte_overlap_planes_get(self.h, _ip(plane_n), _ip(plane_corr)))
+            if not (self.planes_on() or plane_n.any()):                # off, and off at every record of the round
+                plane_n = plane_corr = None
+        return OverlapRecord(betas, self.d, self.n_links, n, hist, link_n, link_sum, link_sum2, plane_n, plane_corr)
+
+    def set_planes(self, on=True):
+        """record the plane autocorrelation (OverlapRecord.plane_n, .plane_corr) at every record from now on, or stop"""
+        self._chk(self.L.pte_overlap_set_planes(self.h, 1 if on else 0))
+        self._planes = self._planes or bool(on)
+
+    def planes_on(self):
+        on = np.zeros(1, dtype=np.int64)
+        self._chk(self.L.pte_overlap_planes_info(self.h, None, None, _ip(on)))
+        return bool(on[0])
 
     def set_cluster_move(self, move, seed=None):
         """the setting of Houdayer's cluster move from now on (move.seed None: `seed`); the launch counter of its stream starts again from 0"""
@@ -201,7 +292,7 @@ class PTPair:
         self.cluster, self.clusters = None, []          # its ClusterRecord of the last round and of every round
 
 
-def check_pair_inputs(inputs, seed_b, pt_kwargs=(), cluster_move=None):
+def check_pair_inputs(inputs, seed_b, pt_kwargs=(), cluster_move=None, wave_vector=False):
     """what a pair refuses, before any device work"""
     if cluster_move is not None and not isinstance(cluster_move, HoudayerMove):
         raise TypeError("pigeons_pair: cluster_move must be None or a HoudayerMove (got %r)" % (cluster_move,))
@@ -220,6 +311,8 @@ def check_pair_inputs(inputs, seed_b, pt_kwargs=(), cluster_move=None):
         raise ValueError("pigeons_pair: seed_b must differ from seed (both %d): identical runs give q = 1 at every record" % inputs.seed)
     if cluster_move is not None and cluster_move_geometry(inputs.target):
         raise NotImplementedError("pigeons_pair: " + cluster_move_geometry(inputs.target))
+    if wave_vector and planes_geometry(inputs.target):
+        raise NotImplementedError("pigeons_pair: " + planes_geometry(inputs.target))
 
 
 def run_pair_round(pair):
@@ -257,21 +350,24 @@ def adapt_pair(pair, red_a, red_b):
     return pair
 
 
-def pigeons_pair(seed_b=None, cluster_move=None, **inputs_kwargs):
+def pigeons_pair(seed_b=None, cluster_move=None, wave_vector=False, **inputs_kwargs):
     """pigeons(; ...) twice over, in step: two PTs over the same target and inputs with seeds `seed` and `seed_b` (default seed + 1), the
     overlap between them recorded at every scan -> PTPair.  Only the first run prints its report.  cluster_move: None, or the HoudayerMove
-    made between the two copies (its accumulators per round in pair.clusters, the last in pair.cluster)."""
+    made between the two copies (its accumulators per round in pair.clusters, the last in pair.cluster).  wave_vector=True: every record
+    also adds the plane autocorrelation, from which OverlapRecord.chi_sg() and .correlation_length() follow."""
     pt_kwargs = {k: inputs_kwargs.pop(k) for k in SHARDING_ARGUMENTS if k in inputs_kwargs}
     inputs = Inputs(**inputs_kwargs)
     if seed_b is None:
         seed_b = inputs.seed + 1
-    check_pair_inputs(inputs, seed_b, pt_kwargs, cluster_move)
+    check_pair_inputs(inputs, seed_b, pt_kwargs, cluster_move, wave_vector)
     a = PT(inputs)
     b = PT(dataclasses.replace(inputs, seed=seed_b, show_report=False, record=list(inputs.record)))
     pair = PTPair(a, b, Overlap(a.replicas, b.replicas))
     pair.cluster_move = cluster_move
     if cluster_move is not None:
         pair.recorder.set_cluster_move(cluster_move, seed=inputs.seed)
+    if wave_vector:
+        pair.recorder.set_planes(True)
     while next_round(a) and next_round(b):
         adapt_pair(pair, *run_pair_round(pair))
         report(a)

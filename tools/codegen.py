@@ -47,7 +47,7 @@ def _key(g, src, unit_flags, extra):
 
 def compile_units(extra=(), force=False, units=None):
     """-> [(source, command, path of the .s, text of the resource remarks)] for the product's translation units (units = None: __graft_entry__.UNITS,
-    the eight whose code tests/test_codegen_frozen.py freezes; or a list such as __graft_entry__.LATTICE_UNITS, CHECKERBOARD_UNITS, LATTICE3D_UNITS, OVERLAP_UNITS or CLUSTER_UNITS), compiled in parallel, cached"""
+    the eight whose code tests/test_codegen_frozen.py freezes; or a list such as __graft_entry__.LATTICE_UNITS, CHECKERBOARD_UNITS, LATTICE3D_UNITS, OVERLAP_UNITS, CLUSTER_UNITS or PLANES_UNITS), compiled in parallel, cached"""
     g = _graft()
     os.makedirs(CACHE, exist_ok=True)
     jobs = []
@@ -70,7 +70,7 @@ def compile_units(extra=(), force=False, units=None):
     with ThreadPoolExecutor(len(jobs)) as ex:
         out = list(ex.map(run, jobs))
     # prune: an assembly file is 15-40 MB (and build/ travels with every gpurun snapshot); keep what this call produced, nothing else
-    keep = set("%s.%s" % (os.path.splitext(src)[0], _key(g, src, unit_flags, extra)) for src, unit_flags in list(g.UNITS) + list(g.LATTICE_UNITS) + list(g.CHECKERBOARD_UNITS) + list(g.LATTICE3D_UNITS) + list(g.OVERLAP_UNITS) + list(g.CLUSTER_UNITS))
+    keep = set("%s.%s" % (os.path.splitext(src)[0], _key(g, src, unit_flags, extra)) for src, unit_flags in list(g.UNITS) + list(g.LATTICE_UNITS) + list(g.CHECKERBOARD_UNITS) + list(g.LATTICE3D_UNITS) + list(g.OVERLAP_UNITS) + list(g.CLUSTER_UNITS) + list(g.PLANES_UNITS))
     for f in os.listdir(CACHE):
         full = os.path.join(CACHE, f)
         if not extra and f.rsplit(".", 1)[0] not in keep:
