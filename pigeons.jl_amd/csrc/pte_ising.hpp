@@ -61,6 +61,8 @@ __device__ inline long long ising_recompute(const unsigned char *sp, int L, int 
 // round instead of 3.8, tools/diag_regimes.py.)
 // The thresholds as doubles (the byte-lattice sweep) and as integer bit patterns held in scalar registers (the bit-packed sweeps: bit
 // patterns of positive doubles are ordered like the doubles): the high words for the filter, the whole patterns for the band.
+// (In the band the byte body takes its uniform before it has the ratio, the bit-packed bodies take none when ratio >= 1: the same
+// thing, since filter_ok keeps the rounded exponent < 0 and so the ratio < 1.)
 struct LatticeThresholds {
     double r4lo, r4hi, r8lo, r8hi;
     unsigned r4lo_h, r4hi_h, r8lo_h, r8hi_h;

@@ -51,20 +51,28 @@ def flip_probability(b, s, jr, jd, L, beta, beta_target, delta_bonds=None):
     return min(1.0, math.exp(ising_lp(beta, beta_target, S + delta) - ising_lp(beta, beta_target, S)))
 
 
-def sweep(bits, jr, jd, beta, beta_target, S, rng, n_steps):
+def sweep(bits, jr, jd, beta, beta_target, S, rng, n_steps, log=None):
     """IsingMetropolis(n_steps) on one replica, in place on the flat list `bits`: the draw order of k_explore_ising, statement for statement.
-    rng: oracle.OracleRng.  Returns the new S."""
+    rng: oracle.OracleRng (anything with rand()).  Returns the new S.  log: a list; every draw appends
+    (k, step, site, delta, S_before, u, ratio, rejected), k = 1, 2, ... the draw's number since entry (tests/lattice_band.py)."""
     L = int(np.asarray(jr).shape[0])
     jrf = [int(v) for v in np.asarray(jr).ravel()]
     jdf = [int(v) for v in np.asarray(jd).ravel()]
     d = L * L
-    for _ in range(n_steps):
+    k = 0
+    for step in range(n_steps):
         for s in range(d):
             delta = site_delta(bits, jrf, jdf, L, s)
             if delta < 0:
                 ratio = math.exp(ising_lp(beta, beta_target, S + delta) - ising_lp(beta, beta_target, S))
-                if ratio < 1 and rng.rand() > ratio:
-                    continue
+                if ratio < 1:
+                    u = rng.rand()
+                    k += 1
+                    rejected = u > ratio
+                    if log is not None:
+                        log.append((k, step, s, delta, S, u, ratio, rejected))
+                    if rejected:
+                        continue
             bits[s] ^= 1
             S += delta
     return S
